@@ -1,8 +1,14 @@
 """Benchmark: 720p frames/s decoded+scored per node (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
                     [--config 720p-batch|720p-10min|720p-2h|1080p-2h|480p-60s]
                     [--workload decode_score|score|transcode] [--extras all|none]
+
+A plain run sets up, warms up, times the K steps, writes the last step's
+outputs when --dump-outputs is given and prints the result line (metric, value,
+unit, ms_per_step, ...).  Everything else below (roofline, rocprofv3 passes,
+parity, cpu_baseline, extras) takes runs of its own and is measured only with
+--full.
 
 One process per GPU: under a launcher (torch.distributed.run) RANK/LOCAL_RANK/
 WORLD_SIZE come from the env and must agree with --gpus; a plain
@@ -27,7 +33,8 @@ before the warm-up, and only the per-frame work runs inside it.
                  + scoring, through plan_batch
   score        : scoring kernel only, on pre-decoded NV12 frames (one video)
   transcode    : the 360p upload transcode (one video)
-Rank 0 prints ONE JSON line (contract in the task statement), including
+Rank 0 prints ONE JSON line (contract in the task statement); with --full it
+includes
   roofline     : the dominant kernel; `achieved`/`frac` on SURVEY 8(d)'s
                  algorithmic bytes per frame, kernel time = busy time (union of
                  dispatch intervals) per dispatch from a rocprofv3 kernel trace
@@ -52,6 +59,11 @@ Rank 0 prints ONE JSON line (contract in the task statement), including
                  stream's bits per frame and planted vs detected scene cuts.
 The rocprofv3 passes are child processes started before this process touches
 the GPU; --profile-dir keeps their summaries.
+
+--dump-outputs DIR writes what the last timed step handed to its caller as
+DIR/<name>.npy (float32 / float64, at most 64 MB in all; see dump_outputs).
+The inputs are seeded, so two builds run with the same arguments can be
+compared file for file.
 """
 from __future__ import annotations
 
@@ -256,7 +268,7 @@ def profile_passes(argv: list[str], out_dir: Path, keep_dir: Path | None,
     res: dict = {}
     env = dict(os.environ, TMPDIR="/tmp")
     child = [sys.executable, str(Path(__file__).resolve()), *argv, "--steps", "1", "--warmup", "1",
-             "--no-cpu-baseline", "--no-pmc", "--no-parity", "--extras", "none"]
+             "--full", "--no-cpu-baseline", "--no-pmc", "--no-parity", "--extras", "none"]
     for pi, what in enumerate(passes):
         d = out_dir / f"p{pi}"
         counters = what.split()
@@ -494,6 +506,96 @@ def roofline_decode_score(scorers, prof: dict | None, width: int, height: int, k
                      "read + NV12 frame write + RGB + thumbnail luma write + predecessor "
                      "read + histogram + SAD"}
     return roof
+
+
+# ------------------------------------------------------------ --dump-outputs
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # all files of one --dump-outputs DIR together
+DUMP_SEED = 0xD0
+_NPY_HEADER = 128                    # an .npy file's header, rounded up
+
+
+def _dump_array(a, budget: int, rng) -> tuple[np.ndarray, np.ndarray | None]:
+    """`a` (numpy array or torch tensor, any dtype) as float32, or float64
+    where float32 could round it (32- and 64-bit integers, doubles), cut to at most
+    `budget` bytes: a larger array keeps a sorted, seeded sample of its rows
+    (axis 0), or of its elements when one row is already too large.  Returns
+    (values, the kept row / flat element indices or None when all is kept)."""
+    is_torch = not isinstance(a, np.ndarray) and hasattr(a, "detach")
+    if not is_torch:
+        a = np.asarray(a)
+    dt = str(a.dtype).replace("torch.", "")
+    out_dt = np.float64 if dt in ("int32", "uint32", "int64", "uint64", "float64") else np.float32
+    item = np.dtype(out_dt).itemsize
+    n = int(a.numel()) if is_torch else int(a.size)
+    rows = None
+    if n * item > budget:
+        # the kept indices are written beside the values as float64: 8 bytes each
+        per_row = max(1, n // max(1, a.shape[0]))
+        if a.ndim > 1 and per_row * item + 8 <= budget:
+            rows = np.sort(rng.choice(a.shape[0], size=budget // (per_row * item + 8),
+                                      replace=False))
+        else:
+            a = a.reshape(-1)
+            rows = np.sort(rng.choice(n, size=budget // (item + 8), replace=False))
+        if is_torch:
+            import torch
+            a = a[torch.from_numpy(rows).to(a.device)]
+        else:
+            a = a[rows]
+    if is_torch:
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=out_dt), rows
+
+
+def dump_outputs(out_dir: Path, arrays: dict) -> dict:
+    """Write {name: array} as out_dir/<name>.npy within DUMP_LIMIT_BYTES in
+    all: every array gets an equal share of the limit, and one that needs more
+    is sampled by _dump_array (seeded, so the same rows every run) with the
+    kept indices beside it as <name>.rows.npy (float64, counted in its share).
+    Returns {file name: bytes written}."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays)) - 2 * _NPY_HEADER
+    written = {}
+    for name in sorted(arrays):
+        vals, rows = _dump_array(arrays[name], share, rng)
+        np.save(out_dir / f"{name}.npy", vals)
+        written[f"{name}.npy"] = (out_dir / f"{name}.npy").stat().st_size
+        if rows is not None:
+            np.save(out_dir / f"{name}.rows.npy", rows.astype(np.float64))
+            written[f"{name}.rows.npy"] = (out_dir / f"{name}.rows.npy").stat().st_size
+    assert sum(written.values()) <= DUMP_LIMIT_BYTES, written
+    return written
+
+
+def step_outputs(workload: str, outs: dict) -> dict:
+    """What the last timed step returned to its caller, as arrays by name.
+      decode_score : plan_batch's BatchItems: `records` [videos, 4] = segment
+                     count, scene-cut count, duration (s), scoring failed; per
+                     video i `v<i>_segment_frames` [segments, 2], `v<i>_cut_frames`
+                     and `v<i>_cut_times` (s)
+      score        : score_nv12's device tensors score / sad / hist / rgb /
+                     last_luma
+      transcode    : `facts` = width, height, frames, IDR pictures, I_PCM /
+                     inter / skipped macroblocks, bytes written; `stream` = the
+                     bytes of the MP4 it wrote"""
+    if workload == "score":
+        return {kk: v for kk, v in outs["r"].items() if not kk.startswith("_") and v is not None}
+    if workload == "transcode":
+        f = outs["facts"]
+        facts = [f[kk] for kk in ("width", "height", "n_frames", "n_idr", "pcm_mbs", "inter_mbs",
+                                  "skip_mbs", "bytes_written")]
+        return {"facts": np.array(facts, np.float64),
+                "stream": np.fromfile(outs["out_path"], np.uint8)}
+    items = outs["items"]
+    arrays = {"records": np.array([[it.n_segments, it.n_cuts, it.duration, float(it.score_failed)]
+                                   for it in items], np.float64).reshape(len(items), 4)}
+    for it in items:
+        arrays[f"v{it.index}_segment_frames"] = np.array(it.segment_frames, np.int64).reshape(-1, 2)
+        arrays[f"v{it.index}_cut_frames"] = np.array(it.cut_frames, np.int64)
+        arrays[f"v{it.index}_cut_times"] = np.array(it.cut_times, np.float64)
+    return arrays
 
 
 # ------------------------------------------------------------ rank launcher
@@ -880,6 +982,15 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: roofline, "
+                         "rocprofv3 passes, parity against the oracle, CPU baseline and (N=1) the "
+                         "extras; --no-parity, --no-cpu-baseline, --no-pmc and --extras none "
+                         "switch single parts off again.  Without it a run only warms up, times "
+                         "the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step returned as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all; rank 0 writes)")
     ap.add_argument("--workload", default="decode_score", choices=["decode_score", "score", "transcode"])
     ap.add_argument("--config", default="720p-batch", choices=sorted(CONFIGS),
                     help="BASELINE configuration per GPU; default = config [3]'s per-GPU share "
@@ -923,6 +1034,12 @@ def main() -> None:
     ap.add_argument("--no-pmc", action="store_true",
                     help="skip the rocprofv3 passes (kernel trace and --pmc) of the headline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # a plain run: nothing that takes runs, passes or host work of its own
+        args.no_parity = args.no_cpu_baseline = args.no_pmc = True
+        args.extras = "none"
 
     # --gpus N > 1 with no launcher around us: start the N ranks ourselves
     # (before anything touches the GPU) and exit with their status
@@ -1111,6 +1228,7 @@ def main() -> None:
 
         if args.workload == "transcode":
             out_path = tmpdir / f"small_rank{rank}.mp4"
+            outs["out_path"] = out_path
             v0 = scorers[local_idx[0]]
 
             def step():
@@ -1148,10 +1266,18 @@ def main() -> None:
     value = total_frames / elapsed
     log(f"rank {rank}: {args.steps} steps in {elapsed:.3f} s -> {value:.0f} frames/s")
 
+    # the last timed step's outputs, before anything below runs the path again
+    if args.dump_outputs and rank == 0:
+        written = dump_outputs(Path(args.dump_outputs), step_outputs(args.workload, outs))
+        log(f"--dump-outputs: {len(written)} files, {sum(written.values())} bytes in {args.dump_outputs}")
+
     # ------------------------------------------- roofline (dominant kernel)
+    # the score and decode_score rooflines time runs of their own: --full only
     roof = None
     sl = [scorers[i] for i in local_idx] if scorers else []
-    if args.workload == "score":
+    if args.workload != "transcode" and not args.full:
+        pass
+    elif args.workload == "score":
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         reps = 5
         ev0.record()
@@ -1351,7 +1477,7 @@ def main() -> None:
             **placement(world, ndev),
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u8", "data": "synthetic",
+            "dtype": "u8", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": f"{args.workload}: {cdesc}; synthetic H.264 {width}x{height} "
                                    + ("(full syntax" + (", B pictures" if args.bframes else "") + ") "
                                       if args.coding == "full" else "")

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import importlib
 import json
+import os
 import sys
 from pathlib import Path
 
@@ -22,7 +23,15 @@ REF_SRC = Path("/root/reference/src")
 GOLDEN = Path(__file__).resolve().parent / "golden"
 
 
-@pytest.mark.skipif(not REF_SRC.is_dir(), reason="reference checkout not present")
+def _reference_readable() -> bool:
+    # a checkout this user may not enter counts as absent (is_dir raises on EACCES)
+    try:
+        return REF_SRC.is_dir() and os.access(REF_SRC, os.R_OK | os.X_OK)
+    except OSError:
+        return False
+
+
+@pytest.mark.skipif(not _reference_readable(), reason="reference checkout not present or not readable")
 def test_reference_content_analyzer_with_vtseg_dropin(monkeypatch):
     sys.path.insert(0, str(GOLDEN))
     try:

@@ -1,6 +1,7 @@
 set -o pipefail
-cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
-timeout -k 10 300 python tools/gpu/score_diag.py > gpurun_out/diag.log 2>&1 || { tail -30 gpurun_out/diag.log; exit 1; }
-timeout -k 10 300 python bench.py --workload score --steps 10 --warmup 2 --no-cpu-baseline > gpurun_out/bench_score.log 2>&1 || { tail -30 gpurun_out/bench_score.log; exit 1; }
-cat gpurun_out/bench_score.log
+ROOT=$(cd "$(dirname "$0")/../.." && pwd)
+cd "$ROOT"
+mkdir -p bench_out
+timeout -k 10 300 python tools/gpu/score_diag.py > bench_out/diag.log 2>&1 || { tail -30 bench_out/diag.log; exit 1; }
+timeout -k 10 300 python bench.py --full --workload score --steps 10 --warmup 2 --no-cpu-baseline > bench_out/bench_score.log 2>&1 || { tail -30 bench_out/bench_score.log; exit 1; }
+cat bench_out/bench_score.log
