@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define VTS_ABI_VERSION 8
+#define VTS_ABI_VERSION 9
 
 enum {
   VTS_OK = 0,
@@ -404,7 +404,8 @@ void vts_batch_free(vts_batch *b);
  * -c:v libx264 -crf 28`).  The session's device decoder decodes every frame,
  * an area filter downscales it to (w, height) with w = ffmpeg's scale=-2
  * width, and a device encoder writes H.264 Constrained Baseline: IDR (all
- * I_PCM) every keyint frames (and at scene cuts if asked), P pictures of full-search
+ * I_PCM, or Intra16x16 with intra = 1) every keyint frames (and at scene cuts
+ * if asked), P pictures of full-search
  * integer motion (P_L0_16x16 / P_Skip) with a quantised residual (qp), I_PCM
  * where that residual would cost more; one slice per macroblock row; MP4
  * (moov at the end), video only.  DESIGN.md §11. */
@@ -427,6 +428,13 @@ typedef struct vts_transcode_params {
                               exceed the I_PCM payload; 0 = default 28 (the
                               reference's CRF); < 0 = no residual (inter within
                               max_mb_sad, else I_PCM)                        */
+  int32_t intra;           /* 0: intra macroblocks are I_PCM (every IDR picture,
+                              and P macroblocks whose residual costs more);
+                              1: they are coded as Intra16x16 (Horizontal / DC
+                              from the left macroblock, Hadamard DC, 4x4
+                              residual at qp) where that takes no more bits
+                              than I_PCM; needs residual coding (qp >= 0).
+                              Any other value: VTS_E_INVALID                 */
 } vts_transcode_params;
 
 typedef struct vts_transcode_info {
@@ -438,6 +446,11 @@ typedef struct vts_transcode_info {
   double ms[4];            /* decode+score+downscale (host clock), motion
                               search span (stream 1), slice writing span
                               (stream 2, overlaps the searches), MP4 mux      */
+  int64_t intra_mbs;       /* Intra16x16 macroblocks (intra = 1); pcm_mbs counts
+                              only the macroblocks that stayed I_PCM           */
+  uint64_t recon_hash;     /* intra = 1: the encoder's own reconstruction,
+                              hashed as vts_synth_info.recon_hash (display-size
+                              NV12, f = the frame index); else 0               */
 } vts_transcode_info;
 
 /* Transcode the session's video to `out_path`. */

@@ -143,6 +143,26 @@ VTS_HD inline void scale_idct4(const int *c, int qp, const int32_t *ls, bool dc_
   }
 }
 
+// 8.5.10: Intra16x16 luma DC.  dcl the 4x4 levels (raster), ls =
+// LevelScale4x4(qP % 6, 0, 0); dcy receives the scaled DC of the luma block
+// at row i, column j (raster), the c[0] of scale_idct4(.., dc_done)
+VTS_HD inline void i16_dc_inverse(const int *dcl, int qp, int ls, int *dcy) {
+  int t[16];
+  for (int i = 0; i < 4; ++i) {
+    const int a0 = dcl[i * 4], a1 = dcl[i * 4 + 1], a2 = dcl[i * 4 + 2], a3 = dcl[i * 4 + 3];
+    t[i * 4] = a0 + a1 + a2 + a3;
+    t[i * 4 + 1] = a0 + a1 - a2 - a3;
+    t[i * 4 + 2] = a0 - a1 - a2 + a3;
+    t[i * 4 + 3] = a0 - a1 + a2 - a3;
+  }
+  for (int j = 0; j < 4; ++j) {
+    const int a0 = t[j], a1 = t[4 + j], a2 = t[8 + j], a3 = t[12 + j];
+    const int f[4] = {a0 + a1 + a2 + a3, a0 + a1 - a2 - a3, a0 - a1 - a2 + a3, a0 - a1 + a2 - a3};
+    for (int i = 0; i < 4; ++i)
+      dcy[i * 4 + j] = qp >= 36 ? (f[i] * ls) << (qp / 6 - 6) : (f[i] * ls + (1 << (5 - qp / 6))) >> (6 - qp / 6);
+  }
+}
+
 // the same with Flat_16 (the upload encoder's own reconstruction)
 VTS_HD inline void scale_idct4(const int *c, int qp, bool dc_done, int *r) {
   int32_t ls[16];
@@ -706,22 +726,9 @@ struct MbRecon {
     } else {
       intra16(m.modes & 3);
       // 8.5.10: Intra16x16 DC, Hadamard + scaling
-      int dcl[16], t[16], dcy[16];
+      int dcl[16], dcy[16];
       load_block(kBlkI16Dc, dcl);
-      for (int i = 0; i < 4; ++i) {
-        const int a0 = dcl[i * 4], a1 = dcl[i * 4 + 1], a2 = dcl[i * 4 + 2], a3 = dcl[i * 4 + 3];
-        t[i * 4] = a0 + a1 + a2 + a3;
-        t[i * 4 + 1] = a0 + a1 - a2 - a3;
-        t[i * 4 + 2] = a0 - a1 - a2 + a3;
-        t[i * 4 + 3] = a0 - a1 + a2 - a3;
-      }
-      const int ls = c.sct->ls4[0][qp % 6][0];  // LevelScale4x4(qP % 6, 0, 0) of Intra Y
-      for (int j = 0; j < 4; ++j) {
-        const int a0 = t[j], a1 = t[4 + j], a2 = t[8 + j], a3 = t[12 + j];
-        const int f[4] = {a0 + a1 + a2 + a3, a0 + a1 - a2 - a3, a0 - a1 - a2 + a3, a0 - a1 + a2 - a3};
-        for (int i = 0; i < 4; ++i)
-          dcy[i * 4 + j] = qp >= 36 ? (f[i] * ls) << (qp / 6 - 6) : (f[i] * ls + (1 << (5 - qp / 6))) >> (6 - qp / 6);
-      }
+      i16_dc_inverse(dcl, qp, c.sct->ls4[0][qp % 6][0], dcy);  // LevelScale4x4(qP % 6, 0, 0) of Intra Y
       for (int b = 0; b < 16; ++b) {
         luma_residual_block(b, qp, true, dcy, res);
         put_luma(b, res);

@@ -14,7 +14,10 @@
 //      reconstruct levels): `enc_search` — one wave per macroblock, full
 //      integer motion search in LDS against the previous reconstruction,
 //      decision inter / I_PCM, reconstruction written (the next level's
-//      reference); then per chunk of 16 levels on a second stream:
+//      reference); with intra = 1, `enc_intra` — one wave per macroblock
+//      row recodes the level's I_PCM macroblocks (level 0: the whole IDR
+//      picture) as Intra16x16 where cheaper, and `enc_hash` hashes the
+//      level's reconstruction; then per chunk of 16 levels on a second stream:
 //      `enc_write` — one lane per slice (macroblock row) writes the CAVLC
 //      slice NAL with emulation prevention into a fixed-capacity staging slot,
 //      leaving I_PCM payloads as gaps; `enc_scan` — device offsets;
@@ -583,7 +586,7 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
 // ------------------------------------------------------ slice writer
 struct WriteArgs {
   const int4 *ent;      // per frame of the level: (frame, GOP position j, IDR parity, index within its level)
-  const uint32_t *cmd;  // [entry][mb] (P levels)
+  const uint32_t *cmd;  // [entry][mb] (P levels; with intra every level)
   const uint8_t *cbp;   // [entry][mb] coded_block_pattern
   const int16_t *coef;  // level ring: [ring slot][index within level][mb][kCoefPerMb]
   int64_t coef_per_level;  // entries a ring slot holds
@@ -594,7 +597,7 @@ struct WriteArgs {
   uint8_t *staging;     // [slice][cap]
   int64_t cap;
   int32_t *sizes;       // [slice] bytes incl. the 4-byte length prefix
-  unsigned long long *stats;  // pcm, inter, skip
+  unsigned long long *stats;  // pcm, inter, skip, intra
   uint32_t *err;
   uint4 *jobs;          // I_PCM payloads left for enc_pcm: (slice, byte offset in the slot, mx, 0)
   uint32_t *n_jobs;
@@ -736,6 +739,422 @@ __device__ int cavlc_block(NalOut *o, const int *lv, int maxNum, int nC) {
   return bits;
 }
 
+// ------------------------------------------------------ intra coding
+// Intra16x16 in place of I_PCM (vts_transcode_params.intra).
+// A slice is one macroblock row, so the row above is never available: luma
+// predicts Horizontal (1) or DC (2) from the left macroblock's reconstructed
+// right column, chroma DC (0) or Horizontal (1), and DC = 128 at mx = 0
+// (8.3.3, 8.3.4).  Each row is a serial chain, so enc_intra is one wave per
+// (level entry, macroblock row) walking mx = 0 .. mbw - 1; all ordering is
+// program order inside that wave plus stream order between launches.
+//
+// Command word of an Intra16x16 macroblock: the high half 0x8000 (mvy =
+// -32768: never a motion) with bit 15 clear; bits 0..1 Intra16x16PredMode,
+// 2..3 intra_chroma_pred_mode, 4..9 coded_block_pattern (luma 0 or 15).
+constexpr uint32_t kIntraCmd = 0x80000000u;
+__device__ __forceinline__ bool is_intra_cmd(uint32_t c) { return (c & 0xffff8000u) == kIntraCmd; }
+__device__ __forceinline__ int ue_bits(uint32_t v) { return 2 * (31 - __builtin_clz(v + 1)) + 1; }
+// nC of 9.2.1 from the left (na) and upper (nb) blocks' total_coeff, -1 = unavailable
+__device__ __forceinline__ int nc_of(int na, int nb) {
+  return (na >= 0 && nb >= 0) ? (na + nb + 1) >> 1 : (na >= 0 ? na : (nb >= 0 ? nb : 0));
+}
+
+struct IntraArgs {
+  const int4 *ent;      // the level's search entries: (frame, -, dst slot, 0)
+  const uint8_t *small;
+  int64_t stride;
+  uint8_t *recon;       // [slot]
+  uint32_t *cmd;        // [entry][mb]
+  uint8_t *cbp;         // [entry][mb]
+  int16_t *coef;        // [entry][mb][kCoefPerMb] (this level's ring slot)
+  int32_t cw, ch, mbw, mbh;
+  int32_t qp;
+  int32_t all;          // 1: every macroblock is a candidate and dst is unwritten (level 0, the IDR
+                        // pictures); 0: the macroblocks enc_search left as kPcmCmd (dst holds the source)
+};
+
+__global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t srcy[64], recy[64];
+  __shared__ uint16_t srcc[64];
+  __shared__ uint8_t recc[2][64];
+  __shared__ int left_y[16], left_c[2][8];  // the left macroblock's right column (reconstruction)
+  __shared__ int pred_y[16], pred_c[2][8];  // the chosen prediction of each row (both modes are constant along a row)
+  __shared__ int lnz[4], lnzc[2][2];        // total_coeff of the left macroblock's right column, -1 none
+  __shared__ int tcy[16], tcc[2][4];        // this macroblock's total_coeff, luma in raster order
+  __shared__ int ydw[16], ydl[16], yds[16]; // luma DC: transform terms, levels, scaled (8.5.10), raster
+  __shared__ int dcw[2][4], dcl[2][4];
+  const int lane = threadIdx.x;
+  const int e = blockIdx.x / a.mbh, my = blockIdx.x % a.mbh;
+  const int4 en = a.ent[e];
+  const uint8_t *src = a.small + static_cast<int64_t>(en.x) * a.stride;
+  uint8_t *dst = a.recon + static_cast<int64_t>(en.z) * a.stride;
+  const int64_t mb0 = (static_cast<int64_t>(e) * a.mbh + my) * a.mbw;
+  const int qp = a.qp, qpc = kQpcTab[qp];
+  const int qbits = 15 + qp / 6, cqb = 15 + qpc / 6;
+  const int64_t f = (int64_t(1) << qbits) / 6, cf = (int64_t(1) << cqb) / 6;
+  const int ly = lane >> 2, lx = 4 * (lane & 3), ci = lane & 7, cj = lane >> 3;
+  if (lane < 4) lnz[lane] = -1;
+  if (lane < 4) lnzc[lane >> 1][lane & 1] = -1;
+  bool left_mine = false;  // the left macroblock was coded by this wave: its column is in left_y / left_c
+  for (int mx = 0; mx < a.mbw; ++mx) {
+    if (!a.all && a.cmd[mb0 + mx] != kPcmCmd) {  // wave-uniform
+      left_mine = false;
+      continue;
+    }
+    const int64_t lo = static_cast<int64_t>(my * 16 + ly) * a.cw + mx * 16 + lx;
+    const int64_t co = static_cast<int64_t>(a.cw) * a.ch + static_cast<int64_t>(my * 8 + cj) * a.cw + 2 * (mx * 8 + ci);
+    const uint32_t sy4 = *reinterpret_cast<const uint32_t *>(src + lo);
+    const uint16_t suv = *reinterpret_cast<const uint16_t *>(src + co);
+    srcy[lane] = sy4;
+    srcc[lane] = suv;
+    if (mx > 0 && !left_mine) {
+      // the left macroblock is enc_search's (an earlier launch): its column
+      // from dst, its total_coeff from its levels as enc_write will count them
+      if (lane < 16) {
+        left_y[lane] = dst[static_cast<int64_t>(my * 16 + lane) * a.cw + mx * 16 - 1];
+      } else if (lane < 24) {
+        const uint16_t p = *reinterpret_cast<const uint16_t *>(
+            dst + static_cast<int64_t>(a.cw) * a.ch + static_cast<int64_t>(my * 8 + lane - 16) * a.cw + 2 * (mx * 8 - 1));
+        left_c[0][lane - 16] = p & 255;
+        left_c[1][lane - 16] = p >> 8;
+      } else if (lane >= 32 && lane < 40) {
+        const int lcbp = a.cbp[mb0 + mx - 1];
+        const int16_t *lp = a.coef + (mb0 + mx - 1) * kCoefPerMb;
+        const int i = lane - 32;
+        int n = 0;
+        if (i < 4) {
+          const int blk = 5 + 2 * (i & 1) + 8 * (i >> 1);  // luma4x4BlkIdx 5, 7, 13, 15
+          if ((lcbp >> (blk >> 2)) & 1)
+            for (int q = 0; q < 16; ++q) n += lp[16 * blk + q] != 0;
+          lnz[i] = n;
+        } else {
+          const int pl = (i - 4) >> 1, k = 1 + 2 * (i & 1);
+          if ((lcbp >> 4) == 2)
+            for (int q = 0; q < 15; ++q) n += lp[264 + 60 * pl + 15 * k + q] != 0;
+          lnzc[pl][i & 1] = n;
+        }
+      }
+    }
+    __syncthreads();
+    // ---- prediction modes by SAD (ties: the lower mode number)
+    int lmode = 2, cmode = 0, dcy = 128, dcu = 128, dcv = 128;
+    if (mx > 0) {
+      int s = 0;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s += left_y[i];
+      dcy = (s + 8) >> 4;
+      int su = 0, sv = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        su += left_c[0][(cj & 4) + i];
+        sv += left_c[1][(cj & 4) + i];
+      }
+      dcu = (su + 2) >> 2;  // 8.3.4: no row above, so every chroma 4x4 block takes its own rows' left samples
+      dcv = (sv + 2) >> 2;
+      const int u = suv & 255, v = suv >> 8;
+      // four sums, each < 2^16, reduced as two packed words
+      uint32_t sl = __builtin_amdgcn_sad_u8(static_cast<uint32_t>(left_y[ly]) * 0x01010101u, sy4, 0) |
+                    (__builtin_amdgcn_sad_u8(static_cast<uint32_t>(dcy) * 0x01010101u, sy4, 0) << 16);
+      uint32_t sc = static_cast<uint32_t>(abs(dcu - u) + abs(dcv - v)) |
+                    (static_cast<uint32_t>(abs(left_c[0][cj] - u) + abs(left_c[1][cj] - v)) << 16);
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        sl += __shfl_xor(sl, off);
+        sc += __shfl_xor(sc, off);
+      }
+      lmode = (sl & 0xffffu) <= (sl >> 16) ? 1 : 2;
+      cmode = (sc & 0xffffu) <= (sc >> 16) ? 0 : 1;
+    }
+    if (lane < 16) pred_y[lane] = lmode == 1 ? left_y[lane] : dcy;
+    if (cmode == 1) {
+      if (lane < 16) pred_c[lane >> 3][lane & 7] = left_c[lane >> 3][lane & 7];
+    } else if (ci == 0) {
+      pred_c[0][cj] = dcu;
+      pred_c[1][cj] = dcv;
+    }
+    __syncthreads();
+    // ---- transform + quantisation: lanes 0..15 the luma blocks
+    // (luma4x4BlkIdx), 16..23 the chroma blocks, 24 the luma DC, 16 / 17 the
+    // chroma DC (enc_search's layout)
+    int lv[16], z[16], nzb = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) lv[i] = z[i] = 0;
+    const int bxl = lane < 16 ? kBlkXd[lane] : 0, byl = lane < 16 ? kBlkYd[lane] : 0;
+    if (lane < 16) {
+      int x[16], w[16];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t sv = srcy[(byl * 4 + r) * 4 + bxl];
+        const int p = pred_y[byl * 4 + r];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) x[r * 4 + c] = static_cast<int>((sv >> (8 * c)) & 255) - p;
+      }
+      fwd4(x, w);
+      ydw[byl * 4 + bxl] = w[0];
+#pragma unroll
+      for (int q = 1; q < 16; ++q) {
+        z[q] = quant1(w[q], kMf[qp % 6][pos_class(q >> 2, q & 3)], qbits, f);
+        nzb |= z[q] != 0;
+      }
+#pragma unroll
+      for (int q = 1; q < 16; ++q) lv[q - 1] = z[kZz4[q]];
+    } else if (lane < 24) {
+      const int pl = (lane - 16) >> 2, k = (lane - 16) & 3, bx = (k & 1) * 4, by = (k >> 1) * 4;
+      int x[16], w[16];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          x[r * 4 + c] = static_cast<int>((srcc[(by + r) * 8 + bx + c] >> (8 * pl)) & 255) - pred_c[pl][by + r];
+      fwd4(x, w);
+      dcw[pl][k] = w[0];
+#pragma unroll
+      for (int q = 1; q < 16; ++q) {
+        z[q] = quant1(w[q], kMf[qpc % 6][pos_class(q >> 2, q & 3)], cqb, cf);
+        nzb |= z[q] != 0;
+      }
+#pragma unroll
+      for (int q = 1; q < 16; ++q) lv[q - 1] = z[kZz4[q]];
+    }
+    __syncthreads();
+    if (lane == 24) {
+      // luma DC: (H D H) / 2 of the 16 DC terms (D by block row, column),
+      // quantised at (qbits + 1, 2f); then the decoder's 8.5.10 for the
+      // reconstruction
+      int t[16], lev[16], sc[16];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int a0 = ydw[i * 4], a1 = ydw[i * 4 + 1], a2 = ydw[i * 4 + 2], a3 = ydw[i * 4 + 3];
+        t[i * 4] = a0 + a1 + a2 + a3;
+        t[i * 4 + 1] = a0 + a1 - a2 - a3;
+        t[i * 4 + 2] = a0 - a1 - a2 + a3;
+        t[i * 4 + 3] = a0 - a1 + a2 - a3;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int a0 = t[j], a1 = t[4 + j], a2 = t[8 + j], a3 = t[12 + j];
+        const int h[4] = {a0 + a1 + a2 + a3, a0 + a1 - a2 - a3, a0 - a1 - a2 + a3, a0 - a1 + a2 - a3};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) lev[i * 4 + j] = quant1((h[i] + 1) >> 1, kMf[qp % 6][0], qbits + 1, 2 * f);
+      }
+      full::i16_dc_inverse(lev, qp, full::level_scale(qp % 6, 0, 0), sc);
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        ydl[k] = lev[k];
+        yds[k] = sc[k];
+      }
+    } else if (lane == 16 || lane == 17) {  // chroma DC: 2x2 Hadamard, quantised at (qbits + 1, 2f)
+      const int pl = lane - 16;
+      const int c0 = dcw[pl][0], c1 = dcw[pl][1], c2 = dcw[pl][2], c3 = dcw[pl][3];
+      const int fd[4] = {c0 + c1 + c2 + c3, c0 - c1 + c2 - c3, c0 + c1 - c2 - c3, c0 - c1 - c2 + c3};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) dcl[pl][k] = quant1(fd[k], kMf[qpc % 6][0], cqb + 1, 2 * cf);
+    }
+    const uint64_t nzm = __ballot(nzb);
+    const bool ac = (nzm & 0xffffu) != 0;  // Intra16x16: the luma coded_block_pattern is 0 or 15
+    int tc = 0;
+#pragma unroll
+    for (int q = 0; q < 15; ++q) tc += lv[q] != 0;
+    __syncthreads();
+    bool dcnz = false;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) dcnz |= dcl[k >> 2][k & 3] != 0;
+    const int cc = ((nzm >> 16) & 0xffu) ? 2 : (dcnz ? 1 : 0);
+    const int cbp = (ac ? 15 : 0) | (cc << 4);
+    if (lane < 16) tcy[byl * 4 + bxl] = ac ? tc : 0;
+    else if (lane < 24) tcc[(lane - 16) >> 2][(lane - 16) & 3] = cc == 2 ? tc : 0;
+    __syncthreads();
+    // ---- the macroblock's bits with the writer's own nC contexts (9.2.1)
+    int contrib = 0;
+    int dlv[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) dlv[q] = 0;
+    if (lane < 16) {
+      if (ac) {
+        const int na = bxl ? tcy[byl * 4 + bxl - 1] : lnz[byl], nb = byl ? tcy[(byl - 1) * 4 + bxl] : -1;
+        contrib = cavlc_block<false>(nullptr, lv, 15, nc_of(na, nb));
+      }
+    } else if (lane < 24) {
+      if (cc == 2) {
+        const int pl = (lane - 16) >> 2, k = (lane - 16) & 3, bx = k & 1, by = k >> 1;
+        const int na = bx ? tcc[pl][by * 2] : lnzc[pl][by], nb = by ? tcc[pl][bx] : -1;
+        contrib = cavlc_block<false>(nullptr, lv, 15, nc_of(na, nb));
+      }
+    } else if (lane < 26) {
+      if (cc) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dlv[q] = dcl[lane - 24][q];
+        contrib = cavlc_block<false>(nullptr, dlv, 4, -1);
+      }
+    } else if (lane == 26) {  // the header and Intra16x16DCLevel (nC of block 0)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) dlv[q] = ydl[kZz4[q]];
+      const int mbt = 1 + lmode + 4 * cc + (ac ? 12 : 0);
+      contrib = ue_bits(static_cast<uint32_t>(a.all ? mbt : 5 + mbt)) + ue_bits(static_cast<uint32_t>(cmode)) + 1 +
+                cavlc_block<false>(nullptr, dlv, 16, nc_of(lnz[0], -1));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) contrib += __shfl_xor(contrib, off);
+    const bool intra = contrib <= kPcmBits;  // wave-uniform
+    if (intra) {
+      // ---- reconstruction through the decoder's inverse path
+      if (lane < 16) {
+        int cfs[16], res[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) cfs[q] = ac ? z[q] : 0;
+        cfs[0] = yds[byl * 4 + bxl];
+        full::scale_idct4(cfs, qp, true, res);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int p = pred_y[byl * 4 + r];
+          uint32_t o = 0;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) o |= static_cast<uint32_t>(min(max(p + res[r * 4 + c], 0), 255)) << (8 * c);
+          recy[(byl * 4 + r) * 4 + bxl] = o;
+        }
+      } else if (lane < 24) {  // chroma (8.5.11 DC, then 8.5.12)
+        const int pl = (lane - 16) >> 2, k = (lane - 16) & 3, bx = (k & 1) * 4, by = (k >> 1) * 4;
+        const int *c = dcl[pl];
+        const int F = k == 0 ? c[0] + c[1] + c[2] + c[3]
+                             : (k == 1 ? c[0] - c[1] + c[2] - c[3] : (k == 2 ? c[0] + c[1] - c[2] - c[3] : c[0] - c[1] - c[2] + c[3]));
+        int cfs[16], res[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) cfs[q] = cc == 2 ? z[q] : 0;
+        cfs[0] = ((F * full::level_scale(qpc % 6, 0, 0)) << (qpc / 6)) >> 5;
+        full::scale_idct4(cfs, qpc, true, res);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int cx = 0; cx < 4; ++cx)
+            recc[pl][(by + r) * 8 + bx + cx] = static_cast<uint8_t>(min(max(pred_c[pl][by + r] + res[r * 4 + cx], 0), 255));
+      }
+      // the levels the slice writer codes: luma DC [0, 16), AC block b at 16 + 15 b, chroma as enc_search
+      int16_t *cp = a.coef + (mb0 + mx) * kCoefPerMb;
+      if (lane < 16) {
+#pragma unroll
+        for (int q = 0; q < 15; ++q) cp[16 + 15 * lane + q] = static_cast<int16_t>(lv[q]);
+      } else if (lane < 24) {
+#pragma unroll
+        for (int q = 0; q < 15; ++q) cp[264 + 15 * (lane - 16) + q] = static_cast<int16_t>(lv[q]);
+      } else if (lane < 26) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) cp[256 + 4 * (lane - 24) + q] = static_cast<int16_t>(dcl[lane - 24][q]);
+      } else if (lane == 26) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) cp[q] = static_cast<int16_t>(dlv[q]);
+      }
+    }
+    __syncthreads();
+    if (intra || a.all) {
+      *reinterpret_cast<uint32_t *>(dst + lo) = intra ? recy[lane] : sy4;
+      *reinterpret_cast<uint16_t *>(dst + co) = intra ? static_cast<uint16_t>(recc[0][lane] | (recc[1][lane] << 8)) : suv;
+    }
+    if (lane == 0) {
+      a.cmd[mb0 + mx] = intra ? kIntraCmd | static_cast<uint32_t>(lmode | (cmode << 2) | (cbp << 4)) : kPcmCmd;
+      a.cbp[mb0 + mx] = static_cast<uint8_t>(intra ? cbp : 0);
+    }
+    // what the macroblock to the right sees: this one's right column (from
+    // LDS, never read back from dst) and its total_coeff (16 after I_PCM)
+    if (lane < 16) {
+      left_y[lane] = static_cast<int>((intra ? recy[lane * 4 + 3] : srcy[lane * 4 + 3]) >> 24);
+    } else if (lane < 32) {
+      const int pl = (lane - 16) >> 3, y = lane & 7;
+      left_c[pl][y] = intra ? recc[pl][y * 8 + 7] : static_cast<int>((srcc[y * 8 + 7] >> (8 * pl)) & 255);
+    } else if (lane < 36) {
+      lnz[lane - 32] = intra ? tcy[(lane - 32) * 4 + 3] : 16;
+    } else if (lane < 40) {
+      const int pl = (lane - 36) >> 1, r = lane & 1;
+      lnzc[pl][r] = intra ? tcc[pl][1 + 2 * r] : 16;
+    }
+    left_mine = true;
+    __syncthreads();
+  }
+}
+
+// The encoder's reconstruction hashed as vts_synth_info.recon_hash: over the
+// display-size NV12 bytes j of each of the level's frames f, b_j ((j % 65521)
+// + 1) (f + 1) added into *acc (wrap-around addition: any order).
+__global__ void __launch_bounds__(256) enc_hash(const int4 *ent, const uint8_t *recon, int64_t stride, int32_t cw,
+                                                int32_t ch, int32_t w, int32_t h, int32_t per_frame,
+                                                unsigned long long *acc) {
+  __shared__ unsigned long long part[4];
+  const int4 en = ent[blockIdx.x / per_frame];  // per_frame workgroups share a frame
+  const int b0 = blockIdx.x % per_frame;
+  const uint8_t *p = recon + static_cast<int64_t>(en.z) * stride;
+  // one dword of a display row per pass (rows start 16-aligned and cw >= w
+  // rounded up to 4, so the dword is inside the coded row; bytes past w are
+  // dropped): NV12 rows y < h luma, then h / 2 rows of Cb|Cr pairs
+  const int nd = (w + 3) >> 2, n = (h + h / 2) * nd;
+  unsigned long long s = 0;
+  for (int i = b0 * 256 + threadIdx.x; i < n; i += per_frame * 256) {
+    const int y = i / nd, x = 4 * (i - y * nd);
+    const uint8_t *row = y < h ? p + static_cast<int64_t>(y) * cw : p + static_cast<int64_t>(cw) * ch + static_cast<int64_t>(y - h) * cw;
+    const uint32_t v = *reinterpret_cast<const uint32_t *>(row + x);
+    int m = (y * w + x) % 65521;  // j % 65521 of the dword's first byte
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (x + k < w) s += static_cast<unsigned long long>(((v >> (8 * k)) & 255u) * static_cast<uint32_t>(m + 1));
+      m = m + 1 == 65521 ? 0 : m + 1;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    atomicAdd(acc, (part[0] + part[1] + part[2] + part[3]) * static_cast<unsigned long long>(en.x + 1));
+}
+
+// chroma DC and AC of residual() (7.3.5.3) as put_residual writes them, cc =
+// coded_block_pattern / 16 (a copy: put_residual keeps its own loop so that
+// the encoder without intra compiles to the code it was)
+__device__ void put_chroma_residual(NalOut &o, const int16_t *cp, int cc, const int (*lnzc)[2], int (*cnzc)[4]) {
+  int lv[16];
+  if (cc)
+    for (int pl = 0; pl < 2; ++pl) {
+      for (int q = 0; q < 4; ++q) lv[q] = cp[256 + 4 * pl + q];
+      cavlc_block<true>(&o, lv, 4, -1);
+    }
+  if (cc == 2)
+    for (int pl = 0; pl < 2; ++pl)
+      for (int k = 0; k < 4; ++k) {
+        const int bx = k & 1, by = k >> 1;
+        const int na = bx ? cnzc[pl][by * 2] : lnzc[pl][by], nb = by ? cnzc[pl][bx] : -1;
+        int tc = 0;
+        for (int q = 0; q < 15; ++q) {
+          lv[q] = cp[264 + 60 * pl + 15 * k + q];
+          tc += lv[q] != 0;
+        }
+        cavlc_block<true>(&o, lv, 15, nc_of(na, nb));
+        cnzc[pl][k] = tc;
+      }
+}
+
+// residual() of an Intra16x16 macroblock: Intra16x16DCLevel (nC of block 0),
+// the 16 Intra16x16ACLevel blocks when the luma coded_block_pattern is 15,
+// chroma.  The arguments as put_residual's.
+__device__ void put_intra_residual(NalOut &o, const int16_t *cp, int cbp, const int *lnz, const int (*lnzc)[2],
+                                   int *cnz, int (*cnzc)[4]) {
+  for (int i = 0; i < 16; ++i) cnz[i] = 0;
+  for (int i = 0; i < 4; ++i) cnzc[0][i] = cnzc[1][i] = 0;
+  int lv[16];
+  for (int q = 0; q < 16; ++q) lv[q] = cp[q];
+  cavlc_block<true>(&o, lv, 16, nc_of(lnz[0], -1));
+  if (cbp & 15)
+    for (int k = 0; k < 16; ++k) {
+      const int bx = kBlkXd[k], by = kBlkYd[k];
+      const int na = bx ? cnz[by * 4 + bx - 1] : lnz[by], nb = by ? cnz[(by - 1) * 4 + bx] : -1;
+      int tc = 0;
+      for (int q = 0; q < 15; ++q) {
+        lv[q] = cp[16 + 15 * k + q];
+        tc += lv[q] != 0;
+      }
+      cavlc_block<true>(&o, lv, 15, nc_of(na, nb));
+      cnz[by * 4 + bx] = tc;
+    }
+  put_chroma_residual(o, cp, cbp >> 4, lnzc, cnzc);
+}
+
 // residual() of an inter macroblock (7.3.5.3): cp the levels, cnz / cnzc
 // receive the blocks' total_coeff; lnz / lnzc the left macroblock's right
 // column (-1: unavailable; the macroblock above is another slice)
@@ -794,6 +1213,9 @@ __device__ void pcm_gap(NalOut &o, uint4 *job, int s, int mx) {
   o.zeros = 0;
 }
 
+// kIntra: enc_intra ran on every level, so IDR pictures have commands too and
+// a command may be kIntraCmd (the other instance is the encoder without it)
+template <bool kIntra>
 __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= a.n_slices) return;
@@ -815,7 +1237,7 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   }
   o.se(a.qp >= 1 ? a.qp - 26 : 0);  // slice_qp_delta: SliceQPY = the residual's QP (pic_init_qp 26)
   o.ue(1);  // disable_deblocking_filter_idc
-  unsigned long long npcm = 0, ninter = 0, nskip = 0;
+  unsigned long long npcm = 0, ninter = 0, nskip = 0, nintra = 0;
   uint32_t skip = 0;
   bool a_ok = false;
   int amx = 0, amy = 0;
@@ -827,24 +1249,46 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   int lnz[4] = {-1, -1, -1, -1}, lnzc[2][2] = {{-1, -1}, {-1, -1}}, cnz[16], cnzc[2][4];
   // reserve this slice's I_PCM jobs
   uint32_t njob = 0;
-  if (idr) {
+  if (idr && !kIntra) {
     njob = static_cast<uint32_t>(a.mbw);
   } else {
     for (int mx = 0; mx < a.mbw; ++mx) njob += cmd[mx] == kPcmCmd;
   }
   uint4 *job = a.jobs + (njob ? atomicAdd(a.n_jobs, njob) : 0u);
   for (int mx = 0; mx < a.mbw; ++mx) {
-    if (idr) {
+    if (idr && !kIntra) {
       o.ue(25);
       pcm_gap(o, job++, s, mx);
       ++npcm;
       continue;
     }
     const uint32_t c = cmd[mx];
+    if (kIntra && is_intra_cmd(c)) {  // Intra16x16 (7.3.5, Table 7-11; 5 more in a P slice)
+      const int cbp = static_cast<int>(c >> 4) & 63;
+      const uint32_t mbt = 1 + (c & 3u) + 4 * static_cast<uint32_t>(cbp >> 4) + ((cbp & 15) ? 12 : 0);
+      if (!idr) {
+        o.ue(skip);
+        skip = 0;
+      }
+      o.ue(idr ? mbt : 5 + mbt);
+      o.ue((c >> 2) & 3u);  // intra_chroma_pred_mode
+      o.se(0);              // mb_qp_delta
+      put_intra_residual(o, coef_row + static_cast<int64_t>(mx) * kCoefPerMb, cbp, lnz, lnzc, cnz, cnzc);
+      for (int i = 0; i < 4; ++i) lnz[i] = cnz[i * 4 + 3];
+      for (int pl = 0; pl < 2; ++pl) {
+        lnzc[pl][0] = cnzc[pl][1];
+        lnzc[pl][1] = cnzc[pl][3];
+      }
+      a_ok = false;  // as after I_PCM: no motion to predict from
+      ++nintra;
+      continue;
+    }
     if (c == kPcmCmd) {
-      o.ue(skip);
-      skip = 0;
-      o.ue(30);  // I_PCM in a P slice
+      if (!idr) {
+        o.ue(skip);
+        skip = 0;
+      }
+      o.ue(idr ? 25 : 30);  // I_PCM in an I / a P slice
       pcm_gap(o, job++, s, mx);
       a_ok = false;
       ++npcm;
@@ -902,6 +1346,7 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   atomicAdd(&a.stats[0], npcm);
   atomicAdd(&a.stats[1], ninter);
   atomicAdd(&a.stats[2], nskip);
+  if (nintra) atomicAdd(&a.stats[3], nintra);
 }
 
 // Slice offsets of one level on the device: offs[s] = running output total +
@@ -1154,6 +1599,9 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
   const int T = p.max_mb_sad == 0 ? 1536 : p.max_mb_sad;
   const int qp = p.qp == 0 ? 28 : (p.qp < 0 ? 0 : p.qp);  // 0: no residual coding (the round-2 encoder)
   if (qp > 51) return fail(VTS_E_INVALID, "qp %d > 51", qp);
+  if (p.intra != 0 && p.intra != 1) return fail(VTS_E_INVALID, "intra %d: 0 or 1", p.intra);
+  const bool intra = p.intra == 1;
+  if (intra && qp < 1) return fail(VTS_E_INVALID, "intra = 1 needs residual coding (qp >= 0)");
   const int keyint = p.keyint > 0 ? p.keyint : 250;
   const float thr = p.cut_threshold > 0 ? p.cut_threshold : c->params.cut_threshold;
   if ((sh & 1) || sh < 16 || sh > c->height)
@@ -1201,7 +1649,9 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
     for (int64_t g = 0; g < ngop; ++g) {
       if (gop_len[g] <= j) continue;
       const int f = static_cast<int>(gop_start[g] + j);
-      sent.push_back(make_int4(f, j == 1 ? -1 : static_cast<int>(2 * g + ((j - 1) & 1)), static_cast<int>(2 * g + (j & 1)), 0));
+      // level 1 predicts from the IDR picture: its source (all I_PCM) or, with intra, its reconstruction
+      sent.push_back(make_int4(f, j == 1 && !intra ? -1 : static_cast<int>(2 * g + ((j - 1) & 1)),
+                               static_cast<int>(2 * g + (j & 1)), 0));
       went.push_back(make_int4(f, static_cast<int>(j), static_cast<int>(g & 1),
                                static_cast<int>(static_cast<int64_t>(went.size()) - lvl_off[j])));
     }
@@ -1243,7 +1693,7 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
   VTS_TRY(B.get(&d_fr, static_cast<size_t>(2 * n)));  // per frame: absolute offset, size
   VTS_TRY(B.get(&d_sizes, static_cast<size_t>(max_chunk * mbh)));
   VTS_TRY(B.get(&d_offs, static_cast<size_t>(max_chunk * mbh)));
-  VTS_TRY(B.get(&d_stats, 3));
+  VTS_TRY(B.get(&d_stats, 5));  // pcm, inter, skip, intra macroblocks; the reconstruction hash
   VTS_TRY(B.get(&d_err, 1));
   uint4 *d_jobs;
   uint32_t *d_njobs;
@@ -1258,7 +1708,8 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
   B.streams = {s1, s2};
   HIP_TRY(hipMemcpy(d_sent, sent.data(), sent.size() * sizeof(int4), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_went, went.data(), went.size() * sizeof(int4), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemsetAsync(d_stats, 0, 3 * sizeof(unsigned long long), s2));
+  HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), s2));
+  if (intra) HIP_TRY(hipMemsetAsync(d_stats + 4, 0, sizeof(unsigned long long), s1));  // enc_hash (s1) adds into it
   HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(uint32_t), s2));
   const int64_t nchunks = (maxlen + kChunkLevels - 1) / kChunkLevels;
   std::vector<hipEvent_t> ev(static_cast<size_t>(maxlen + 5 + nchunks), nullptr);
@@ -1273,6 +1724,34 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
   hipEvent_t es0 = ev[maxlen], es1 = ev[maxlen + 1], ew0 = ev[maxlen + 2], ew1 = ev[maxlen + 3];
   hipEvent_t *wev = &ev[maxlen + 5];  // per chunk: its slices written (its ring slots free again)
   HIP_TRY(hipEventRecord(es0, s1));
+  // intra: the level's kPcmCmd macroblocks (level 0: every macroblock) become
+  // Intra16x16 where cheaper, then the level's reconstruction is hashed; both
+  // on the search stream, before the next level's search reads the slots
+  auto enqueue_intra = [&](int64_t j) {
+    const int64_t ne = lvl_off[j + 1] - lvl_off[j];
+    IntraArgs ia{};
+    ia.ent = d_sent + lvl_off[j];
+    ia.small = S.d;
+    ia.stride = S.stride;
+    ia.recon = d_recon;
+    ia.cmd = d_cmd + lvl_off[j] * nmb;
+    ia.cbp = d_cbp + lvl_off[j] * nmb;
+    ia.coef = d_coef + (j % kRing) * ngop * nmb * kCoefPerMb;
+    ia.cw = S.cw;
+    ia.ch = S.ch;
+    ia.mbw = mbw;
+    ia.mbh = mbh;
+    ia.qp = qp;
+    ia.all = j == 0;
+    hipLaunchKernelGGL(enc_intra, dim3(static_cast<unsigned>(ne * mbh)), dim3(64), 0, s1, ia);
+    const int hb = std::max(1, std::min(64, (S.w * S.h * 3 / 2 + 4095) / 4096));
+    hipLaunchKernelGGL(enc_hash, dim3(static_cast<unsigned>(hb * ne)), dim3(256), 0, s1, d_sent + lvl_off[j], d_recon,
+                       S.stride, S.cw, S.ch, S.w, S.h, hb, d_stats + 4);
+  };
+  if (intra) {
+    enqueue_intra(0);
+    HIP_TRY(hipEventRecord(ev[0], s1));
+  }
   int64_t next_search = 1;
   bool searches_done = false;
   // enqueue the searches of levels < upto; level j reuses the ring slot of
@@ -1304,6 +1783,7 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
         case 16: hipLaunchKernelGGL(enc_search<16>, grid, dim3(64), 0, s1, sa); break;
         default: hipLaunchKernelGGL(enc_search<0>, grid, dim3(64), 0, s1, sa); break;
       }
+      if (intra) enqueue_intra(j);
       HIP_TRY(hipEventRecord(ev[j], s1));
     }
     if (next_search >= maxlen && !searches_done) {
@@ -1348,7 +1828,7 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
     const int64_t j1 = std::min(maxlen, j0 + kChunkLevels);
     const int64_t e0 = lvl_off[j0], ne = lvl_off[j1] - e0;
     const int ns = static_cast<int>(ne * mbh);
-    if (j1 - 1 > 0) HIP_TRY(hipStreamWaitEvent(s2, ev[j1 - 1], 0));  // searches run in level order
+    if (j1 - 1 > 0 || intra) HIP_TRY(hipStreamWaitEvent(s2, ev[j1 - 1], 0));  // searches run in level order
     HIP_TRY(hipMemcpyAsync(d_base, d_total, sizeof(int64_t), hipMemcpyDeviceToDevice, s2));
     HIP_TRY(hipMemsetAsync(d_njobs, 0, sizeof(uint32_t), s2));
     WriteArgs wa{};
@@ -1373,7 +1853,8 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
     wa.jobs = d_jobs;
     wa.n_jobs = d_njobs;
     wa.n_slices = ns;
-    hipLaunchKernelGGL(enc_write, dim3(static_cast<unsigned>((ns + 63) / 64)), dim3(64), 0, s2, wa);
+    if (intra) hipLaunchKernelGGL(enc_write<true>, dim3(static_cast<unsigned>((ns + 63) / 64)), dim3(64), 0, s2, wa);
+    else hipLaunchKernelGGL(enc_write<false>, dim3(static_cast<unsigned>((ns + 63) / 64)), dim3(64), 0, s2, wa);
     HIP_TRY(hipEventRecord(wev[j0 / kChunkLevels], s2));
     VTS_TRY(enqueue_searches(j1 + kRing));  // the ring slots of this chunk's levels are free once it is written
     hipLaunchKernelGGL(enc_scan, dim3(1), dim3(1024), 0, s2, d_sizes, ns, d_went + e0, mbh, d_offs, d_total,
@@ -1422,7 +1903,7 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
   }
   VTS_TRY(status);
   uint32_t err = 0;
-  unsigned long long st[3] = {0, 0, 0};
+  unsigned long long st[5] = {0, 0, 0, 0, 0};
   HIP_TRY(hipMemcpy(&err, d_err, sizeof err, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost));
   if (err) return fail(VTS_E_CAPACITY, "a slice exceeded its %lld-byte staging slot", static_cast<long long>(cap));
@@ -1454,6 +1935,8 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
     info->pcm_mbs = static_cast<int64_t>(st[0]);
     info->inter_mbs = static_cast<int64_t>(st[1]);
     info->skip_mbs = static_cast<int64_t>(st[2]);
+    info->intra_mbs = static_cast<int64_t>(st[3]);
+    info->recon_hash = intra ? st[4] : 0;
     info->bytes_written = mw.bytes_written();
     for (int i = 0; i < 4; ++i) info->ms[i] = ms[i];
   }

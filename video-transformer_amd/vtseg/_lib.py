@@ -13,7 +13,7 @@ import os
 from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "libvtseg.so"
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 VTS_OK = 0
 VTS_E_INVALID = -1
@@ -113,13 +113,14 @@ class SynthInfo(C.Structure):
 class TranscodeParams(C.Structure):
     _fields_ = [("height", C.c_int32), ("search_range", C.c_int32), ("max_mb_sad", C.c_int32),
                 ("keyint", C.c_int32), ("cut_threshold", C.c_float), ("idr_at_cuts", C.c_int32),
-                ("qp", C.c_int32)]
+                ("qp", C.c_int32), ("intra", C.c_int32)]
 
 
 class TranscodeInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_frames", C.c_int64),
                 ("n_idr", C.c_int64), ("pcm_mbs", C.c_int64), ("inter_mbs", C.c_int64),
-                ("skip_mbs", C.c_int64), ("bytes_written", C.c_int64), ("ms", C.c_double * 4)]
+                ("skip_mbs", C.c_int64), ("bytes_written", C.c_int64), ("ms", C.c_double * 4),
+                ("intra_mbs", C.c_int64), ("recon_hash", C.c_uint64)]
 
 
 class ManifestArgs(C.Structure):
