@@ -406,7 +406,8 @@ void vts_batch_free(vts_batch *b);
  * width, and a device encoder writes H.264 Constrained Baseline: IDR (all
  * I_PCM, or Intra16x16 with intra = 1) every keyint frames (and at scene cuts
  * if asked), P pictures of full-search
- * integer motion (P_L0_16x16 / P_Skip) with a quantised residual (qp), I_PCM
+ * integer motion (P_L0_16x16 / P_Skip; refined to half or quarter samples
+ * with vts_transcode_ext.subpel) with a quantised residual (qp), I_PCM
  * where that residual would cost more; one slice per macroblock row; MP4
  * (moov at the end), video only.  DESIGN.md §11. */
 typedef struct vts_transcode_params {
@@ -448,14 +449,45 @@ typedef struct vts_transcode_info {
                               (stream 2, overlaps the searches), MP4 mux      */
   int64_t intra_mbs;       /* Intra16x16 macroblocks (intra = 1); pcm_mbs counts
                               only the macroblocks that stayed I_PCM           */
-  uint64_t recon_hash;     /* intra = 1: the encoder's own reconstruction,
-                              hashed as vts_synth_info.recon_hash (display-size
-                              NV12, f = the frame index); else 0               */
+  uint64_t recon_hash;     /* intra = 1 or subpel != 0: the encoder's own
+                              reconstruction, hashed as
+                              vts_synth_info.recon_hash (display-size NV12, f =
+                              the frame index; an I_PCM IDR picture is its
+                              source); else 0                                  */
 } vts_transcode_info;
 
 /* Transcode the session's video to `out_path`. */
 int vts_transcode(vts_ctx *ctx, const char *out_path, const vts_transcode_params *p,
                   vts_transcode_info *info);
+
+/* Further encoder settings and facts travel in size-tagged structs, so that
+ * later ones need neither a new entry point nor a new ABI version: the caller
+ * sets struct_size to its own sizeof; a size below 8 is VTS_E_INVALID, a
+ * larger one than the library knows is accepted, and only the prefix both
+ * sides know is read or written.  Callers detect vts_transcode_ex by its
+ * symbol (the version stays 9: the change is purely additive). */
+typedef struct vts_transcode_ext {
+  uint32_t struct_size;    /* sizeof(vts_transcode_ext) of the caller          */
+  int32_t subpel;          /* motion refinement around the integer winner, by
+                              luma SAD of the 8.4.2.2.1 prediction: 0 none
+                              (every output byte as vts_transcode), 1 half
+                              samples, 2 half then quarter samples (DESIGN.md
+                              §11); any other value: VTS_E_INVALID            */
+} vts_transcode_ext;
+
+typedef struct vts_transcode_ext_info {
+  uint32_t struct_size;    /* sizeof(vts_transcode_ext_info) of the caller     */
+  int32_t _pad;
+  int64_t subpel_mbs;      /* inter macroblocks with a fractional vector       */
+  int64_t qpel_mbs;        /* ... with an odd (quarter-sample) component       */
+} vts_transcode_ext_info;
+
+/* vts_transcode with the settings of `ext` (NULL: none) and the further facts
+ * in `ext_info` (NULL: not wanted).  vts_transcode(c, o, p, i) is
+ * vts_transcode_ex(c, o, p, NULL, i, NULL). */
+int vts_transcode_ex(vts_ctx *ctx, const char *out_path, const vts_transcode_params *p,
+                     const vts_transcode_ext *ext, vts_transcode_info *info,
+                     vts_transcode_ext_info *ext_info);
 
 /* ------------------------------------------------ synthetic stream writer */
 

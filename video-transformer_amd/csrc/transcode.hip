@@ -12,7 +12,8 @@
 //      opt-in, at every scene cut from the scores);
 //   3. per GOP position j ("level", every GOP at once, as the decoder's
 //      reconstruct levels): `enc_search` — one wave per macroblock, full
-//      integer motion search in LDS against the previous reconstruction,
+//      integer motion search in LDS against the previous reconstruction
+//      (opt-in, vts_transcode_ext.subpel: refined to half / quarter samples),
 //      decision inter / I_PCM, reconstruction written (the next level's
 //      reference); with intra = 1, `enc_intra` — one wave per macroblock
 //      row recodes the level's I_PCM macroblocks (level 0: the whole IDR
@@ -44,6 +45,13 @@ constexpr uint32_t kPcmCmd = 0x80008000u;  // (mvx, mvy) = (-32768, -32768): nev
 constexpr int kMaxTaps = 16;
 constexpr int kMaxRange = 16;
 constexpr int kWinPitch = 16 + 2 * kMaxRange + 4;  // LDS window row pitch (bytes)
+// Sub-sample refinement (vts_transcode_ext.subpel): the window grows by the
+// 6-tap filter's reach around every integer candidate, 2 + 1 samples before
+// (the fraction may step below the integer winner) and 3 after; the low
+// column margin is 4 so that the integer pass keeps its dword alignment.
+constexpr int kSpLoX = 4, kSpLoY = 3, kSpHi = 3;
+constexpr int kWinPitchSp = 16 + 2 * kMaxRange + 12;  // >= 4 ceil((16 + 2 R + kSpLoX + kSpHi) / 4), + a dword
+constexpr int kSpPitch = 20;                          // half-sample plane row pitch: 18 samples, 5 dwords
 
 // ----------------------------------------------------------- downscale
 // Area filter, per axis: destination o covers source footprint [o n, (o+1) n)
@@ -228,6 +236,7 @@ struct SearchArgs {
   int32_t cw, ch, mbw, nmb;
   int32_t range, max_sad;
   int32_t qp, _pad;     // qp >= 1: residual coding at that QP
+  unsigned long long *sp_stats;  // SP > 0: inter macroblocks with a fractional vector: [0] no odd component, [1] one
 };
 
 __device__ __forceinline__ uint32_t u32_at(const uint8_t *lds_row, int off) {  // 4 bytes at any offset
@@ -254,9 +263,40 @@ __device__ __forceinline__ uint32_t u32_at(const uint8_t *lds_row, int off) {  /
 #endif
 constexpr int kUvPitch = 8 + 2 * kMaxRange + 2;  // chroma window row pitch (Cb|Cr pairs)
 
-template <int RT>  // compile-time search range (register-blocked path), 0 = any range
+// The prediction of quarter-sample offset (qx, qy) from an integer position
+// (8.4.2.2.1, Table 8-12) in terms of the half-sample grid around it, where
+// (X, Y) even/even is an integer sample G, odd/even b, even/odd h, odd/odd j:
+// a position on the grid is that sample; any other is (p + q + 1) >> 1 of
+// two grid neighbours, (XA, YA) and (XB, YB) — the horizontal or vertical
+// pair when one component is even, else the two of the cell's four corners
+// that are b / h samples.
+__device__ __forceinline__ void sp_pair(int qx, int qy, int &XA, int &YA, int &XB, int &YB) {
+  const int X0 = qx >> 1, Y0 = qy >> 1, ax = qx & 1, ay = qy & 1;
+  if (ax && ay) {
+    const int odd = (X0 + Y0) & 1;  // the corner (X0, Y0) is b or h
+    XA = X0 + 1 - odd;
+    YA = Y0;
+    XB = X0 + odd;
+    YB = Y0 + 1;
+  } else {
+    XA = X0;
+    YA = Y0;
+    XB = X0 + ax;
+    YB = Y0 + ay;
+  }
+}
+// rounding byte average of two dwords, no unpacking
+__device__ __forceinline__ uint32_t avg_u8x4(uint32_t p, uint32_t q) { return (p | q) - (((p ^ q) >> 1) & 0x7f7f7f7fu); }
+
+// RT: compile-time search range (register-blocked path), 0 = any range.
+// SP: sub-sample refinement around the integer winner, 0 none (the code is
+// the integer-only kernel's), 1 half samples, 2 half then quarter samples.
+template <int RT, int SP>
 __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
-  __shared__ __attribute__((aligned(16))) uint8_t win[(16 + 2 * kMaxRange) * kWinPitch];
+  constexpr int LX = SP ? kSpLoX : 0, LY = SP ? kSpLoY : 0, HI = SP ? kSpHi : 0;  // window margins
+  constexpr int WP = SP ? kWinPitchSp : kWinPitch;
+  static_assert(!(SP && VTS_SEARCH_UV_LDS), "the LDS chroma window is sized for integer vectors");
+  __shared__ __attribute__((aligned(16))) uint8_t win[(16 + 2 * kMaxRange + LY + HI) * WP];
   __shared__ __attribute__((aligned(16))) uint32_t srcy[64];
   __shared__ uint16_t winuv[kUvPitch * kUvPitch];
   const int lane = threadIdx.x;
@@ -268,8 +308,8 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
   const uint8_t *ref = en.y < 0 ? a.small + static_cast<int64_t>(en.x - 1) * a.stride
                                 : a.recon + static_cast<int64_t>(en.y) * a.stride;
   uint8_t *dst = a.recon + static_cast<int64_t>(en.z) * a.stride;
-  const int R = a.range, side = 2 * R + 1, wsz = 16 + 2 * R;
-  const int x0 = mx * 16 - R, y0 = my * 16 - R;
+  const int R = a.range, side = 2 * R + 1, wsz = 16 + 2 * R + LX + HI, wrows = 16 + 2 * R + LY + HI;
+  const int x0 = mx * 16 - R - LX, y0 = my * 16 - R - LY;
   // source luma: lane -> row lane / 4, 4 bytes
   srcy[lane] = *reinterpret_cast<const uint32_t *>(src + static_cast<int64_t>(my * 16 + (lane >> 2)) * a.cw +
                                                    mx * 16 + 4 * (lane & 3));
@@ -277,7 +317,7 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
     // window rows of W4 dwords (one division per lane, then carry stepping);
     // a dword wholly inside the picture row and aligned (R % 4 == 0) is one
     // load, else 4 edge-clamped byte loads
-    const int W4 = (wsz + 3) >> 2, total = wsz * W4;
+    const int W4 = (wsz + 3) >> 2, total = wrows * W4;
     int r = lane / W4, cd = lane - r * W4;
     const int dr = 64 / W4, dc = 64 - dr * W4;
     for (int k = lane; k < total; k += 64) {
@@ -291,7 +331,7 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) v |= static_cast<uint32_t>(rowp[min(max(sx + q, 0), a.cw - 1)]) << (8 * q);
       }
-      *reinterpret_cast<uint32_t *>(win + r * kWinPitch + 4 * cd) = v;
+      *reinterpret_cast<uint32_t *>(win + r * WP + 4 * cd) = v;
       r += dr;
       cd += dc;
       if (cd >= W4) {
@@ -332,14 +372,14 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
 #pragma unroll
       for (int g = 0; g < G; ++g) acc[g] = 0;
       const int sh = gx & 3;
-      const uint32_t *wb = reinterpret_cast<const uint32_t *>(win + dy0 * kWinPitch + (gx & ~3));
+      const uint32_t *wb = reinterpret_cast<const uint32_t *>(win + (dy0 + LY) * WP + LX + (gx & ~3));
 #if VTS_SEARCH_SRC_LDS
 #pragma unroll 2
 #else
 #pragma unroll
 #endif
       for (int w = 0; w < 16 + G - 1; ++w) {
-        const uint32_t *wr = wb + w * (kWinPitch / 4);
+        const uint32_t *wr = wb + w * (WP / 4);
         const uint32_t w0 = wr[0], w1 = wr[1], w2 = wr[2], w3 = wr[3], w4 = wr[4];
         const uint32_t r0 = __builtin_amdgcn_alignbyte(w1, w0, sh), r1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
         const uint32_t r2 = __builtin_amdgcn_alignbyte(w3, w2, sh), r3 = __builtin_amdgcn_alignbyte(w4, w3, sh);
@@ -379,11 +419,11 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
       const int ox = dx + R, sh = ox & 3;
       // per row: the 5 dwords covering the 16 candidate bytes, 4 byte-aligns,
       // the source row as one 16-byte broadcast read, 4 v_sad_u8
-      const uint32_t *wr = reinterpret_cast<const uint32_t *>(win + (dy + R) * kWinPitch + (ox & ~3));
+      const uint32_t *wr = reinterpret_cast<const uint32_t *>(win + (dy + R + LY) * WP + LX + (ox & ~3));
       const uint4 *sr = reinterpret_cast<const uint4 *>(srcy);
   #pragma unroll 4
       for (int yy = 0; yy < 16; ++yy) {
-        const uint32_t *w = wr + yy * (kWinPitch / 4);
+        const uint32_t *w = wr + yy * (WP / 4);
         const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
         const uint4 sv = sr[yy];
         s = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, sh), sv.x, s);
@@ -405,11 +445,113 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
   const int dy = r / side - R, dx = r % side - R;
   // prediction and cost: lane -> 4 luma samples (row lane/4) and one chroma pair
   const int ly = lane >> 2, lx = 4 * (lane & 3);
-  const uint32_t py = u32_at(win + (dy + R + ly) * kWinPitch, dx + R + lx);
+  int cqx = 0, cqy = 0;  // the refined vector, in quarter samples from the integer winner
+  uint32_t py;
+  if constexpr (SP > 0) {
+    // ---- sub-sample refinement.  With (x, y) relative to the integer
+    // winner's block, whose sample (0, 0) is win[oy][ox]: the half-sample
+    // planes b(x + 1/2, y), h(x, y + 1/2), j(x + 1/2, y + 1/2) for every
+    // position a candidate of either step reads, x, y in -1 .. 16 (the planes'
+    // index is x + 1, y + 1).  j is filtered from the unclipped horizontal
+    // intermediates of rows -3 .. 18, which also give b.
+    __shared__ int16_t hmid[22 * 18];
+    __shared__ __attribute__((aligned(16))) uint8_t pb[18 * kSpPitch], ph[17 * kSpPitch], pj[17 * kSpPitch];
+    const int ox = LX + R + dx, oy = LY + R + dy;
+    for (int i = lane; i < 22 * 17; i += 64) {  // x = xx - 1 in -1 .. 15, row yy - 3
+      const int yy = i / 17, xx = i - yy * 17;
+      const uint8_t *p = win + (oy - 3 + yy) * WP + ox + xx - 3;
+      const int t = full::tap6(p[0], p[1], p[2], p[3], p[4], p[5]);
+      hmid[yy * 18 + xx] = static_cast<int16_t>(t);
+      if (yy >= 2 && yy < 20) pb[(yy - 2) * kSpPitch + xx] = static_cast<uint8_t>(full::clip1((t + 16) >> 5));
+    }
+    for (int i = lane; i < 17 * 18; i += 64) {  // x = xx - 1 in -1 .. 16, y = yy - 1 in -1 .. 15
+      const int yy = i / 18, xx = i - yy * 18;
+      const uint8_t *p = win + (oy + yy - 3) * WP + ox + xx - 1;
+      const int t = full::tap6(p[0], p[WP], p[2 * WP], p[3 * WP], p[4 * WP], p[5 * WP]);
+      ph[yy * kSpPitch + xx] = static_cast<uint8_t>(full::clip1((t + 16) >> 5));
+    }
+    __syncthreads();
+    for (int i = lane; i < 17 * 17; i += 64) {  // x = xx - 1, y = yy - 1 in -1 .. 15: rows yy .. yy + 5 of hmid
+      const int yy = i / 17, xx = i - yy * 17;
+      const int16_t *p = hmid + yy * 18 + xx;
+      const int t = full::tap6(p[0], p[18], p[36], p[54], p[72], p[90]);
+      pj[yy * kSpPitch + xx] = static_cast<uint8_t>(full::clip1((t + 512) >> 10));
+    }
+    __syncthreads();
+    // the 4-aligned LDS row, byte offset and pitch at which block row 0 of
+    // the grid sample (X, Y), X, Y in -2 .. 2, starts
+    auto operand = [&](int X, int Y, const uint8_t *&row, int &off, int &pitch) {
+      const int cx = X >> 1, cy = Y >> 1;
+      if (!((X | Y) & 1)) {
+        row = win + (oy + cy) * WP;
+        off = ox + cx;
+        pitch = WP;
+      } else {
+        row = ((X & 1) ? ((Y & 1) ? pj : pb) : ph) + (cy + 1) * kSpPitch;
+        off = cx + 1;
+        pitch = kSpPitch;
+      }
+    };
+    // Per step the 8 candidates around the centre go to 8 lanes each (2 rows
+    // a lane); the centre's SAD is known.  Key (SAD, index): centre 0, the
+    // others 1 .. 8 in raster order.
+    uint32_t csad = static_cast<uint32_t>(best >> 32);
+#pragma unroll
+    for (int step = 2; step >= (SP == 2 ? 1 : 2); step >>= 1) {
+      const int k = (lane >> 3) + 1, pos = k - 1 < 4 ? k - 1 : k;
+      const int qx = cqx + step * (pos % 3 - 1), qy = cqy + step * (pos / 3 - 1);
+      int XA, YA, XB, YB, offa, offb, pa, pb_;
+      const uint8_t *ra, *rb;
+      sp_pair(qx, qy, XA, YA, XB, YB);
+      operand(XA, YA, ra, offa, pa);
+      operand(XB, YB, rb, offb, pb_);
+      uint32_t s = 0;
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr) {
+        const int row = 2 * (lane & 7) + rr;
+        const uint32_t *wa = reinterpret_cast<const uint32_t *>(ra + row * pa + (offa & ~3));
+        const uint32_t *wb = reinterpret_cast<const uint32_t *>(rb + row * pb_ + (offb & ~3));
+        const uint4 sv = reinterpret_cast<const uint4 *>(srcy)[row];
+        const uint32_t a0 = wa[0], a1 = wa[1], a2 = wa[2], a3 = wa[3], a4 = wa[4];
+        const uint32_t b0 = wb[0], b1 = wb[1], b2 = wb[2], b3 = wb[3], b4 = wb[4];
+        const int sa = offa & 3, sb = offb & 3;
+        s = __builtin_amdgcn_sad_u8(avg_u8x4(__builtin_amdgcn_alignbyte(a1, a0, sa), __builtin_amdgcn_alignbyte(b1, b0, sb)), sv.x, s);
+        s = __builtin_amdgcn_sad_u8(avg_u8x4(__builtin_amdgcn_alignbyte(a2, a1, sa), __builtin_amdgcn_alignbyte(b2, b1, sb)), sv.y, s);
+        s = __builtin_amdgcn_sad_u8(avg_u8x4(__builtin_amdgcn_alignbyte(a3, a2, sa), __builtin_amdgcn_alignbyte(b3, b2, sb)), sv.z, s);
+        s = __builtin_amdgcn_sad_u8(avg_u8x4(__builtin_amdgcn_alignbyte(a4, a3, sa), __builtin_amdgcn_alignbyte(b4, b3, sb)), sv.w, s);
+      }
+      s += __shfl_xor(s, 1);
+      s += __shfl_xor(s, 2);
+      s += __shfl_xor(s, 4);
+      uint64_t key = (static_cast<uint64_t>(s) << 32) | static_cast<uint32_t>(k);
+      const uint64_t ckey = static_cast<uint64_t>(csad) << 32;
+      key = ckey < key ? ckey : key;
+#pragma unroll
+      for (int off = 32; off >= 8; off >>= 1) {
+        const uint64_t o = __shfl_xor(key, off);
+        key = o < key ? o : key;
+      }
+      const int kw = static_cast<int>(key & 0xffffffffu);
+      if (kw) {  // wave-uniform
+        const int pw = kw - 1 < 4 ? kw - 1 : kw;
+        cqx += step * (pw % 3 - 1);
+        cqy += step * (pw / 3 - 1);
+        csad = static_cast<uint32_t>(key >> 32);
+      }
+    }
+    int XA, YA, XB, YB, offa, offb, pa, pb_;
+    const uint8_t *ra, *rb;
+    sp_pair(cqx, cqy, XA, YA, XB, YB);
+    operand(XA, YA, ra, offa, pa);
+    operand(XB, YB, rb, offb, pb_);
+    py = avg_u8x4(u32_at(ra + ly * pa, offa + lx), u32_at(rb + ly * pb_, offb + lx));
+  } else {
+    py = u32_at(win + (dy + R + ly) * kWinPitch, dx + R + lx);
+  }
   const uint32_t sy4 = srcy[lane];
   uint32_t cost = __builtin_amdgcn_sad_u8(py, sy4, 0);
   const int ci = lane & 7, cj = lane >> 3;
-  const int mvx = 4 * dx, mvy = 4 * dy, fx = mvx & 7, fy = mvy & 7;
+  const int mvx = 4 * dx + cqx, mvy = 4 * dy + cqy, fx = mvx & 7, fy = mvy & 7;
   // window coordinates of taps (xi, yi) and (xi + 1, yi + 1); the window holds
   // the clamped samples, so this equals the decoder's per-tap clamping
 #if VTS_SEARCH_UV_LDS
@@ -443,6 +585,8 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
     if (lane == 0) {
       a.cmd[e * a.nmb + mb] = inter ? mvw : kPcmCmd;
       if (a.cbp) a.cbp[e * a.nmb + mb] = 0;
+      if constexpr (SP > 0)
+        if (inter && ((mvx | mvy) & 3)) atomicAdd(&a.sp_stats[(mvx | mvy) & 1], 1ull);
     }
     return;
   }
@@ -580,6 +724,8 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
   if (lane == 0) {
     a.cmd[e * a.nmb + mb] = inter ? mvw : kPcmCmd;
     a.cbp[e * a.nmb + mb] = static_cast<uint8_t>(inter ? cbp : 0);
+    if constexpr (SP > 0)
+      if (inter && ((mvx | mvy) & 3)) atomicAdd(&a.sp_stats[(mvx | mvy) & 1], 1ull);
   }
 }
 
@@ -1583,14 +1729,41 @@ int small_window(vts_ctx *c, int ring, int64_t f0, int64_t f1, hipStream_t s) {
   return VTS_OK;
 }
 
+namespace {
+template <int SP>
+void launch_search(int R, dim3 grid, hipStream_t s, const SearchArgs &sa) {
+  switch (R) {
+    case 4: hipLaunchKernelGGL((enc_search<4, SP>), grid, dim3(64), 0, s, sa); break;
+    case 8: hipLaunchKernelGGL((enc_search<8, SP>), grid, dim3(64), 0, s, sa); break;
+    case 16: hipLaunchKernelGGL((enc_search<16, SP>), grid, dim3(64), 0, s, sa); break;
+    default: hipLaunchKernelGGL((enc_search<0, SP>), grid, dim3(64), 0, s, sa); break;
+  }
+}
+}  // namespace
+
 }  // namespace vts
 
 using namespace vts;
 
 extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transcode_params *pin,
                              vts_transcode_info *info) {
+  return vts_transcode_ex(c, out_path, pin, nullptr, info, nullptr);
+}
+
+extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_transcode_params *pin,
+                                const vts_transcode_ext *ext, vts_transcode_info *info,
+                                vts_transcode_ext_info *xinfo) {
   clear_error();
   if (!c || !out_path) return fail(VTS_E_INVALID, "NULL argument");
+  // size-tagged structs: only the prefix known here is read or written
+  int subpel = 0;
+  if (ext) {
+    if (ext->struct_size < 8) return fail(VTS_E_INVALID, "vts_transcode_ext.struct_size %u < 8", ext->struct_size);
+    subpel = ext->subpel;
+    if (subpel < 0 || subpel > 2) return fail(VTS_E_INVALID, "subpel %d: 0, 1 or 2", subpel);
+  }
+  if (xinfo && xinfo->struct_size < 8)
+    return fail(VTS_E_INVALID, "vts_transcode_ext_info.struct_size %u < 8", xinfo->struct_size);
   using clk = std::chrono::steady_clock;
   vts_transcode_params p{};
   if (pin) p = *pin;
@@ -1601,6 +1774,7 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
   if (qp > 51) return fail(VTS_E_INVALID, "qp %d > 51", qp);
   if (p.intra != 0 && p.intra != 1) return fail(VTS_E_INVALID, "intra %d: 0 or 1", p.intra);
   const bool intra = p.intra == 1;
+  const bool hashed = intra || subpel != 0;  // recon_hash is computed
   if (intra && qp < 1) return fail(VTS_E_INVALID, "intra = 1 needs residual coding (qp >= 0)");
   const int keyint = p.keyint > 0 ? p.keyint : 250;
   const float thr = p.cut_threshold > 0 ? p.cut_threshold : c->params.cut_threshold;
@@ -1693,7 +1867,8 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
   VTS_TRY(B.get(&d_fr, static_cast<size_t>(2 * n)));  // per frame: absolute offset, size
   VTS_TRY(B.get(&d_sizes, static_cast<size_t>(max_chunk * mbh)));
   VTS_TRY(B.get(&d_offs, static_cast<size_t>(max_chunk * mbh)));
-  VTS_TRY(B.get(&d_stats, 5));  // pcm, inter, skip, intra macroblocks; the reconstruction hash
+  // pcm, inter, skip, intra macroblocks; the reconstruction hash; enc_search's two sub-sample counts
+  VTS_TRY(B.get(&d_stats, 7));
   VTS_TRY(B.get(&d_err, 1));
   uint4 *d_jobs;
   uint32_t *d_njobs;
@@ -1708,8 +1883,16 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
   B.streams = {s1, s2};
   HIP_TRY(hipMemcpy(d_sent, sent.data(), sent.size() * sizeof(int4), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_went, went.data(), went.size() * sizeof(int4), hipMemcpyHostToDevice));
+  int4 *d_hent = nullptr;  // level 0's entries with the frame as the slot (enqueue_hash)
+  if (hashed && !intra) {
+    std::vector<int4> hent(sent.begin(), sent.begin() + lvl_off[1]);
+    for (int4 &h : hent) h.z = h.x;
+    VTS_TRY(B.get(&d_hent, hent.size()));
+    HIP_TRY(hipMemcpy(d_hent, hent.data(), hent.size() * sizeof(int4), hipMemcpyHostToDevice));
+  }
   HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), s2));
-  if (intra) HIP_TRY(hipMemsetAsync(d_stats + 4, 0, sizeof(unsigned long long), s1));  // enc_hash (s1) adds into it
+  // enc_hash and enc_search<., SP > 0> (s1) add into these
+  if (hashed) HIP_TRY(hipMemsetAsync(d_stats + 4, 0, 3 * sizeof(unsigned long long), s1));
   HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(uint32_t), s2));
   const int64_t nchunks = (maxlen + kChunkLevels - 1) / kChunkLevels;
   std::vector<hipEvent_t> ev(static_cast<size_t>(maxlen + 5 + nchunks), nullptr);
@@ -1744,14 +1927,21 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
     ia.qp = qp;
     ia.all = j == 0;
     hipLaunchKernelGGL(enc_intra, dim3(static_cast<unsigned>(ne * mbh)), dim3(64), 0, s1, ia);
-    const int hb = std::max(1, std::min(64, (S.w * S.h * 3 / 2 + 4095) / 4096));
-    hipLaunchKernelGGL(enc_hash, dim3(static_cast<unsigned>(hb * ne)), dim3(256), 0, s1, d_sent + lvl_off[j], d_recon,
-                       S.stride, S.cw, S.ch, S.w, S.h, hb, d_stats + 4);
   };
-  if (intra) {
-    enqueue_intra(0);
-    HIP_TRY(hipEventRecord(ev[0], s1));
-  }
+  // the level's pictures hashed where the next level reads them: the
+  // reconstruction slots, or (level 0 without intra: the IDR pictures are
+  // their source) the small store, through entries whose slot is the frame
+  auto enqueue_hash = [&](int64_t j) {
+    const int64_t ne = lvl_off[j + 1] - lvl_off[j];
+    const bool from_source = j == 0 && !intra;
+    const int hb = std::max(1, std::min(64, (S.w * S.h * 3 / 2 + 4095) / 4096));
+    hipLaunchKernelGGL(enc_hash, dim3(static_cast<unsigned>(hb * ne)), dim3(256), 0, s1,
+                       from_source ? d_hent : d_sent + lvl_off[j], from_source ? S.d : d_recon, S.stride, S.cw, S.ch,
+                       S.w, S.h, hb, d_stats + 4);
+  };
+  if (intra) enqueue_intra(0);
+  if (hashed) enqueue_hash(0);
+  if (intra) HIP_TRY(hipEventRecord(ev[0], s1));
   int64_t next_search = 1;
   bool searches_done = false;
   // enqueue the searches of levels < upto; level j reuses the ring slot of
@@ -1776,14 +1966,15 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
       sa.range = R;
       sa.max_sad = T;
       sa.qp = qp;
+      sa.sp_stats = d_stats + 5;
       const dim3 grid(static_cast<unsigned>(ne * nmb));
-      switch (R) {
-        case 4: hipLaunchKernelGGL(enc_search<4>, grid, dim3(64), 0, s1, sa); break;
-        case 8: hipLaunchKernelGGL(enc_search<8>, grid, dim3(64), 0, s1, sa); break;
-        case 16: hipLaunchKernelGGL(enc_search<16>, grid, dim3(64), 0, s1, sa); break;
-        default: hipLaunchKernelGGL(enc_search<0>, grid, dim3(64), 0, s1, sa); break;
+      switch (subpel) {
+        case 1: launch_search<1>(R, grid, s1, sa); break;
+        case 2: launch_search<2>(R, grid, s1, sa); break;
+        default: launch_search<0>(R, grid, s1, sa); break;
       }
       if (intra) enqueue_intra(j);
+      if (hashed) enqueue_hash(j);
       HIP_TRY(hipEventRecord(ev[j], s1));
     }
     if (next_search >= maxlen && !searches_done) {
@@ -1903,7 +2094,7 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
   }
   VTS_TRY(status);
   uint32_t err = 0;
-  unsigned long long st[5] = {0, 0, 0, 0, 0};
+  unsigned long long st[7] = {0, 0, 0, 0, 0, 0, 0};
   HIP_TRY(hipMemcpy(&err, d_err, sizeof err, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost));
   if (err) return fail(VTS_E_CAPACITY, "a slice exceeded its %lld-byte staging slot", static_cast<long long>(cap));
@@ -1936,9 +2127,13 @@ extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transco
     info->inter_mbs = static_cast<int64_t>(st[1]);
     info->skip_mbs = static_cast<int64_t>(st[2]);
     info->intra_mbs = static_cast<int64_t>(st[3]);
-    info->recon_hash = intra ? st[4] : 0;
+    info->recon_hash = hashed ? st[4] : 0;
     info->bytes_written = mw.bytes_written();
     for (int i = 0; i < 4; ++i) info->ms[i] = ms[i];
+  }
+  if (xinfo) {
+    if (xinfo->struct_size >= 16) xinfo->subpel_mbs = subpel ? static_cast<int64_t>(st[5] + st[6]) : 0;
+    if (xinfo->struct_size >= 24) xinfo->qpel_mbs = subpel ? static_cast<int64_t>(st[6]) : 0;
   }
   return VTS_OK;
 }

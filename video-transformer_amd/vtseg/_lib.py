@@ -123,6 +123,17 @@ class TranscodeInfo(C.Structure):
                 ("intra_mbs", C.c_int64), ("recon_hash", C.c_uint64)]
 
 
+class TranscodeExt(C.Structure):
+    """Size-tagged: set struct_size = sizeof(TranscodeExt)."""
+    _fields_ = [("struct_size", C.c_uint32), ("subpel", C.c_int32)]
+
+
+class TranscodeExtInfo(C.Structure):
+    """Size-tagged: set struct_size = sizeof(TranscodeExtInfo)."""
+    _fields_ = [("struct_size", C.c_uint32), ("_pad", C.c_int32),
+                ("subpel_mbs", C.c_int64), ("qpel_mbs", C.c_int64)]
+
+
 class ManifestArgs(C.Structure):
     _fields_ = [("video_id", C.c_char_p), ("segment_dir", C.c_char_p),
                 ("created_at", C.c_char_p), ("duration", C.c_double),
@@ -182,6 +193,9 @@ SIGNATURES: dict[str, tuple] = {
     "vts_close": (C.c_int, [C.c_void_p]),
     "vts_transcode": (C.c_int, [C.c_void_p, C.c_char_p, _P(TranscodeParams),
                                 _P(TranscodeInfo)]),
+    "vts_transcode_ex": (C.c_int, [C.c_void_p, C.c_char_p, _P(TranscodeParams),
+                                   _P(TranscodeExt), _P(TranscodeInfo),
+                                   _P(TranscodeExtInfo)]),
     "vts_synth_write": (C.c_int, [C.c_char_p, _P(SynthParams), _P(SynthInfo),
                                   _P(C.c_int64), C.c_int64]),
     "vts_rccl_unique_id": (C.c_int, [_P(C.c_uint8)]),
