@@ -408,7 +408,8 @@ void vts_batch_free(vts_batch *b);
  * if asked), P pictures of full-search
  * integer motion (P_L0_16x16 / P_Skip; refined to half or quarter samples
  * with vts_transcode_ext.subpel) with a quantised residual (qp), I_PCM
- * where that residual would cost more; one slice per macroblock row; MP4
+ * where that residual would cost more; one slice per macroblock row, the
+ * in-loop filter off or (vts_transcode_ext2.deblock) on inside each slice; MP4
  * (moov at the end), video only.  DESIGN.md §11. */
 typedef struct vts_transcode_params {
   int32_t height;          /* output display height, even; 0 = 360            */
@@ -449,7 +450,7 @@ typedef struct vts_transcode_info {
                               (stream 2, overlaps the searches), MP4 mux      */
   int64_t intra_mbs;       /* Intra16x16 macroblocks (intra = 1); pcm_mbs counts
                               only the macroblocks that stayed I_PCM           */
-  uint64_t recon_hash;     /* intra = 1 or subpel != 0: the encoder's own
+  uint64_t recon_hash;     /* intra = 1, subpel != 0 or deblock = 1: the encoder's own
                               reconstruction, hashed as
                               vts_synth_info.recon_hash (display-size NV12, f =
                               the frame index; an I_PCM IDR picture is its
@@ -481,6 +482,35 @@ typedef struct vts_transcode_ext_info {
   int64_t subpel_mbs;      /* inter macroblocks with a fractional vector       */
   int64_t qpel_mbs;        /* ... with an odd (quarter-sample) component       */
 } vts_transcode_ext_info;
+
+/* The in-loop deblocking filter (8.7) in the encoder, DESIGN.md §11.  Both
+ * structs begin with the ones above and are passed to vts_transcode_ex by
+ * pointer cast with struct_size = their own sizeof; the library reads deblock
+ * when struct_size >= 12, deblock_alpha at >= 16, deblock_beta at >= 20 (a
+ * field the struct does not reach is 0) and writes deblock_mbs at >= 32.
+ * deblock = 1: every slice (one per macroblock row) carries
+ * disable_deblocking_filter_idc = 2 and the two offsets, and the encoder
+ * filters its own reconstruction the same way before the next picture
+ * predicts from it: the left macroblock edge and the inner 4x4 edges, never
+ * the top macroblock edge (a slice boundary; idc 0 is not offered).  Needs
+ * residual coding (qp >= 0).  VTS_E_INVALID, the field named in the message:
+ * deblock not 0 or 1, an offset outside -6..6, a non-zero offset with
+ * deblock = 0, deblock = 1 with qp < 0.  recon_hash is also filled when
+ * deblock = 1. */
+typedef struct vts_transcode_ext2 {
+  vts_transcode_ext base;
+  int32_t deblock;         /* 0 off (every output byte as before), 1 on         */
+  int32_t deblock_alpha;   /* slice_alpha_c0_offset_div2, -6..6                 */
+  int32_t deblock_beta;    /* slice_beta_offset_div2, -6..6                     */
+  int32_t _pad;
+} vts_transcode_ext2;
+
+typedef struct vts_transcode_ext_info2 {
+  vts_transcode_ext_info base;
+  int64_t deblock_mbs;     /* macroblocks in which the filter ran on at least
+                              one sample line (filterSamplesFlag); 0 when
+                              deblock is off                                   */
+} vts_transcode_ext_info2;
 
 /* vts_transcode with the settings of `ext` (NULL: none) and the further facts
  * in `ext_info` (NULL: not wanted).  vts_transcode(c, o, p, i) is

@@ -34,6 +34,7 @@
 #include <string>
 #include <vector>
 
+#include "enc_deblock.h"
 #include "mp4.h"
 #include "recon_full.h"
 #include "session.h"
@@ -41,7 +42,7 @@
 namespace vts {
 namespace {
 
-constexpr uint32_t kPcmCmd = 0x80008000u;  // (mvx, mvy) = (-32768, -32768): never a motion
+using full::edb::kPcmCmd;  // (mvx, mvy) = (-32768, -32768): never a motion (enc_deblock.h)
 constexpr int kMaxTaps = 16;
 constexpr int kMaxRange = 16;
 constexpr int kWinPitch = 16 + 2 * kMaxRange + 4;  // LDS window row pitch (bytes)
@@ -748,7 +749,7 @@ struct WriteArgs {
   uint4 *jobs;          // I_PCM payloads left for enc_pcm: (slice, byte offset in the slot, mx, 0)
   uint32_t *n_jobs;
   int32_t n_slices;
-  int32_t _pad;
+  int32_t dbk_alpha, dbk_beta, _pad;  // enc_write<., true>: slice_alpha_c0_offset_div2, slice_beta_offset_div2
 };
 
 // RBSP bits -> EBSP bytes (emulation prevention) into a staging slot, four
@@ -897,8 +898,8 @@ __device__ int cavlc_block(NalOut *o, const int *lv, int maxNum, int nC) {
 // Command word of an Intra16x16 macroblock: the high half 0x8000 (mvy =
 // -32768: never a motion) with bit 15 clear; bits 0..1 Intra16x16PredMode,
 // 2..3 intra_chroma_pred_mode, 4..9 coded_block_pattern (luma 0 or 15).
-constexpr uint32_t kIntraCmd = 0x80000000u;
-__device__ __forceinline__ bool is_intra_cmd(uint32_t c) { return (c & 0xffff8000u) == kIntraCmd; }
+using full::edb::kIntraCmd;
+using full::edb::is_intra_cmd;
 __device__ __forceinline__ int ue_bits(uint32_t v) { return 2 * (31 - __builtin_clz(v + 1)) + 1; }
 // nC of 9.2.1 from the left (na) and upper (nb) blocks' total_coeff, -1 = unavailable
 __device__ __forceinline__ int nc_of(int na, int nb) {
@@ -1217,6 +1218,142 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
   }
 }
 
+// ------------------------------------------------------ in-loop deblocking
+// vts_transcode_ext2.deblock: every slice carries
+// disable_deblocking_filter_idc = 2 and a slice is one macroblock row, so a
+// row's filtering (8.7) is a serial chain over its macroblocks that touches no
+// other row: one wave per (level entry, macroblock row) walking mx = 0 ..
+// mbw - 1, as enc_intra does; all ordering is program order inside the wave
+// plus stream order between launches.  Per macroblock, in the standard's
+// order: the vertical edges e = 0..3 (0 only with a left neighbour), then the
+// horizontal edges 1..3 (the top edge is a slice boundary); an edge step is 16
+// luma lines on lanes 0..15 and, for e = 0 and 2, 8 Cb + 8 Cr lines on lanes
+// 16..31.  The decisions (bS, indexA / indexB, the line filter) are
+// enc_deblock.h's, which the CPU harness walks in the same order.
+//
+// LDS tile, 24 rows of kDbPitch bytes: rows 0..15 luma, 16..23 the Cb|Cr
+// pairs; bytes 0..3 of a row the left macroblock's last four luma columns
+// (last two chroma pairs), bytes 4..19 this macroblock.  A macroblock ends
+// with one 16-byte store per row: the left macroblock's final columns 12..15
+// and this one's columns 0..11 (the next edge 0 still changes 13..15).
+struct DeblockArgs {
+  const int4 *ent;      // the level's search entries: (frame, -, dst slot, 0)
+  uint8_t *recon;       // [slot]
+  int64_t stride;
+  const uint32_t *cmd;  // [entry][mb]
+  const uint8_t *cbp;   // [entry][mb]
+  const int16_t *coef;  // [entry][mb][kCoefPerMb] (this level's ring slot)
+  int32_t cw, ch, mbw, mbh;
+  int32_t qp, off_a, off_b, _pad;  // SliceQPY, FilterOffsetA, FilterOffsetB
+  unsigned long long *count;       // macroblocks with a filtered line
+};
+constexpr int kDbPitch = 20;
+
+__global__ void __launch_bounds__(64) enc_deblock(DeblockArgs a) {
+  namespace edb = full::edb;
+  __shared__ __attribute__((aligned(16))) uint8_t T[24 * kDbPitch];
+  struct alignas(16) Lv {
+    int16_t s[16];
+  };
+  const int lane = threadIdx.x;
+  const int e = blockIdx.x / a.mbh, my = blockIdx.x % a.mbh;
+  const int4 en = a.ent[e];
+  uint8_t *dst = a.recon + static_cast<int64_t>(en.z) * a.stride;
+  const int64_t mb0 = (static_cast<int64_t>(e) * a.mbh + my) * a.mbw;
+  // loads and stores: lane (r, q4) moves dword q4 of luma row r and, below 32, of chroma row r
+  const int r = lane >> 2, q4 = 4 * (lane & 3);
+  uint8_t *gy = dst + static_cast<int64_t>(my * 16 + r) * a.cw + q4;
+  uint8_t *gc = dst + static_cast<int64_t>(a.cw) * a.ch + static_cast<int64_t>(my * 8 + (r & 7)) * a.cw + q4;
+  uint8_t *ty = T + r * kDbPitch + q4, *tc = T + (16 + (r & 7)) * kDbPitch + q4;
+  // filtering: lanes 0..15 luma line `lane`; 16..31 plane pl, chroma line kc (the luma line 2 kc)
+  const bool chroma = lane >= 16;
+  const int pl = (lane >> 3) & 1, kc = lane & 7, line = chroma ? 2 * kc : lane;
+  auto load_lv = [&](int mx, Lv &lv) {
+    if (lane < 16) {
+      const uint4 *p = reinterpret_cast<const uint4 *>(a.coef + (mb0 + mx) * kCoefPerMb + 16 * lane);
+      reinterpret_cast<uint4 *>(lv.s)[0] = p[0];
+      reinterpret_cast<uint4 *>(lv.s)[1] = p[1];
+    }
+  };
+  // the next macroblock's samples, command, coded_block_pattern and levels, read one macroblock ahead
+  uint32_t pf_y = *reinterpret_cast<const uint32_t *>(gy), pf_c = 0;
+  if (lane < 32) pf_c = *reinterpret_cast<const uint32_t *>(gc);
+  uint32_t n_cmd = a.cmd[mb0];
+  int n_cbp = a.cbp[mb0];
+  Lv n_lv{};
+  load_lv(0, n_lv);
+  // indexA, alpha' and beta' of this lane's plane for the three qPav an edge can have (qP is 0 for
+  // I_PCM and the slice QP otherwise), looked up once: both sides I_PCM, one side, neither
+  const edb::Idx x_pcm = edb::indices(0, 0, a.off_a, a.off_b, chroma, 0);
+  const edb::Idx x_mix = edb::indices(0, a.qp, a.off_a, a.off_b, chroma, 0);
+  const edb::Idx x_qp = edb::indices(a.qp, a.qp, a.off_a, a.off_b, chroma, 0);
+  uint32_t carry = 0;  // lanes 0..23: the row's last dword of the macroblock to the left
+  edb::Mb left = edb::mb_of_cmd(kPcmCmd, 0);
+  bool prev_filtered = false;  // wave-uniform
+  for (int mx = 0; mx < a.mbw; ++mx) {
+    *reinterpret_cast<uint32_t *>(ty + 4) = pf_y;
+    if (lane < 32) *reinterpret_cast<uint32_t *>(tc + 4) = pf_c;
+    if (lane < 24) *reinterpret_cast<uint32_t *>(T + lane * kDbPitch) = carry;
+    const uint32_t cmd = n_cmd;
+    const bool nzb = lane < 16 && edb::blk_nz(n_lv.s, n_cbp, lane);
+    if (mx + 1 < a.mbw) {
+      pf_y = *reinterpret_cast<const uint32_t *>(gy + (mx + 1) * 16);
+      if (lane < 32) pf_c = *reinterpret_cast<const uint32_t *>(gc + (mx + 1) * 16);
+      n_cmd = a.cmd[mb0 + mx + 1];
+      n_cbp = a.cbp[mb0 + mx + 1];
+      load_lv(mx + 1, n_lv);
+    }
+    const edb::Mb cur = edb::mb_of_cmd(cmd, edb::nz_raster(static_cast<uint32_t>(__ballot(nzb))));
+    __syncthreads();
+    bool filtered = false;
+#pragma unroll
+    for (int dir = 0; dir < 2; ++dir)
+#pragma unroll
+      for (int ed = 0; ed < 4; ++ed) {
+        if (ed == 0 && (dir == 1 || mx == 0)) continue;
+        const edb::Mb &p = ed == 0 ? left : cur;
+        const bool mine = lane < 16 || (lane < 32 && !(ed & 1));
+        const int bS = mine ? edb::line_bs(p, cur, dir, ed, line) : 0;
+        const int qpp = edb::qp_of(p, a.qp), qpq = edb::qp_of(cur, a.qp);
+        const edb::Idx x = qpp != qpq ? x_mix : (qpp ? x_qp : x_pcm);
+        const bool act = bS > 0 && x.alpha && x.beta;
+        if (__ballot(act)) {  // wave-uniform
+          if (act) {
+            uint8_t *s;
+            int step;
+            if (dir == 0) {
+              s = T + (chroma ? 16 + kc : lane) * kDbPitch + 4 + 4 * ed + (chroma ? pl : 0);
+              step = chroma ? 2 : 1;
+            } else {
+              s = T + (chroma ? 16 + 2 * ed : 4 * ed) * kDbPitch + 4 + (chroma ? 2 * kc + pl : lane);
+              step = kDbPitch;
+            }
+            filtered |= edb::filter(s, step, bS, chroma, x);
+          }
+          __syncthreads();
+        }
+      }
+    const bool wave_filtered = __ballot(filtered) != 0;
+    const uint32_t oy = *reinterpret_cast<const uint32_t *>(ty);
+    const uint32_t oc = lane < 32 ? *reinterpret_cast<const uint32_t *>(tc) : 0;
+    if (lane < 24) carry = *reinterpret_cast<const uint32_t *>(T + lane * kDbPitch + 16);
+    __syncthreads();
+    // columns 12..15 of the macroblock to the left changed here or in its own step; 0..11 of this one here
+    if ((wave_filtered || prev_filtered) && (mx > 0 || q4 > 0)) {
+      *reinterpret_cast<uint32_t *>(gy + mx * 16 - 4) = oy;
+      if (lane < 32) *reinterpret_cast<uint32_t *>(gc + mx * 16 - 4) = oc;
+    }
+    if (wave_filtered && lane == 0) atomicAdd(a.count, 1ull);
+    prev_filtered = wave_filtered;
+    left = cur;
+  }
+  if (prev_filtered && lane < 24) {  // the last macroblock's columns 12..15
+    uint8_t *g = lane < 16 ? dst + static_cast<int64_t>(my * 16 + lane) * a.cw
+                           : dst + static_cast<int64_t>(a.cw) * a.ch + static_cast<int64_t>(my * 8 + lane - 16) * a.cw;
+    *reinterpret_cast<uint32_t *>(g + a.mbw * 16 - 4) = carry;
+  }
+}
+
 // The encoder's reconstruction hashed as vts_synth_info.recon_hash: over the
 // display-size NV12 bytes j of each of the level's frames f, b_j ((j % 65521)
 // + 1) (f + 1) added into *acc (wrap-around addition: any order).
@@ -1360,8 +1497,10 @@ __device__ void pcm_gap(NalOut &o, uint4 *job, int s, int mx) {
 }
 
 // kIntra: enc_intra ran on every level, so IDR pictures have commands too and
-// a command may be kIntraCmd (the other instance is the encoder without it)
-template <bool kIntra>
+// a command may be kIntraCmd (the other instance is the encoder without it).
+// kDbk: the slices ask for the in-loop filter inside the slice (enc_deblock
+// ran on the reconstruction); false: the header, and the code, without it
+template <bool kIntra, bool kDbk>
 __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= a.n_slices) return;
@@ -1382,7 +1521,13 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
     o.bits(3, 0);  // num_ref_idx_active_override, ref_pic_list_modification_l0, adaptive_ref_pic_marking
   }
   o.se(a.qp >= 1 ? a.qp - 26 : 0);  // slice_qp_delta: SliceQPY = the residual's QP (pic_init_qp 26)
-  o.ue(1);  // disable_deblocking_filter_idc
+  if constexpr (kDbk) {
+    o.ue(2);  // disable_deblocking_filter_idc: filtered, but not across slice boundaries
+    o.se(a.dbk_alpha);  // slice_alpha_c0_offset_div2
+    o.se(a.dbk_beta);   // slice_beta_offset_div2
+  } else {
+    o.ue(1);  // disable_deblocking_filter_idc
+  }
   unsigned long long npcm = 0, ninter = 0, nskip = 0, nintra = 0;
   uint32_t skip = 0;
   bool a_ok = false;
@@ -1756,11 +1901,21 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   clear_error();
   if (!c || !out_path) return fail(VTS_E_INVALID, "NULL argument");
   // size-tagged structs: only the prefix known here is read or written
-  int subpel = 0;
+  int subpel = 0, deblock = 0, dbk_alpha = 0, dbk_beta = 0;
   if (ext) {
     if (ext->struct_size < 8) return fail(VTS_E_INVALID, "vts_transcode_ext.struct_size %u < 8", ext->struct_size);
     subpel = ext->subpel;
     if (subpel < 0 || subpel > 2) return fail(VTS_E_INVALID, "subpel %d: 0, 1 or 2", subpel);
+    // vts_transcode_ext2: each field only when the caller's struct holds it
+    const vts_transcode_ext2 *x2 = reinterpret_cast<const vts_transcode_ext2 *>(ext);
+    if (ext->struct_size >= 12) deblock = x2->deblock;
+    if (ext->struct_size >= 16) dbk_alpha = x2->deblock_alpha;
+    if (ext->struct_size >= 20) dbk_beta = x2->deblock_beta;
+    if (deblock != 0 && deblock != 1) return fail(VTS_E_INVALID, "deblock %d: 0 or 1", deblock);
+    if (dbk_alpha < -6 || dbk_alpha > 6) return fail(VTS_E_INVALID, "deblock_alpha %d: -6 .. 6", dbk_alpha);
+    if (dbk_beta < -6 || dbk_beta > 6) return fail(VTS_E_INVALID, "deblock_beta %d: -6 .. 6", dbk_beta);
+    if (!deblock && dbk_alpha) return fail(VTS_E_INVALID, "deblock_alpha %d without deblock = 1", dbk_alpha);
+    if (!deblock && dbk_beta) return fail(VTS_E_INVALID, "deblock_beta %d without deblock = 1", dbk_beta);
   }
   if (xinfo && xinfo->struct_size < 8)
     return fail(VTS_E_INVALID, "vts_transcode_ext_info.struct_size %u < 8", xinfo->struct_size);
@@ -1774,8 +1929,9 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   if (qp > 51) return fail(VTS_E_INVALID, "qp %d > 51", qp);
   if (p.intra != 0 && p.intra != 1) return fail(VTS_E_INVALID, "intra %d: 0 or 1", p.intra);
   const bool intra = p.intra == 1;
-  const bool hashed = intra || subpel != 0;  // recon_hash is computed
+  const bool hashed = intra || subpel != 0 || deblock;  // recon_hash is computed
   if (intra && qp < 1) return fail(VTS_E_INVALID, "intra = 1 needs residual coding (qp >= 0)");
+  if (deblock && qp < 1) return fail(VTS_E_INVALID, "deblock = 1 needs residual coding (qp >= 0)");
   const int keyint = p.keyint > 0 ? p.keyint : 250;
   const float thr = p.cut_threshold > 0 ? p.cut_threshold : c->params.cut_threshold;
   if ((sh & 1) || sh < 16 || sh > c->height)
@@ -1867,8 +2023,9 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   VTS_TRY(B.get(&d_fr, static_cast<size_t>(2 * n)));  // per frame: absolute offset, size
   VTS_TRY(B.get(&d_sizes, static_cast<size_t>(max_chunk * mbh)));
   VTS_TRY(B.get(&d_offs, static_cast<size_t>(max_chunk * mbh)));
-  // pcm, inter, skip, intra macroblocks; the reconstruction hash; enc_search's two sub-sample counts
-  VTS_TRY(B.get(&d_stats, 7));
+  // pcm, inter, skip, intra macroblocks; the reconstruction hash; enc_search's two sub-sample counts;
+  // enc_deblock's filtered macroblocks
+  VTS_TRY(B.get(&d_stats, 8));
   VTS_TRY(B.get(&d_err, 1));
   uint4 *d_jobs;
   uint32_t *d_njobs;
@@ -1891,8 +2048,8 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
     HIP_TRY(hipMemcpy(d_hent, hent.data(), hent.size() * sizeof(int4), hipMemcpyHostToDevice));
   }
   HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), s2));
-  // enc_hash and enc_search<., SP > 0> (s1) add into these
-  if (hashed) HIP_TRY(hipMemsetAsync(d_stats + 4, 0, 3 * sizeof(unsigned long long), s1));
+  // enc_hash, enc_search<., SP > 0> and enc_deblock (s1) add into these
+  if (hashed) HIP_TRY(hipMemsetAsync(d_stats + 4, 0, 4 * sizeof(unsigned long long), s1));
   HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(uint32_t), s2));
   const int64_t nchunks = (maxlen + kChunkLevels - 1) / kChunkLevels;
   std::vector<hipEvent_t> ev(static_cast<size_t>(maxlen + 5 + nchunks), nullptr);
@@ -1928,6 +2085,29 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
     ia.all = j == 0;
     hipLaunchKernelGGL(enc_intra, dim3(static_cast<unsigned>(ne * mbh)), dim3(64), 0, s1, ia);
   };
+  // deblock: the level's reconstruction filtered in place (8.7, inside each
+  // macroblock row's slice) behind its search and intra coding, before it is
+  // hashed and the next level predicts from it.  Level 0 without intra is all
+  // I_PCM (qPav 0, alpha' 0: nothing is filtered) and is not launched
+  auto enqueue_deblock = [&](int64_t j) {
+    const int64_t ne = lvl_off[j + 1] - lvl_off[j];
+    DeblockArgs da{};
+    da.ent = d_sent + lvl_off[j];
+    da.recon = d_recon;
+    da.stride = S.stride;
+    da.cmd = d_cmd + lvl_off[j] * nmb;
+    da.cbp = d_cbp + lvl_off[j] * nmb;
+    da.coef = d_coef + (j % kRing) * ngop * nmb * kCoefPerMb;
+    da.cw = S.cw;
+    da.ch = S.ch;
+    da.mbw = mbw;
+    da.mbh = mbh;
+    da.qp = qp;
+    da.off_a = 2 * dbk_alpha;
+    da.off_b = 2 * dbk_beta;
+    da.count = d_stats + 7;
+    hipLaunchKernelGGL(enc_deblock, dim3(static_cast<unsigned>(ne * mbh)), dim3(64), 0, s1, da);
+  };
   // the level's pictures hashed where the next level reads them: the
   // reconstruction slots, or (level 0 without intra: the IDR pictures are
   // their source) the small store, through entries whose slot is the frame
@@ -1940,6 +2120,7 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
                        S.w, S.h, hb, d_stats + 4);
   };
   if (intra) enqueue_intra(0);
+  if (intra && deblock) enqueue_deblock(0);
   if (hashed) enqueue_hash(0);
   if (intra) HIP_TRY(hipEventRecord(ev[0], s1));
   int64_t next_search = 1;
@@ -1974,6 +2155,7 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
         default: launch_search<0>(R, grid, s1, sa); break;
       }
       if (intra) enqueue_intra(j);
+      if (deblock) enqueue_deblock(j);
       if (hashed) enqueue_hash(j);
       HIP_TRY(hipEventRecord(ev[j], s1));
     }
@@ -2044,8 +2226,16 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
     wa.jobs = d_jobs;
     wa.n_jobs = d_njobs;
     wa.n_slices = ns;
-    if (intra) hipLaunchKernelGGL(enc_write<true>, dim3(static_cast<unsigned>((ns + 63) / 64)), dim3(64), 0, s2, wa);
-    else hipLaunchKernelGGL(enc_write<false>, dim3(static_cast<unsigned>((ns + 63) / 64)), dim3(64), 0, s2, wa);
+    wa.dbk_alpha = dbk_alpha;
+    wa.dbk_beta = dbk_beta;
+    const dim3 wgrid(static_cast<unsigned>((ns + 63) / 64));
+    if (deblock) {
+      if (intra) hipLaunchKernelGGL((enc_write<true, true>), wgrid, dim3(64), 0, s2, wa);
+      else hipLaunchKernelGGL((enc_write<false, true>), wgrid, dim3(64), 0, s2, wa);
+    } else {
+      if (intra) hipLaunchKernelGGL((enc_write<true, false>), wgrid, dim3(64), 0, s2, wa);
+      else hipLaunchKernelGGL((enc_write<false, false>), wgrid, dim3(64), 0, s2, wa);
+    }
     HIP_TRY(hipEventRecord(wev[j0 / kChunkLevels], s2));
     VTS_TRY(enqueue_searches(j1 + kRing));  // the ring slots of this chunk's levels are free once it is written
     hipLaunchKernelGGL(enc_scan, dim3(1), dim3(1024), 0, s2, d_sizes, ns, d_went + e0, mbh, d_offs, d_total,
@@ -2094,7 +2284,7 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   }
   VTS_TRY(status);
   uint32_t err = 0;
-  unsigned long long st[7] = {0, 0, 0, 0, 0, 0, 0};
+  unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   HIP_TRY(hipMemcpy(&err, d_err, sizeof err, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost));
   if (err) return fail(VTS_E_CAPACITY, "a slice exceeded its %lld-byte staging slot", static_cast<long long>(cap));
@@ -2134,6 +2324,8 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   if (xinfo) {
     if (xinfo->struct_size >= 16) xinfo->subpel_mbs = subpel ? static_cast<int64_t>(st[5] + st[6]) : 0;
     if (xinfo->struct_size >= 24) xinfo->qpel_mbs = subpel ? static_cast<int64_t>(st[6]) : 0;
+    if (xinfo->struct_size >= 32)
+      reinterpret_cast<vts_transcode_ext_info2 *>(xinfo)->deblock_mbs = deblock ? static_cast<int64_t>(st[7]) : 0;
   }
   return VTS_OK;
 }

@@ -134,6 +134,18 @@ class TranscodeExtInfo(C.Structure):
                 ("subpel_mbs", C.c_int64), ("qpel_mbs", C.c_int64)]
 
 
+class TranscodeExt2(C.Structure):
+    """vts_transcode_ext2: begins with TranscodeExt; passed to
+    vts_transcode_ex by pointer cast with base.struct_size = sizeof(TranscodeExt2)."""
+    _fields_ = [("base", TranscodeExt), ("deblock", C.c_int32), ("deblock_alpha", C.c_int32),
+                ("deblock_beta", C.c_int32), ("_pad", C.c_int32)]
+
+
+class TranscodeExtInfo2(C.Structure):
+    """vts_transcode_ext_info2: begins with TranscodeExtInfo; as TranscodeExt2."""
+    _fields_ = [("base", TranscodeExtInfo), ("deblock_mbs", C.c_int64)]
+
+
 class ManifestArgs(C.Structure):
     _fields_ = [("video_id", C.c_char_p), ("segment_dir", C.c_char_p),
                 ("created_at", C.c_char_p), ("duration", C.c_double),

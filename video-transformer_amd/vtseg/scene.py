@@ -262,7 +262,8 @@ class VideoScorer:
     def transcode(self, out_path: str | Path, *, height: int = 360, search_range: int = 8,
                   max_mb_sad: int = 1536, keyint: int = 250, idr_at_cuts: bool = False,
                   cut_threshold: float = 0.0, qp: int = 28, intra: bool = False,
-                  subpel: int = 0) -> dict:
+                  subpel: int = 0, deblock: bool = False,
+                  deblock_offsets: tuple[int, int] = (0, 0)) -> dict:
         """360p upload transcode of this video into `out_path`
         (vts_transcode_ex): decode + score + area downscale +
         device H.264 encode with a quantised residual at `qp` (<= 0: none, the
@@ -271,7 +272,11 @@ class VideoScorer:
         that is cheaper than I_PCM; needs `qp` > 0.  `subpel`: the motion
         vector of every P macroblock is refined around the integer winner to
         half samples (1) or half then quarter samples (2); 0 is the integer
-        encoder, byte for byte.  Returns the facts (with `intra` or `subpel`
+        encoder, byte for byte.  `deblock`: the in-loop deblocking filter,
+        inside each macroblock row's slice (disable_deblocking_filter_idc 2),
+        with `deblock_offsets` = (slice_alpha_c0_offset_div2,
+        slice_beta_offset_div2), each -6..6; needs `qp` > 0; off, every byte
+        is as before.  Returns the facts (with `intra`, `subpel` or `deblock`
         also the encoder's `recon_hash`) and per-stage milliseconds."""
         prm = _lib.TranscodeParams()
         prm.height = height
@@ -283,14 +288,19 @@ class VideoScorer:
         prm.qp = qp if qp > 0 else -1
         prm.intra = 1 if intra else 0
         info = _lib.TranscodeInfo()
-        ext = _lib.TranscodeExt(C.sizeof(_lib.TranscodeExt), subpel)
-        xinfo = _lib.TranscodeExtInfo(C.sizeof(_lib.TranscodeExtInfo))
+        ext = _lib.TranscodeExt2(_lib.TranscodeExt(C.sizeof(_lib.TranscodeExt2), subpel),
+                                 1 if deblock else 0, int(deblock_offsets[0]), int(deblock_offsets[1]))
+        xinfo2 = _lib.TranscodeExtInfo2(_lib.TranscodeExtInfo(C.sizeof(_lib.TranscodeExtInfo2)))
+        xinfo = xinfo2.base
         _lib.check(self._lib.vts_transcode_ex(self._ctx, str(out_path).encode(), C.byref(prm),
-                                              C.byref(ext), C.byref(info), C.byref(xinfo)))
+                                              C.cast(C.pointer(ext), C.POINTER(_lib.TranscodeExt)),
+                                              C.byref(info),
+                                              C.cast(C.pointer(xinfo2), C.POINTER(_lib.TranscodeExtInfo))))
         return {"width": info.width, "height": info.height, "n_frames": info.n_frames,
                 "n_idr": info.n_idr, "pcm_mbs": info.pcm_mbs, "inter_mbs": info.inter_mbs,
                 "skip_mbs": info.skip_mbs, "intra_mbs": info.intra_mbs,
                 "subpel_mbs": xinfo.subpel_mbs, "qpel_mbs": xinfo.qpel_mbs,
+                "deblock_mbs": xinfo2.deblock_mbs,
                 "recon_hash": int(info.recon_hash), "bytes_written": info.bytes_written,
                 "decode_ms": info.ms[0], "search_ms": info.ms[1], "write_ms": info.ms[2],
                 "mux_ms": info.ms[3]}

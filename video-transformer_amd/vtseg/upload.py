@@ -53,13 +53,15 @@ def _ffmpeg(video_path: Path, out: Path, logger: logging.Logger) -> Path:
 
 def compress_video_for_upload(video_path: Path, *, logger: logging.Logger | None = None,
                               device: int = 0, max_size_mb: float = MAX_SIZE_MB,
-                              intra: bool = False, subpel: int = 0) -> Path:
+                              intra: bool = False, subpel: int = 0, deblock: bool = False,
+                              deblock_offsets: tuple[int, int] = (0, 0)) -> Path:
     """Same decisions and return values as the reference method: the input
     path when it is <= 30 MB, an existing non-empty compressed_<name> as is,
     otherwise the new compressed file, or the input path when compression
-    is impossible.  `intra` and `subpel` are VideoScorer.transcode's:
-    Intra16x16 instead of I_PCM intra macroblocks, and half- (1) or quarter-
-    sample (2) motion refinement."""
+    is impossible.  `intra`, `subpel`, `deblock` and `deblock_offsets` are
+    VideoScorer.transcode's: Intra16x16 instead of I_PCM intra macroblocks,
+    half- (1) or quarter-sample (2) motion refinement, and the in-loop
+    deblocking filter with its two slice offsets."""
     log = logger or logging.getLogger(__name__)
     video_path = Path(video_path)
     file_size_mb = video_path.stat().st_size / (1024 * 1024)
@@ -76,7 +78,8 @@ def compress_video_for_upload(video_path: Path, *, logger: logging.Logger | None
         from . import _lib
         from .scene import VideoScorer
         with VideoScorer(video_path, device=device) as v:
-            facts = v.transcode(video_only, intra=intra, subpel=subpel)
+            facts = v.transcode(video_only, intra=intra, subpel=subpel, deblock=deblock,
+                                deblock_offsets=deblock_offsets)
         # the source's audio / other tracks, stream-copied beside the new video
         _lib.check(_lib.lib().vts_add_tracks(str(video_only).encode(),
                                              str(video_path).encode(), str(out).encode()))
