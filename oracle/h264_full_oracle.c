@@ -290,24 +290,6 @@ static const int NORM_V[6][3] = {{10, 16, 13}, {11, 18, 14}, {13, 20, 16},
 /* Table 8-15: QPc for qPI >= 30 */
 static const int QPC_TAB[22] = {29, 30, 31, 32, 32, 33, 34, 34, 35, 35, 36,
                                 36, 37, 37, 37, 38, 38, 38, 39, 39, 39, 39};
-/* Table 8-16 / 8-17 */
-static const int ALPHA[52] = {0,  0,  0,  0,  0,  0,  0,  0,   0,   0,   0,   0,   0,
-                              0,  0,  0,  4,  4,  5,  6,  7,   8,   9,   10,  12,  13,
-                              15, 17, 20, 22, 25, 28, 32, 36,  40,  45,  50,  56,  63,
-                              71, 80, 90, 101, 113, 127, 144, 162, 182, 203, 226, 255, 255};
-static const int BETA[52] = {0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  2,  2,
-                             2,  3,  3,  3,  3,  4,  4,  4,  6,  6,  7,  7,  8,  8,  9,  9,  10, 10,
-                             11, 11, 12, 12, 13, 13, 14, 14, 15, 15, 16, 16, 17, 17, 18, 18};
-static const int TC0[52][3] = {
-  {0, 0, 0},   {0, 0, 0},   {0, 0, 0},   {0, 0, 0},  {0, 0, 0},  {0, 0, 0},  {0, 0, 0},
-  {0, 0, 0},   {0, 0, 0},   {0, 0, 0},   {0, 0, 0},  {0, 0, 0},  {0, 0, 0},  {0, 0, 0},
-  {0, 0, 0},   {0, 0, 0},   {0, 0, 0},   {0, 0, 1},  {0, 0, 1},  {0, 0, 1},  {0, 0, 1},
-  {0, 1, 1},   {0, 1, 1},   {1, 1, 1},   {1, 1, 1},  {1, 1, 1},  {1, 1, 1},  {1, 1, 2},
-  {1, 1, 2},   {1, 1, 2},   {1, 1, 2},   {1, 2, 3},  {1, 2, 3},  {2, 2, 3},  {2, 2, 4},
-  {2, 3, 4},   {2, 3, 4},   {3, 3, 5},   {3, 4, 6},  {3, 4, 6},  {4, 5, 7},  {4, 5, 8},
-  {4, 6, 9},   {5, 7, 10},  {6, 8, 11},  {6, 8, 13}, {7, 10, 14}, {8, 11, 16}, {9, 12, 18},
-  {10, 13, 20}, {11, 15, 23}, {13, 17, 25}};
-
 /* luma4x4BlkIdx -> (x, y) in 4x4 block units (6.4.3) */
 static const int BLK_X[16] = {0, 1, 0, 1, 2, 3, 2, 3, 0, 1, 0, 1, 2, 3, 2, 3};
 static const int BLK_Y[16] = {0, 0, 1, 1, 0, 0, 1, 1, 2, 2, 3, 3, 2, 2, 3, 3};
@@ -1072,7 +1054,7 @@ static void filter_line(uint8_t *s, int step, int bS, int chroma, int indexA, in
   if (!(bS > 0 && iabs(p0 - q0) < alpha && iabs(p1 - p0) < beta && iabs(q1 - q0) < beta)) return;
   int p2 = chroma ? 0 : s[-3 * step], q2 = chroma ? 0 : s[2 * step];
   if (bS < 4) {
-    int tc0 = TC0[indexA][bS - 1];
+    int tc0 = FO_TC0[indexA][bS - 1];
     int ap = iabs(p2 - p0), aq = iabs(q2 - q0);
     int tc = chroma ? tc0 + 1 : tc0 + (ap < beta) + (aq < beta);
     int delta = clip3(-tc, tc, (((q0 - p0) << 2) + (p1 - q1) + 4) >> 3);
@@ -1134,7 +1116,7 @@ static void deblock_picture(fo_dec *d, fo_pic *pic) {
             int xp = dir ? xq : (xq + 15) % 16, yp = dir ? (yq + 15) % 16 : yq;
             int bS = bs_of(p, (yp / 4) * 4 + xp / 4, q, (yq / 4) * 4 + xq / 4, e == 0);
             uint8_t *s = pic->y + (int64_t)(my * 16 + yq) * d->W + mx * 16 + xq;
-            filter_line(s, dir ? d->W : 1, bS, 0, iA, ALPHA[iA], BETA[iB]);
+            filter_line(s, dir ? d->W : 1, bS, 0, iA, FO_ALPHA[iA], FO_BETA[iB]);
           }
         }
         /* chroma: edges 0 and 2 (chroma sample 0 and 4) */
@@ -1151,7 +1133,7 @@ static void deblock_picture(fo_dec *d, fo_pic *pic) {
               int bS = bs_of(p, (yp / 4) * 4 + xp / 4, q, (yq / 4) * 4 + xq / 4, e == 0);
               int cx = dir ? k : 2 * e, cy = dir ? 2 * e : k;
               uint8_t *s = img + (int64_t)(my * 8 + cy) * (d->W / 2) + mx * 8 + cx;
-              filter_line(s, dir ? d->W / 2 : 1, bS, 1, iA, ALPHA[iA], BETA[iB]);
+              filter_line(s, dir ? d->W / 2 : 1, bS, 1, iA, FO_ALPHA[iA], FO_BETA[iB]);
             }
           }
         }

@@ -84,6 +84,11 @@ def lib() -> C.CDLL:
                                       C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.or_transcode_ex.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -372,13 +377,19 @@ def sps_pps(mbw: int, mbh: int, crop_r: int, crop_b: int, fps: float) -> tuple[b
 def transcode(frames: np.ndarray, width: int, height: int, scores: np.ndarray, *,
               threshold: float = 0.08, out_height: int = 360, search_range: int = 8,
               max_mb_sad: int = 1536, keyint: int = 250, idr_at_cuts: bool = False,
-              want_recon: bool = False, qp: int = 28) -> dict:
+              want_recon: bool = False, qp: int = 28, intra: bool = False, subpel: int = 0,
+              deblock: bool = False, deblock_offsets: tuple[int, int] = (0, 0)) -> dict:
     """The upload transcode of display-size NV12 frames [F, H*3/2, W] with
     their scene scores: output samples (bytes), per-frame sizes / sync flags,
     SPS/PPS, stats and (optionally) the encoder's reconstruction.  qp >= 1:
     P macroblocks carry a quantised residual at that QP (I_PCM only where the
     residual would cost more); qp <= 0: the round-2 encoder (no residual,
-    I_PCM where the prediction misses by more than max_mb_sad)."""
+    I_PCM where the prediction misses by more than max_mb_sad).  `intra`,
+    `subpel` (0, 1, 2), `deblock` and `deblock_offsets` are the device
+    encoder's opt-in paths of the same names; with them the
+    reconstruction is the filtered one, and the result also counts
+    `intra_mbs`, `subpel_mbs`, `qpel_mbs` and `deblock_mbs` as the device's
+    facts do.  All off: or_transcode's bytes."""
     F = frames.shape[0]
     sw = small_width(width, height, out_height)
     cw, ch = (sw + 15) & ~15, (out_height + 15) & ~15
@@ -391,21 +402,26 @@ def transcode(frames: np.ndarray, width: int, height: int, scores: np.ndarray, *
     size = np.zeros(F, np.int64)
     sync = np.zeros(F, np.uint8)
     recon = np.zeros((F, ch * 3 // 2, cw), np.uint8) if want_recon else None
-    stats = np.zeros(4, np.int64)
+    stats = np.zeros(8, np.int64)
     n = C.c_int64(0)
-    rc = lib().or_transcode(fr.ctypes.data, F, width, height, sc.ctypes.data, threshold,
-                            int(idr_at_cuts), out_height, search_range, max_mb_sad, keyint, int(qp),
-                            out.ctypes.data, cap,
-                            off.ctypes.data, size.ctypes.data, sync.ctypes.data,
-                            recon.ctypes.data if recon is not None else None,
-                            stats.ctypes.data, C.byref(n))
+    tail = (out.ctypes.data, cap, off.ctypes.data, size.ctypes.data, sync.ctypes.data,
+            recon.ctypes.data if recon is not None else None, stats.ctypes.data, C.byref(n))
+    if intra or subpel or deblock or tuple(deblock_offsets) != (0, 0):
+        rc = lib().or_transcode_ex(fr.ctypes.data, F, width, height, sc.ctypes.data, threshold,
+                                   int(idr_at_cuts), out_height, search_range, max_mb_sad, keyint, int(qp),
+                                   int(bool(intra)), int(subpel), int(bool(deblock)),
+                                   int(deblock_offsets[0]), int(deblock_offsets[1]), *tail)
+    else:
+        rc = lib().or_transcode(fr.ctypes.data, F, width, height, sc.ctypes.data, threshold,
+                                int(idr_at_cuts), out_height, search_range, max_mb_sad, keyint, int(qp), *tail)
     if rc != 0:
         raise RuntimeError(f"oracle transcode rc={rc}")
     samples = [bytes(out[off[i]:off[i] + size[i]]) for i in range(F)]
     return {"width": sw, "height": out_height, "coded_width": cw, "coded_height": ch,
             "samples": samples, "sync": sync.astype(bool), "recon": recon,
             "pcm_mbs": int(stats[0]), "inter_mbs": int(stats[1]), "skip_mbs": int(stats[2]),
-            "n_idr": int(stats[3])}
+            "n_idr": int(stats[3]), "intra_mbs": int(stats[4]), "subpel_mbs": int(stats[5]),
+            "qpel_mbs": int(stats[6]), "deblock_mbs": int(stats[7])}
 
 
 def decode_samples(sps: bytes, pps: bytes, samples: list[bytes], nal_length_size: int = 4):

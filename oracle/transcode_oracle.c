@@ -45,10 +45,31 @@
  *     its motion is (0, 0) and nothing is coded.  cbp, mb_qp_delta 0 and
  *     residual_block_cavlc with nC from the left macroblock (the one above is
  *     another slice) as 7.3.5.3 / 9.2.1 write them.
+ *
+ * The three opt-in paths (or_transcode_ex; DESIGN.md §11, "The rules the byte
+ * oracle restates"), all off by default and then absent from every byte:
+ *   - subpel 1 / 2: around the integer winner the eight half-sample
+ *     neighbours, then (2) around that winner the eight quarter-sample ones;
+ *     every candidate's prediction per sample straight from 8.4.2.2.1 and Table
+ *     8-12 (luma_frac: the integer sample and each of the 15 fractional
+ *     positions by its own formula, clamped source coordinates; no shared
+ *     planes), cost = luma SAD, key (SAD, index) with the centre index 0;
+ *   - intra: the IDR picture's macroblocks, and the P macroblocks the search
+ *     left as I_PCM, as Intra16x16 (Horizontal or DC from the left macroblock
+ *     of the row's slice, by SAD) where its exact bits are <= 3072;
+ *   - deblock: clause 8.7 with disable_deblocking_filter_idc 2 on every
+ *     picture's reconstruction before the next picture predicts from it
+ *     (deblock_picture, written here; Tables 8-16 / 8-17 from
+ *     h264_std_tables.h).
+ * tests/test_transcode_oracle.py closes each of them through the general
+ * oracle decoder (h264_full_oracle.c, which has its own 8.3.3, 8.4.2.2.1 and
+ * 8.7); tests/test_transcode_bytes_gpu.py holds the device to these bytes.
  */
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include "h264_std_tables.h" /* Tables 8-16 / 8-17 (the deblocking filter) */
 
 /* ------------------------------------------------------------ sizes */
 
@@ -243,9 +264,12 @@ static const int CBP_P[48] = {0,  16, 1,  2,  4,  8,  32, 3,  5,  10, 12, 15, 47
 
 typedef struct {
   int pcm, mvx, mvy;  /* mv in quarter-pel */
-  int cbp;            /* coded_block_pattern of an inter macroblock */
+  int cbp;            /* coded_block_pattern of an inter or Intra16x16 macroblock */
+  int i16;            /* Intra16x16 (pcm = 0, no motion) */
+  int lmode, cmode;   /* Intra16x16PredMode, intra_chroma_pred_mode */
   int16_t lv[384];    /* levels in scan order: luma by luma4x4BlkIdx (16 x 16), Cb / Cr DC (2 x 4),
-                         Cb / Cr AC by chroma4x4BlkIdx (8 x 15) */
+                         Cb / Cr AC by chroma4x4BlkIdx (8 x 15); Intra16x16: Intra16x16DCLevel in
+                         [0, 16), Intra16x16ACLevel of block k in [16 + 15 k, 31 + 15 k) */
 } or_mb;
 
 /* ------------------------------------------------------ residual coding */
@@ -477,17 +501,78 @@ static int residual_mb(const uint8_t *sy, const uint8_t *su, const uint8_t *sv, 
   return bound;
 }
 
-/* prediction of one macroblock from ref (coded NV12 cw x ch), integer luma
- * motion (dx, dy); chroma 8.4.2.2.2 with edge clamping */
-static void predict_mb(const uint8_t *ref, int cw, int ch, int mx, int my, int dx, int dy,
-                       uint8_t *py, uint8_t *pu, uint8_t *pv) {
+/* ---- 8.4.2.2.1, one luma sample at a time.  L: the reference sample at
+ * (x, y), clamped into the picture (8-239 / 8-240). */
+static int ref_l(const uint8_t *ref, int cw, int ch, int x, int y) {
+  return ref[(int64_t)clampi(y, 0, ch - 1) * cw + clampi(x, 0, cw - 1)];
+}
+static int tap6i(int a, int b, int c, int d, int e, int f) { return a - 5 * b + 20 * c + 20 * d - 5 * e + f; }
+static int clip255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+/* b1 (8-241): the horizontal intermediate between (x, y) and (x + 1, y) */
+static int hz1(const uint8_t *r, int cw, int ch, int x, int y) {
+  return tap6i(ref_l(r, cw, ch, x - 2, y), ref_l(r, cw, ch, x - 1, y), ref_l(r, cw, ch, x, y),
+               ref_l(r, cw, ch, x + 1, y), ref_l(r, cw, ch, x + 2, y), ref_l(r, cw, ch, x + 3, y));
+}
+/* h1 (8-242): the vertical intermediate between (x, y) and (x, y + 1) */
+static int vt1(const uint8_t *r, int cw, int ch, int x, int y) {
+  return tap6i(ref_l(r, cw, ch, x, y - 2), ref_l(r, cw, ch, x, y - 1), ref_l(r, cw, ch, x, y),
+               ref_l(r, cw, ch, x, y + 1), ref_l(r, cw, ch, x, y + 2), ref_l(r, cw, ch, x, y + 3));
+}
+static int half_b(const uint8_t *r, int cw, int ch, int x, int y) { return clip255((hz1(r, cw, ch, x, y) + 16) >> 5); }
+static int half_h(const uint8_t *r, int cw, int ch, int x, int y) { return clip255((vt1(r, cw, ch, x, y) + 16) >> 5); }
+/* j (8-245 / 8-246): the six horizontal intermediates of rows y - 2 .. y + 3 */
+static int half_j(const uint8_t *r, int cw, int ch, int x, int y) {
+  int j1 = tap6i(hz1(r, cw, ch, x, y - 2), hz1(r, cw, ch, x, y - 1), hz1(r, cw, ch, x, y),
+                 hz1(r, cw, ch, x, y + 1), hz1(r, cw, ch, x, y + 2), hz1(r, cw, ch, x, y + 3));
+  return clip255((j1 + 512) >> 10);
+}
+/* The predicted luma sample for full-sample location (x, y) and fraction
+ * (xf, yf), Table 8-12 with Figure 8-4's names: G (x, y), H (x + 1, y), M
+ * (x, y + 1); b, s the horizontal half samples of rows y, y + 1; h, m the
+ * vertical ones of columns x, x + 1; j the centre. */
+static int luma_frac(const uint8_t *r, int cw, int ch, int x, int y, int xf, int yf) {
+  int G = ref_l(r, cw, ch, x, y), H = ref_l(r, cw, ch, x + 1, y), M = ref_l(r, cw, ch, x, y + 1);
+  switch (4 * xf + yf) {
+    case 0: return G;
+    case 1: return (G + half_h(r, cw, ch, x, y) + 1) >> 1;                                 /* d */
+    case 2: return half_h(r, cw, ch, x, y);                                                /* h */
+    case 3: return (M + half_h(r, cw, ch, x, y) + 1) >> 1;                                 /* n */
+    case 4: return (G + half_b(r, cw, ch, x, y) + 1) >> 1;                                 /* a */
+    case 5: return (half_b(r, cw, ch, x, y) + half_h(r, cw, ch, x, y) + 1) >> 1;           /* e */
+    case 6: return (half_h(r, cw, ch, x, y) + half_j(r, cw, ch, x, y) + 1) >> 1;           /* i */
+    case 7: return (half_h(r, cw, ch, x, y) + half_b(r, cw, ch, x, y + 1) + 1) >> 1;       /* p = (h + s) */
+    case 8: return half_b(r, cw, ch, x, y);                                                /* b */
+    case 9: return (half_b(r, cw, ch, x, y) + half_j(r, cw, ch, x, y) + 1) >> 1;           /* f */
+    case 10: return half_j(r, cw, ch, x, y);                                               /* j */
+    case 11: return (half_j(r, cw, ch, x, y) + half_b(r, cw, ch, x, y + 1) + 1) >> 1;      /* q = (j + s) */
+    case 12: return (H + half_b(r, cw, ch, x, y) + 1) >> 1;                                /* c */
+    case 13: return (half_b(r, cw, ch, x, y) + half_h(r, cw, ch, x + 1, y) + 1) >> 1;      /* g = (b + m) */
+    case 14: return (half_j(r, cw, ch, x, y) + half_h(r, cw, ch, x + 1, y) + 1) >> 1;      /* k = (j + m) */
+    default: return (half_h(r, cw, ch, x + 1, y) + half_b(r, cw, ch, x, y + 1) + 1) >> 1;  /* r = (m + s) */
+  }
+}
+/* luma prediction of macroblock (mx, my) at the quarter-sample vector (mvx, mvy) */
+static void predict_luma(const uint8_t *ref, int cw, int ch, int mx, int my, int mvx, int mvy, uint8_t *py) {
   for (int j = 0; j < 16; j++)
-    for (int i = 0; i < 16; i++) {
-      int sx = clampi(mx * 16 + i + dx, 0, cw - 1), sy = clampi(my * 16 + j + dy, 0, ch - 1);
-      py[j * 16 + i] = ref[(int64_t)sy * cw + sx];
-    }
+    for (int i = 0; i < 16; i++)
+      py[j * 16 + i] = (uint8_t)luma_frac(ref, cw, ch, mx * 16 + i + (mvx >> 2), my * 16 + j + (mvy >> 2),
+                                          mvx & 3, mvy & 3);
+}
+static int64_t luma_sad(const uint8_t *src, int cw, int mx, int my, const uint8_t *py) {
+  int64_t s = 0;
+  for (int j = 0; j < 16; j++)
+    for (int i = 0; i < 16; i++) s += abs((int)py[j * 16 + i] - (int)src[(int64_t)(my * 16 + j) * cw + mx * 16 + i]);
+  return s;
+}
+
+/* prediction of one macroblock from ref (coded NV12 cw x ch) at the
+ * quarter-sample luma vector (mvx, mvy): luma 8.4.2.2.1 (an integer vector
+ * reads the clamped sample itself), chroma 8.4.2.2.2 with edge clamping */
+static void predict_mb(const uint8_t *ref, int cw, int ch, int mx, int my, int mvx, int mvy,
+                       uint8_t *py, uint8_t *pu, uint8_t *pv) {
+  predict_luma(ref, cw, ch, mx, my, mvx, mvy, py);
   const uint8_t *uv = ref + (int64_t)cw * ch;
-  int mvx = 4 * dx, mvy = 4 * dy, fx = mvx & 7, fy = mvy & 7, ccw = cw / 2, cch = ch / 2;
+  int fx = mvx & 7, fy = mvy & 7, ccw = cw / 2, cch = ch / 2;
   for (int j = 0; j < 8; j++)
     for (int i = 0; i < 8; i++) {
       int xi = mx * 8 + i + (mvx >> 3), yi = my * 8 + j + (mvy >> 3);
@@ -504,11 +589,15 @@ static void predict_mb(const uint8_t *ref, int cw, int ch, int mx, int my, int d
 
 /* encode one P picture's decisions and reconstruction (qp >= 1: residual coding) */
 static void encode_p(const uint8_t *src, const uint8_t *ref, uint8_t *rec, int cw, int ch, int R,
-                     int T, int qp, or_mb *mbs) {
+                     int T, int qp, int subpel, or_mb *mbs, int64_t *stats) {
   int mbw = cw / 16, mbh = ch / 16;
   const uint8_t *suv = src + (int64_t)cw * ch;
   uint8_t *ruv = rec + (int64_t)cw * ch;
   int side = 2 * R + 1, ncand = side * side, center = R * side + R;
+  int64_t n_frac = 0, n_quarter = 0;
+  /* the macroblocks of a P picture are independent of each other (each reads
+   * the previous picture): threads only shorten the checker's run */
+#pragma omp parallel for collapse(2) schedule(dynamic, 4) reduction(+ : n_frac, n_quarter)
   for (int my = 0; my < mbh; my++)
     for (int mx = 0; mx < mbw; mx++) {
       int64_t best = -1;
@@ -525,7 +614,23 @@ static void encode_p(const uint8_t *src, const uint8_t *ref, uint8_t *rec, int c
         if (best < 0 || s < best) { best = s; bdx = dx; bdy = dy; }
       }
       uint8_t py[256], pu[64], pv[64];
-      predict_mb(ref, cw, ch, mx, my, bdx, bdy, py, pu, pv);
+      /* sub-sample refinement: around the
+       * integer winner in steps of 2, then (subpel == 2) around that winner in
+       * steps of 1; key (SAD, index), the centre index 0, the other eight 1..8
+       * in raster order of (j, i); the least key wins */
+      int wmvx = 4 * bdx, wmvy = 4 * bdy;
+      int64_t wsad = best;
+      for (int step = 2; subpel >= 1 && step >= (subpel == 2 ? 1 : 2); step >>= 1) {
+        int cx = wmvx, cy = wmvy;  /* the centre keeps its SAD and wins ties; then raster order */
+        for (int j = -1; j <= 1; j++)
+          for (int i = -1; i <= 1; i++) {
+            if (!i && !j) continue;
+            predict_luma(ref, cw, ch, mx, my, cx + step * i, cy + step * j, py);
+            int64_t s = luma_sad(src, cw, mx, my, py);
+            if (s < wsad) { wsad = s; wmvx = cx + step * i; wmvy = cy + step * j; }
+          }
+      }
+      predict_mb(ref, cw, ch, mx, my, wmvx, wmvy, py, pu, pv);
       int64_t cost = 0;
       for (int j = 0; j < 16; j++)
         for (int i = 0; i < 16; i++)
@@ -562,8 +667,13 @@ static void encode_p(const uint8_t *src, const uint8_t *ref, uint8_t *rec, int c
         inter = T >= 0 && cost <= T;
       }
       m->pcm = !inter;
-      m->mvx = inter ? 4 * bdx : 0;
-      m->mvy = inter ? 4 * bdy : 0;
+      m->i16 = 0;
+      m->mvx = inter ? wmvx : 0;
+      m->mvy = inter ? wmvy : 0;
+      if (inter && ((wmvx | wmvy) & 3)) {  /* a fractional vector; one with an odd component */
+        n_frac++;
+        if ((wmvx | wmvy) & 1) n_quarter++;
+      }
       for (int j = 0; j < 16; j++)
         for (int i = 0; i < 16; i++) {
           int64_t o = (int64_t)(my * 16 + j) * cw + mx * 16 + i;
@@ -576,6 +686,8 @@ static void encode_p(const uint8_t *src, const uint8_t *ref, uint8_t *rec, int c
           ruv[o + 1] = inter ? pv[j * 8 + i] : suv[o + 1];
         }
     }
+  stats[5] += n_frac;
+  stats[6] += n_quarter;
 }
 
 /* residual() of an inter macroblock (7.3.5.3) with nC from the left
@@ -624,10 +736,387 @@ static void put_pcm(or_bw *b, const uint8_t *src, int cw, int ch, int mx, int my
       for (int i = 0; i < 8; i++) bw_u(b, 8, uv[(int64_t)(my * 8 + j) * cw + 2 * (mx * 8 + i) + pl]);
 }
 
+/* -------------------------------------------------- Intra16x16 (intra = 1) */
+
+static int nc_of(int na, int nb) {
+  return (na >= 0 && nb >= 0) ? (na + nb + 1) >> 1 : (na >= 0 ? na : (nb >= 0 ? nb : 0));
+}
+
+/* macroblock_layer() of an Intra16x16 macroblock (7.3.5, Table 7-11) without
+ * its mb_skip_run: mb_type (5 more in a P slice), intra_chroma_pred_mode,
+ * mb_qp_delta 0, Intra16x16DCLevel (nC of block 0), the 16 Intra16x16ACLevel
+ * blocks when the luma coded_block_pattern is 15, chroma DC / AC.  lnz / lnzc:
+ * the left macroblock's right column of total_coeff (-1 unavailable); the row
+ * above is another slice.  b == NULL only counts.  Returns the bits; cnz / cnzc
+ * receive this macroblock's total_coeff (an AC block's counts its 15 levels). */
+static int put_intra_mb(or_bw *b, const or_mb *m, int p_slice, const int *lnz, const int (*lnzc)[2], int *cnz,
+                        int (*cnzc)[4]) {
+  or_bw cnt = {NULL, 0, 0, 0, 0};
+  if (!b) b = &cnt;
+  int64_t before = b->n * 8 + b->nb;
+  int cbp = m->cbp;
+  uint32_t mbt = (uint32_t)(1 + m->lmode + 4 * (cbp >> 4) + ((cbp & 15) ? 12 : 0));
+  bw_ue(b, p_slice ? 5 + mbt : mbt);
+  bw_ue(b, (uint32_t)m->cmode);
+  bw_se(b, 0);
+  for (int i = 0; i < 16; i++) cnz[i] = 0;
+  for (int pl = 0; pl < 2; pl++)
+    for (int i = 0; i < 4; i++) cnzc[pl][i] = 0;
+  block_bits(b, m->lv, 16, nc_of(lnz[0], -1));
+  if (cbp & 15)
+    for (int k = 0; k < 16; k++) {
+      int bx = BLK_X[k], by = BLK_Y[k];
+      int na = bx ? cnz[by * 4 + bx - 1] : lnz[by], nb = by ? cnz[(by - 1) * 4 + bx] : -1;
+      const int16_t *lv = m->lv + 16 + 15 * k;
+      block_bits(b, lv, 15, nc_of(na, nb));
+      int tc = 0;
+      for (int i = 0; i < 15; i++) tc += lv[i] != 0;
+      cnz[by * 4 + bx] = tc;
+    }
+  if (cbp >> 4)
+    for (int pl = 0; pl < 2; pl++) block_bits(b, m->lv + 256 + 4 * pl, 4, -1);
+  if ((cbp >> 4) == 2)
+    for (int pl = 0; pl < 2; pl++)
+      for (int k = 0; k < 4; k++) {
+        int bx = k & 1, by = k >> 1;
+        int na = bx ? cnzc[pl][by * 2] : lnzc[pl][by], nb = by ? cnzc[pl][bx] : -1;
+        const int16_t *lv = m->lv + 264 + 60 * pl + 15 * k;
+        block_bits(b, lv, 15, nc_of(na, nb));
+        int tc = 0;
+        for (int i = 0; i < 15; i++) tc += lv[i] != 0;
+        cnzc[pl][k] = tc;
+      }
+  return (int)(b->n * 8 + b->nb - before);
+}
+
+/* total_coeff of a coded macroblock's right column, as the macroblock to its
+ * right reads it for nC (9.2.1): 16 after I_PCM, 0 after P_Skip or an uncoded
+ * 8x8 / chroma AC, else the number of non-zero levels of luma4x4BlkIdx 5, 7,
+ * 13, 15 and chroma4x4BlkIdx 1, 3 */
+static void right_column_nz(const or_mb *m, int *lnz, int (*lnzc)[2]) {
+  static const int RB[4] = {5, 7, 13, 15};
+  for (int i = 0; i < 4; i++) {
+    int k = RB[i], tc = 0;
+    if (m->pcm) tc = 16;
+    else if (m->i16) { if (m->cbp & 15) for (int q = 0; q < 15; q++) tc += m->lv[16 + 15 * k + q] != 0; }
+    else if ((m->cbp >> (k >> 2)) & 1) for (int q = 0; q < 16; q++) tc += m->lv[16 * k + q] != 0;
+    lnz[i] = tc;
+  }
+  for (int pl = 0; pl < 2; pl++)
+    for (int r = 0; r < 2; r++) {
+      int tc = 0;
+      if (m->pcm) tc = 16;
+      else if ((m->cbp >> 4) == 2) for (int q = 0; q < 15; q++) tc += m->lv[264 + 60 * pl + 15 * (1 + 2 * r) + q] != 0;
+      lnzc[pl][r] = tc;
+    }
+}
+
+/* 8.5.10: Intra16x16 luma DC levels c (4x4, raster by block row / column) ->
+ * the scaled DC dcY of each block */
+static void i16_dc_scale(const int *c, int qp, int *dcy) {
+  int t[16], f[16];
+  for (int i = 0; i < 4; i++) {  /* f = A c A, A = [1 1 1 1; 1 1 -1 -1; 1 -1 -1 1; 1 -1 1 -1] */
+    int a0 = c[i * 4], a1 = c[i * 4 + 1], a2 = c[i * 4 + 2], a3 = c[i * 4 + 3];
+    t[i * 4] = a0 + a1 + a2 + a3; t[i * 4 + 1] = a0 + a1 - a2 - a3;
+    t[i * 4 + 2] = a0 - a1 - a2 + a3; t[i * 4 + 3] = a0 - a1 + a2 - a3;
+  }
+  for (int j = 0; j < 4; j++) {
+    int a0 = t[j], a1 = t[4 + j], a2 = t[8 + j], a3 = t[12 + j];
+    f[j] = a0 + a1 + a2 + a3; f[4 + j] = a0 + a1 - a2 - a3;
+    f[8 + j] = a0 - a1 - a2 + a3; f[12 + j] = a0 - a1 + a2 - a3;
+  }
+  int ls = 16 * NV[qp % 6][0];
+  for (int k = 0; k < 16; k++)
+    dcy[k] = qp >= 36 ? (f[k] * ls) << (qp / 6 - 6) : (f[k] * ls + (1 << (5 - qp / 6))) >> (6 - qp / 6);
+}
+
+/* Try macroblock (mx, my) as Intra16x16 (the Intra16x16 rules):
+ * prediction from the left macroblock's right column of this picture's
+ * unfiltered reconstruction rec (the row above is another slice); returns 1 and
+ * writes the reconstruction and m when its exact bits are <= 3072, else 0 (the
+ * macroblock is I_PCM: rec holds the source).  lnz / lnzc as put_intra_mb's. */
+static int encode_intra_mb(const uint8_t *src, uint8_t *rec, int cw, int ch, int mx, int my, int qp, int p_slice,
+                           const int *lnz, const int (*lnzc)[2], or_mb *m) {
+  const uint8_t *suv = src + (int64_t)cw * ch;
+  uint8_t *ruv = rec + (int64_t)cw * ch;
+  int py[16], pc[2][8];  /* both modes are constant along a row: the prediction of each row */
+  int lmode = 2, cmode = 0;  /* no neighbour: DC (128) for luma and chroma */
+  for (int j = 0; j < 16; j++) py[j] = 128;
+  for (int pl = 0; pl < 2; pl++)
+    for (int j = 0; j < 8; j++) pc[pl][j] = 128;
+  if (mx > 0) {
+    int ly[16], lc[2][8], sum = 0;
+    for (int j = 0; j < 16; j++) {
+      ly[j] = rec[(int64_t)(my * 16 + j) * cw + mx * 16 - 1];
+      sum += ly[j];
+    }
+    int dcy = (sum + 8) >> 4;  /* 8.3.3.3, only the left samples available */
+    int dcc[2][8];
+    for (int pl = 0; pl < 2; pl++) {
+      for (int j = 0; j < 8; j++) lc[pl][j] = ruv[(int64_t)(my * 8 + j) * cw + 2 * (mx * 8 - 1) + pl];
+      for (int half = 0; half < 2; half++) {  /* 8.3.4.1-3 without the row above: each 4x4 block's own rows */
+        int s4 = lc[pl][4 * half] + lc[pl][4 * half + 1] + lc[pl][4 * half + 2] + lc[pl][4 * half + 3];
+        for (int j = 0; j < 4; j++) dcc[pl][4 * half + j] = (s4 + 2) >> 2;
+      }
+    }
+    int64_t sad_h = 0, sad_dc = 0, csad_dc = 0, csad_h = 0;
+    for (int j = 0; j < 16; j++)
+      for (int i = 0; i < 16; i++) {
+        int sv = src[(int64_t)(my * 16 + j) * cw + mx * 16 + i];
+        sad_h += abs(sv - ly[j]);
+        sad_dc += abs(sv - dcy);
+      }
+    for (int pl = 0; pl < 2; pl++)
+      for (int j = 0; j < 8; j++)
+        for (int i = 0; i < 8; i++) {
+          int sv = suv[(int64_t)(my * 8 + j) * cw + 2 * (mx * 8 + i) + pl];
+          csad_dc += abs(sv - dcc[pl][j]);
+          csad_h += abs(sv - lc[pl][j]);
+        }
+    /* the least SAD; a tie goes to the lower mode number (luma: Horizontal 1
+     * before DC 2; chroma: DC 0 before Horizontal 1) */
+    lmode = sad_h <= sad_dc ? 1 : 2;
+    cmode = csad_dc <= csad_h ? 0 : 1;
+    for (int j = 0; j < 16; j++) py[j] = lmode == 1 ? ly[j] : dcy;
+    for (int pl = 0; pl < 2; pl++)
+      for (int j = 0; j < 8; j++) pc[pl][j] = cmode == 1 ? lc[pl][j] : dcc[pl][j];
+  }
+  or_mb t;
+  memset(&t, 0, sizeof t);
+  t.i16 = 1;
+  t.lmode = lmode;
+  t.cmode = cmode;
+  int qbits = 15 + qp / 6;
+  int64_t f = ((int64_t)1 << qbits) / 6;
+  /* luma: AC levels of each block at (qbits, f); the 16 DC terms through the
+   * 4x4 Hadamard, halved with (x + 1) >> 1 (arithmetic), then at (qbits + 1, 2f) */
+  int zac[16][16], dcw[16], acnz = 0;
+  for (int k = 0; k < 16; k++) {
+    int bx = BLK_X[k] * 4, by = BLK_Y[k] * 4, x[16], w[16];
+    for (int i = 0; i < 4; i++)
+      for (int j = 0; j < 4; j++) x[i * 4 + j] = src[(int64_t)(my * 16 + by + i) * cw + mx * 16 + bx + j] - py[by + i];
+    fwd4(x, w);
+    dcw[BLK_Y[k] * 4 + BLK_X[k]] = w[0];
+    zac[k][0] = 0;
+    for (int q = 1; q < 16; q++) {
+      zac[k][q] = quant1(w[q], MF[qp % 6][pos_class(q >> 2, q & 3)], qbits, f);
+      acnz |= zac[k][q] != 0;
+    }
+    for (int s = 1; s < 16; s++) t.lv[16 + 15 * k + s - 1] = (int16_t)zac[k][ZZ[s]];
+  }
+  int hd[16], tt[16], dcl[16], dcy_s[16];
+  for (int i = 0; i < 4; i++) {
+    int a0 = dcw[i * 4], a1 = dcw[i * 4 + 1], a2 = dcw[i * 4 + 2], a3 = dcw[i * 4 + 3];
+    tt[i * 4] = a0 + a1 + a2 + a3; tt[i * 4 + 1] = a0 + a1 - a2 - a3;
+    tt[i * 4 + 2] = a0 - a1 - a2 + a3; tt[i * 4 + 3] = a0 - a1 + a2 - a3;
+  }
+  for (int j = 0; j < 4; j++) {
+    int a0 = tt[j], a1 = tt[4 + j], a2 = tt[8 + j], a3 = tt[12 + j];
+    hd[j] = a0 + a1 + a2 + a3; hd[4 + j] = a0 + a1 - a2 - a3;
+    hd[8 + j] = a0 - a1 - a2 + a3; hd[12 + j] = a0 - a1 + a2 - a3;
+  }
+  for (int k = 0; k < 16; k++) {
+    int half = hd[k] >= 0 ? (hd[k] + 1) / 2 : -((-hd[k]) / 2);  /* floor((x + 1) / 2) */
+    dcl[k] = quant1(half, MF[qp % 6][0], qbits + 1, 2 * f);
+  }
+  for (int s = 0; s < 16; s++) t.lv[s] = (int16_t)dcl[ZZ[s]];
+  i16_dc_scale(dcl, qp, dcy_s);
+  /* chroma: as an inter macroblock's (residual_mb) against the intra prediction */
+  int qpc = QPC[qp], cqb = 15 + qpc / 6;
+  int64_t cf = ((int64_t)1 << cqb) / 6;
+  int cacnz = 0, cdcnz = 0, cz[2][4][16], cdl[2][4];
+  for (int pl = 0; pl < 2; pl++) {
+    int wdc[4];
+    for (int k = 0; k < 4; k++) {
+      int bx = (k & 1) * 4, by = (k >> 1) * 4, x[16], w[16];
+      for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++)
+          x[i * 4 + j] = suv[(int64_t)(my * 8 + by + i) * cw + 2 * (mx * 8 + bx + j) + pl] - pc[pl][by + i];
+      fwd4(x, w);
+      wdc[k] = w[0];
+      cz[pl][k][0] = 0;
+      for (int q = 1; q < 16; q++) {
+        cz[pl][k][q] = quant1(w[q], MF[qpc % 6][pos_class(q >> 2, q & 3)], cqb, cf);
+        cacnz |= cz[pl][k][q] != 0;
+      }
+      for (int s = 1; s < 16; s++) t.lv[264 + pl * 60 + k * 15 + s - 1] = (int16_t)cz[pl][k][ZZ[s]];
+    }
+    int fd[4] = {wdc[0] + wdc[1] + wdc[2] + wdc[3], wdc[0] - wdc[1] + wdc[2] - wdc[3],
+                 wdc[0] + wdc[1] - wdc[2] - wdc[3], wdc[0] - wdc[1] - wdc[2] + wdc[3]};
+    for (int k = 0; k < 4; k++) {
+      cdl[pl][k] = quant1(fd[k], MF[qpc % 6][0], cqb + 1, 2 * cf);
+      cdcnz |= cdl[pl][k] != 0;
+      t.lv[256 + 4 * pl + k] = (int16_t)cdl[pl][k];
+    }
+  }
+  /* coded_block_pattern: luma 15 when any AC level of any block is non-zero,
+   * else 0; chroma 2 with a non-zero AC level, else 1 with a non-zero DC level */
+  int cc = cacnz ? 2 : (cdcnz ? 1 : 0);
+  t.cbp = (acnz ? 15 : 0) | (cc << 4);
+  int cnz[16], cnzc[2][4];
+  if (put_intra_mb(NULL, &t, p_slice, lnz, lnzc, cnz, cnzc) > 3072) return 0;
+  /* reconstruction: the decoder's (8.5.10 DC, 8.5.12; uncoded AC reads as zero) */
+  for (int k = 0; k < 16; k++) {
+    int bx = BLK_X[k] * 4, by = BLK_Y[k] * 4, co[16], r[16];
+    for (int q = 0; q < 16; q++) co[q] = acnz ? zac[k][q] : 0;
+    co[0] = dcy_s[BLK_Y[k] * 4 + BLK_X[k]];
+    idct4(co, qp, 1, r);
+    for (int i = 0; i < 4; i++)
+      for (int j = 0; j < 4; j++)
+        rec[(int64_t)(my * 16 + by + i) * cw + mx * 16 + bx + j] = (uint8_t)clip255(py[by + i] + r[i * 4 + j]);
+  }
+  for (int pl = 0; pl < 2; pl++) {
+    const int *c = cdl[pl];
+    int F[4] = {c[0] + c[1] + c[2] + c[3], c[0] - c[1] + c[2] - c[3], c[0] + c[1] - c[2] - c[3],
+                c[0] - c[1] - c[2] + c[3]};
+    for (int k = 0; k < 4; k++) {
+      int co[16], r[16], bx = (k & 1) * 4, by = (k >> 1) * 4;
+      for (int q = 0; q < 16; q++) co[q] = cc == 2 ? cz[pl][k][q] : 0;
+      co[0] = ((F[k] * 16 * NV[qpc % 6][0]) << (qpc / 6)) >> 5;
+      idct4(co, qpc, 1, r);
+      for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++)
+          ruv[(int64_t)(my * 8 + by + i) * cw + 2 * (mx * 8 + bx + j) + pl] = (uint8_t)clip255(pc[pl][by + i] + r[i * 4 + j]);
+    }
+  }
+  *m = t;
+  return 1;
+}
+
+/* The intra pass over one picture: all = 1 (an IDR picture) tries every
+ * macroblock, all = 0 (a P picture) those the search left as I_PCM.  A row is
+ * a chain: a macroblock predicts from, and takes its nC from, the macroblock
+ * to its left as it is finally coded. */
+static void encode_intra(const uint8_t *src, uint8_t *rec, int cw, int ch, int qp, int all, or_mb *mbs) {
+  int mbw = cw / 16, mbh = ch / 16;
+  for (int my = 0; my < mbh; my++) {
+    int lnz[4] = {-1, -1, -1, -1}, lnzc[2][2] = {{-1, -1}, {-1, -1}};
+    for (int mx = 0; mx < mbw; mx++) {
+      or_mb *m = &mbs[my * mbw + mx];
+      if (all) {  /* nothing is coded yet: I_PCM, the source */
+        memset(m, 0, sizeof *m);
+        m->pcm = 1;
+        for (int j = 0; j < 16; j++)
+          memcpy(rec + (int64_t)(my * 16 + j) * cw + mx * 16, src + (int64_t)(my * 16 + j) * cw + mx * 16, 16);
+        for (int j = 0; j < 8; j++)
+          memcpy(rec + (int64_t)cw * ch + (int64_t)(my * 8 + j) * cw + mx * 16,
+                 src + (int64_t)cw * ch + (int64_t)(my * 8 + j) * cw + mx * 16, 16);
+      }
+      if (m->pcm && encode_intra_mb(src, rec, cw, ch, mx, my, qp, !all, lnz, (const int(*)[2])lnzc, m)) m->pcm = 0;
+      right_column_nz(m, lnz, lnzc);
+    }
+  }
+}
+
+/* ------------------------------------------- deblocking filter (deblock = 1) */
+
+/* 8.7.2.3 / 8.7.2.4: one line of samples s[k step], k = -4 .. 3 (p3 .. p0, q0
+ * .. q3) across an edge; returns filterSamplesFlag */
+static int deblock_line(uint8_t *s, int64_t step, int bS, int chroma, int indexA, int alpha, int beta) {
+  int p0 = s[-step], p1 = s[-2 * step], q0 = s[0], q1 = s[step];
+  if (bS == 0 || !(abs(p0 - q0) < alpha && abs(p1 - p0) < beta && abs(q1 - q0) < beta)) return 0;
+  int p2 = chroma ? 0 : s[-3 * step], q2 = chroma ? 0 : s[2 * step];
+  int ap = abs(p2 - p0), aq = abs(q2 - q0);
+  if (bS < 4) {
+    int tc0 = FO_TC0[indexA][bS - 1];
+    int tc = chroma ? tc0 + 1 : tc0 + (ap < beta) + (aq < beta);
+    int delta = clampi((((q0 - p0) << 2) + (p1 - q1) + 4) >> 3, -tc, tc);
+    s[-step] = (uint8_t)clip255(p0 + delta);
+    s[0] = (uint8_t)clip255(q0 - delta);
+    if (!chroma && ap < beta) s[-2 * step] = (uint8_t)(p1 + clampi((p2 + ((p0 + q0 + 1) >> 1) - (p1 << 1)) >> 1, -tc0, tc0));
+    if (!chroma && aq < beta) s[step] = (uint8_t)(q1 + clampi((q2 + ((p0 + q0 + 1) >> 1) - (q1 << 1)) >> 1, -tc0, tc0));
+  } else {
+    int strong = abs(p0 - q0) < ((alpha >> 2) + 2);
+    if (!chroma && ap < beta && strong) {
+      int p3 = s[-4 * step];
+      s[-step] = (uint8_t)((p2 + 2 * p1 + 2 * p0 + 2 * q0 + q1 + 4) >> 3);
+      s[-2 * step] = (uint8_t)((p2 + p1 + p0 + q0 + 2) >> 2);
+      s[-3 * step] = (uint8_t)((2 * p3 + 3 * p2 + p1 + p0 + q0 + 4) >> 3);
+    } else {
+      s[-step] = (uint8_t)((2 * p1 + p0 + q1 + 2) >> 2);
+    }
+    if (!chroma && aq < beta && strong) {
+      int q3 = s[3 * step];
+      s[0] = (uint8_t)((p1 + 2 * p0 + 2 * q0 + 2 * q1 + q2 + 4) >> 3);
+      s[step] = (uint8_t)((p0 + q0 + q1 + q2 + 2) >> 2);
+      s[2 * step] = (uint8_t)((2 * q3 + 3 * q2 + q1 + q0 + p0 + 4) >> 3);
+    } else {
+      s[0] = (uint8_t)((2 * q1 + q0 + p1 + 2) >> 2);
+    }
+  }
+  return 1;
+}
+
+/* the raster 4x4 luma block (bx, by) of an inter macroblock has a non-zero
+ * level that the slice writer codes */
+static int blk_coded(const or_mb *m, int bx, int by) {
+  int k = 0;
+  while (BLK_X[k] != bx || BLK_Y[k] != by) k++;
+  if (!((m->cbp >> (k >> 2)) & 1)) return 0;
+  for (int q = 0; q < 16; q++)
+    if (m->lv[16 * k + q]) return 1;
+  return 0;
+}
+
+/* bS (8.7.2.1) of a line between block (pbx, pby) of macroblock p and block
+ * (qbx, qby) of macroblock q; one reference picture, frame macroblocks */
+static int edge_bs(const or_mb *p, int pbx, int pby, const or_mb *q, int qbx, int qby, int mb_edge) {
+  if (p->pcm || p->i16 || q->pcm || q->i16) return mb_edge ? 4 : 3;
+  if (blk_coded(p, pbx, pby) || blk_coded(q, qbx, qby)) return 2;
+  return (abs(p->mvx - q->mvx) >= 4 || abs(p->mvy - q->mvy) >= 4) ? 1 : 0;
+}
+
+/* Clause 8.7 over one picture with disable_deblocking_filter_idc = 2 and one
+ * slice per macroblock row, in place on rec: per macroblock in raster order
+ * the left macroblock edge (when it has a left neighbour) and the three inner
+ * vertical luma edges, then the three inner horizontal ones (the top edge is
+ * a slice boundary), chroma edges 0 and 2 of each direction likewise.  offa /
+ * offb = FilterOffsetA / B.  Returns the macroblocks with a filtered line. */
+static int64_t deblock_picture(uint8_t *rec, int cw, int ch, const or_mb *mbs, int qp, int offa, int offb) {
+  int mbw = cw / 16, mbh = ch / 16;
+  int64_t count = 0;
+  for (int my = 0; my < mbh; my++)
+    for (int mx = 0; mx < mbw; mx++) {
+      const or_mb *q = &mbs[my * mbw + mx];
+      int any = 0;
+      for (int chroma = 0; chroma < 2; chroma++)
+        for (int pl = 0; pl < (chroma ? 2 : 1); pl++)
+          for (int dir = 0; dir < 2; dir++)
+            for (int e = 0; e < 4; e += chroma ? 2 : 1) {
+              if (e == 0 && (dir == 1 || mx == 0)) continue;
+              const or_mb *p = e == 0 ? &mbs[my * mbw + mx - 1] : q;
+              int qpp = p->pcm ? 0 : qp, qpq = q->pcm ? 0 : qp;  /* qPp, qPq: 0 for I_PCM (8.7.2.2) */
+              int qpav = chroma ? (QPC[qpp] + QPC[qpq] + 1) >> 1 : (qpp + qpq + 1) >> 1;
+              int indexA = clampi(qpav + offa, 0, 51), indexB = clampi(qpav + offb, 0, 51);
+              int alpha = FO_ALPHA[indexA], beta = FO_BETA[indexB];
+              for (int k = 0; k < (chroma ? 8 : 16); k++) {
+                int lk = chroma ? 2 * k : k;  /* the luma line whose bS the chroma line takes */
+                int bS = dir == 0 ? edge_bs(p, (e + 3) & 3, lk >> 2, q, e, lk >> 2, e == 0)
+                                  : edge_bs(p, lk >> 2, (e + 3) & 3, q, lk >> 2, e, 0);
+                uint8_t *s;
+                int64_t step;
+                if (!chroma) {
+                  s = dir == 0 ? rec + (int64_t)(my * 16 + k) * cw + mx * 16 + 4 * e
+                               : rec + (int64_t)(my * 16 + 4 * e) * cw + mx * 16 + k;
+                  step = dir == 0 ? 1 : cw;
+                } else {
+                  uint8_t *uv = rec + (int64_t)cw * ch;
+                  s = dir == 0 ? uv + (int64_t)(my * 8 + k) * cw + 2 * (mx * 8 + 2 * e) + pl
+                               : uv + (int64_t)(my * 8 + 2 * e) * cw + 2 * (mx * 8 + k) + pl;
+                  step = dir == 0 ? 2 : cw;
+                }
+                any |= deblock_line(s, step, bS, chroma, indexA, alpha, beta);
+              }
+            }
+      count += any;
+    }
+  return count;
+}
+
 /* one picture, one slice per macroblock row, appended to out */
 static int write_picture(const uint8_t *src, int cw, int ch, const or_mb *mbs, int idr, int idr_id,
-                         int frame_num, int qp, uint8_t *out, int64_t cap, int64_t *pos, uint8_t *rbsp,
-                         int64_t rcap, int64_t *stats) {
+                         int frame_num, int qp, int intra, int deblock, int dalpha, int dbeta, uint8_t *out,
+                         int64_t cap, int64_t *pos, uint8_t *rbsp, int64_t rcap, int64_t *stats) {
   int mbw = cw / 16, mbh = ch / 16;
   for (int row = 0; row < mbh; row++) {
     or_bw b = {rbsp, 0, rcap, 0, 0};
@@ -648,17 +1137,46 @@ static int write_picture(const uint8_t *src, int cw, int ch, const or_mb *mbs, i
       bw_u(&b, 1, 0);                  /* adaptive_ref_pic_marking_mode_flag */
     }
     bw_se(&b, qp >= 1 ? qp - 26 : 0);  /* slice_qp_delta: SliceQPY = the residual's QP (pic_init_qp 26) */
-    bw_ue(&b, 1);                      /* disable_deblocking_filter_idc */
+    if (deblock) {
+      bw_ue(&b, 2);                    /* disable_deblocking_filter_idc: not across slice boundaries */
+      bw_se(&b, dalpha);               /* slice_alpha_c0_offset_div2 */
+      bw_se(&b, dbeta);                /* slice_beta_offset_div2 */
+    } else {
+      bw_ue(&b, 1);                    /* disable_deblocking_filter_idc */
+    }
     uint32_t skip = 0;
     int amv_ok = 0, amvx = 0, amvy = 0;  /* left neighbour A: inter with this mv */
     /* total_coeff of the left macroblock's right column (nC, 9.2.1): -1 none */
     int lnz[4] = {-1, -1, -1, -1}, lnzc[2][2] = {{-1, -1}, {-1, -1}}, cnz[16], cnzc[2][4];
     for (int mx = 0; mx < mbw; mx++) {
       const or_mb *m = &mbs[row * mbw + mx];
-      if (idr) {
+      if (idr && !intra) {
         bw_ue(&b, 25);
         put_pcm(&b, src, cw, ch, mx, row);
         stats[0]++;
+        continue;
+      }
+      if (m->i16) {  /* Intra16x16 in an I or a P slice */
+        if (!idr) {
+          bw_ue(&b, skip);
+          skip = 0;
+        }
+        put_intra_mb(&b, m, !idr, lnz, (const int(*)[2])lnzc, cnz, cnzc);
+        for (int i = 0; i < 4; i++) lnz[i] = cnz[i * 4 + 3];
+        for (int pl = 0; pl < 2; pl++) {
+          lnzc[pl][0] = cnzc[pl][1];
+          lnzc[pl][1] = cnzc[pl][3];
+        }
+        amv_ok = 0;  /* an intra neighbour predicts no motion (8.4.1.3.2) */
+        stats[4]++;
+        continue;
+      }
+      if (idr) {  /* I_PCM in an I slice of the intra encoder */
+        bw_ue(&b, 25);
+        put_pcm(&b, src, cw, ch, mx, row);
+        stats[0]++;
+        for (int i = 0; i < 4; i++) lnz[i] = 16;
+        for (int pl = 0; pl < 2; pl++) lnzc[pl][0] = lnzc[pl][1] = 16;
         continue;
       }
       if (m->pcm) {
@@ -720,11 +1238,24 @@ static int write_picture(const uint8_t *src, int cw, int ch, const or_mb *mbs, i
  * recon (may be NULL): n coded NV12 reconstructions (cw x ch x 1.5 each);
  * stats: [pcm MBs, P_L0_16x16 MBs, P_Skip MBs, IDR pictures].
  * Returns 0, -1 bad argument, -2 capacity, -3 out of memory. */
-int or_transcode(const uint8_t *frames, int64_t n, int W, int H, const float *scores, float thr,
-                 int idr_at_cuts, int sh, int R, int T, int keyint, int qp, uint8_t *out, int64_t cap, int64_t *sample_off,
-                 int64_t *sample_size, uint8_t *sync, uint8_t *recon, int64_t *stats,
-                 int64_t *out_len) {
+/* or_transcode_ex: the same with the three opt-in paths of DESIGN.md §11.
+ * intra (0 / 1): Intra16x16 coding of the IDR pictures and of the P
+ * macroblocks the search leaves as I_PCM; subpel (0, 1, 2): half- / quarter-
+ * sample refinement of the motion; deblock (0 / 1) with dalpha / dbeta
+ * (slice_alpha_c0_offset_div2 / slice_beta_offset_div2, -6 .. 6): the in-loop
+ * filter inside each macroblock row's slice.  stats has 8 entries: the four
+ * above, then [Intra16x16 MBs, inter MBs with a fractional vector, of those
+ * with a quarter-sample component, MBs with a filtered line]; recon is the
+ * filtered reconstruction (what a decoder outputs).  All zero: or_transcode. */
+int or_transcode_ex(const uint8_t *frames, int64_t n, int W, int H, const float *scores, float thr,
+                    int idr_at_cuts, int sh, int R, int T, int keyint, int qp, int intra, int subpel, int deblock,
+                    int dalpha, int dbeta, uint8_t *out, int64_t cap, int64_t *sample_off,
+                    int64_t *sample_size, uint8_t *sync, uint8_t *recon, int64_t *stats,
+                    int64_t *out_len) {
   if (n <= 0 || sh < 2 || (sh & 1) || R < 0 || R > 16 || keyint < 1 || qp > 51) return -1;
+  if ((intra != 0 && intra != 1) || subpel < 0 || subpel > 2 || (deblock != 0 && deblock != 1)) return -1;
+  if (dalpha < -6 || dalpha > 6 || dbeta < -6 || dbeta > 6 || (!deblock && (dalpha || dbeta))) return -1;
+  if ((intra || deblock) && qp < 1) return -1;
   int sw = or_small_width(W, H, sh);
   int cw = (sw + 15) & ~15, ch = (sh + 15) & ~15, mbw = cw / 16, mbh = ch / 16;
   int64_t fsz = (int64_t)cw * ch * 3 / 2, dsz = (int64_t)W * H * 3 / 2;
@@ -737,7 +1268,7 @@ int or_transcode(const uint8_t *frames, int64_t n, int W, int H, const float *sc
   int rc = (src && rec[0] && rec[1] && mbs && rbsp) ? 0 : -3;
   int64_t pos = 0, last_idr = 0, n_idr = 0;
   int cur = 0;
-  for (int k = 0; k < 4; k++) stats[k] = 0;
+  for (int k = 0; k < 8; k++) stats[k] = 0;
   for (int64_t f = 0; f < n && !rc; f++) {
     or_downscale_nv12(frames + f * dsz, W, H, src, sw, sh);
     int idr = f == 0 || (idr_at_cuts && scores[f] > thr) || f - last_idr >= keyint;
@@ -746,13 +1277,28 @@ int or_transcode(const uint8_t *frames, int64_t n, int W, int H, const float *sc
     sample_off[f] = pos;
     sync[f] = (uint8_t)idr;
     if (idr) {
-      memcpy(rec[cur], src, (size_t)fsz);
-      rc = write_picture(src, cw, ch, mbs, 1, (int)(n_idr & 1), 0, qp, out, cap, &pos, rbsp, rcap, stats);
+      if (intra) {
+        encode_intra(src, rec[cur], cw, ch, qp, 1, mbs);
+      } else {  /* every macroblock I_PCM: the source */
+        memcpy(rec[cur], src, (size_t)fsz);
+        for (int k = 0; k < mbw * mbh; k++) {
+          mbs[k].pcm = 1;
+          mbs[k].i16 = mbs[k].cbp = mbs[k].mvx = mbs[k].mvy = 0;
+        }
+      }
+      rc = write_picture(src, cw, ch, mbs, 1, (int)(n_idr & 1), 0, qp, intra, deblock, dalpha, dbeta, out, cap,
+                         &pos, rbsp, rcap, stats);
       n_idr++;
     } else {
-      encode_p(src, rec[cur ^ 1], rec[cur], cw, ch, R, T, qp, mbs);
-      rc = write_picture(src, cw, ch, mbs, 0, 0, j & 0xffff, qp, out, cap, &pos, rbsp, rcap, stats);
+      encode_p(src, rec[cur ^ 1], rec[cur], cw, ch, R, T, qp, subpel, mbs, stats);
+      if (intra) encode_intra(src, rec[cur], cw, ch, qp, 0, mbs);
+      rc = write_picture(src, cw, ch, mbs, 0, 0, j & 0xffff, qp, intra, deblock, dalpha, dbeta, out, cap, &pos,
+                         rbsp, rcap, stats);
     }
+    /* the in-loop filter: the next picture predicts from, and the decoder
+     * outputs, the filtered picture.  An all-I_PCM picture has qPav 0 on every
+     * edge (alpha' = 0): nothing passes, and the filter leaves it as it is */
+    if (deblock && !rc) stats[7] += deblock_picture(rec[cur], cw, ch, mbs, qp, 2 * dalpha, 2 * dbeta);
     sample_size[f] = pos - sample_off[f];
     if (recon) memcpy(recon + f * fsz, rec[cur], (size_t)fsz);
     cur ^= 1;
@@ -760,5 +1306,16 @@ int or_transcode(const uint8_t *frames, int64_t n, int W, int H, const float *sc
   stats[3] = n_idr;
   *out_len = pos;
   free(src); free(rec[0]); free(rec[1]); free(mbs); free(rbsp);
+  return rc;
+}
+
+int or_transcode(const uint8_t *frames, int64_t n, int W, int H, const float *scores, float thr,
+                 int idr_at_cuts, int sh, int R, int T, int keyint, int qp, uint8_t *out, int64_t cap, int64_t *sample_off,
+                 int64_t *sample_size, uint8_t *sync, uint8_t *recon, int64_t *stats,
+                 int64_t *out_len) {
+  int64_t st[8];
+  int rc = or_transcode_ex(frames, n, W, H, scores, thr, idr_at_cuts, sh, R, T, keyint, qp, 0, 0, 0, 0, 0, out, cap,
+                           sample_off, sample_size, sync, recon, st, out_len);
+  for (int k = 0; k < 4 && rc != -1; k++) stats[k] = st[k];
   return rc;
 }

@@ -4,7 +4,7 @@
 With `deblock=True` every slice (one per macroblock row) carries
 disable_deblocking_filter_idc = 2 and the two slice offsets, and `enc_deblock`
 filters each level's reconstruction before the next level predicts from it.
-There is no byte oracle for it.  As for Intra16x16 and the sub-sample
+The bytes are pinned in tests/test_transcode_bytes_gpu.py.  As for Intra16x16 and the sub-sample
 refinement, the pin is a closed loop through two independent decoders: the
 output is decoded by the CPU general oracle (oracle/h264_full_oracle.c) and by
 the device's general decoder, which both implement clause 8.7; the two must

@@ -1,7 +1,7 @@
 """The opt-in Intra16x16 coder of the device upload transcode
 (vts_transcode_params.intra).
 
-There is no byte oracle for the new syntax.  The pin is a closed loop through
+The bytes are pinned in tests/test_transcode_bytes_gpu.py.  The pin here is a closed loop through
 two independent decoders: the output of `transcode(intra=True)` is decoded by
 the CPU general oracle (oracle/h264_full_oracle.c) and by the device's general
 decoder; the two must agree, and the hash of the oracle's decode must equal

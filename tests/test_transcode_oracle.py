@@ -150,6 +150,214 @@ def test_oracle_residual_coding_round_trip(tmp_path, clip, qp, R, T):
     assert 10 * np.log10(255.0 ** 2 / max(mse, 1e-9)) > 30.0
 
 
+# ------------------ the opt-in paths: intra, subpel, deblock
+# The oracle's own closed loop, before it judges the device
+# (tests/test_transcode_bytes_gpu.py): the general oracle decoder, which has its
+# own 8.3.3 / 8.4.2.2.1 / 8.7, reads the output back to the encoder's
+# reconstruction, and the counts are consistent.
+
+def _closed_loop(tmp_path, frames, W, H, sc, *, out_height, intra, subpel, deblock, **kw):
+    r = oracle.transcode(frames, W, H, sc, out_height=out_height, want_recon=True, intra=bool(intra),
+                         subpel=subpel, deblock=bool(deblock), **kw)
+    cw, ch, sw, sh = r["coded_width"], r["coded_height"], r["width"], r["height"]
+    rec = r["recon"]
+    dec = _decode_full_samples(tmp_path, r)
+    want = np.concatenate([rec[:, :sh, :sw], rec[:, ch:ch + sh // 2, :sw]], 1)
+    bad = [i for i in range(len(want)) if not np.array_equal(dec[i], want[i])]
+    assert bad == [], f"the oracle decoder differs from the encoder's reconstruction at frames {bad[:8]}"
+    n_mb = len(frames) * (cw // 16) * (ch // 16)
+    print({k: v for k, v in r.items() if k.endswith("_mbs") or k == "n_idr"}, sum(map(len, r["samples"])), "bytes")
+    assert r["pcm_mbs"] + r["inter_mbs"] + r["skip_mbs"] + r["intra_mbs"] == n_mb
+    assert 0 <= r["qpel_mbs"] <= r["subpel_mbs"] <= r["inter_mbs"]
+    assert (r["subpel_mbs"] > 0) == (subpel > 0)
+    assert r["qpel_mbs"] == 0 or subpel == 2
+    assert (r["intra_mbs"] > 0) == bool(intra)
+    if not deblock:
+        assert r["deblock_mbs"] == 0
+    return r
+
+
+@pytest.mark.parametrize("deblock", [0, 1])
+@pytest.mark.parametrize("subpel", [0, 1, 2])
+@pytest.mark.parametrize("intra", [0, 1])
+def test_oracle_optin_paths_closed_loop(tmp_path, clip, intra, subpel, deblock):
+    frames, sc, _ = clip
+    r = _closed_loop(tmp_path, frames, 320, 192, sc, out_height=96, intra=intra, subpel=subpel, deblock=deblock)
+    if deblock:
+        assert 0 < r["deblock_mbs"] <= len(frames) * 60   # qp 28
+    if subpel == 2:
+        assert r["qpel_mbs"] > 0
+    if not (intra or subpel or deblock):
+        # all off: today's bytes, through either entry
+        old = oracle.transcode(frames, 320, 192, sc, out_height=96, want_recon=True)
+        assert r["samples"] == old["samples"] and np.array_equal(r["recon"], old["recon"])
+        assert (r["pcm_mbs"], r["inter_mbs"], r["skip_mbs"], r["n_idr"]) == \
+            (old["pcm_mbs"], old["inter_mbs"], old["skip_mbs"], old["n_idr"])
+
+
+def test_oracle_all_off_ex_entry_is_or_transcode(clip):
+    """or_transcode_ex with every new argument zero writes or_transcode's
+    bytes (oracle.transcode takes the old entry when nothing is set)."""
+    import ctypes as C
+    frames, sc, _ = clip
+    old = oracle.transcode(frames, 320, 192, sc, out_height=96, want_recon=True, keyint=16, qp=28)
+    F, cw, ch = len(frames), old["coded_width"], old["coded_height"]
+    cap = sum(map(len, old["samples"])) + 64
+    out, off, size = np.zeros(cap, np.uint8), np.zeros(F, np.int64), np.zeros(F, np.int64)
+    sync, recon, stats = np.zeros(F, np.uint8), np.zeros((F, ch * 3 // 2, cw), np.uint8), np.zeros(8, np.int64)
+    n = C.c_int64(0)
+    fr, s32 = np.ascontiguousarray(frames, np.uint8), np.ascontiguousarray(sc, np.float32)
+    rc = oracle.lib().or_transcode_ex(fr.ctypes.data, F, 320, 192, s32.ctypes.data, 0.08, 0, 96, 8, 1536, 16, 28,
+                                      0, 0, 0, 0, 0, out.ctypes.data, cap, off.ctypes.data, size.ctypes.data,
+                                      sync.ctypes.data, recon.ctypes.data, stats.ctypes.data, C.byref(n))
+    assert rc == 0
+    assert bytes(out[:n.value]) == b"".join(old["samples"])
+    assert np.array_equal(recon, old["recon"])
+    assert list(stats) == [old["pcm_mbs"], old["inter_mbs"], old["skip_mbs"], old["n_idr"], 0, 0, 0, 0]
+
+
+def test_oracle_intra_deblock_high_qp(tmp_path, clip):
+    """qp 40 with Intra16x16 and the filter: bS 4 / 3 edges and the strong
+    filter (alpha' 101, beta' 13 pass on smooth content)."""
+    frames, sc, _ = clip
+    r = _closed_loop(tmp_path, frames, 320, 192, sc, out_height=96, intra=1, subpel=0, deblock=1, qp=40)
+    assert r["deblock_mbs"] > 0
+
+
+@pytest.mark.parametrize("R", [0, 16])
+def test_oracle_subpel_at_the_range_limits(tmp_path, clip, R):
+    """search_range 0 (the refinement is the whole search) and 16 (vectors up
+    to 4 * 16 + 3 quarter samples, far over the clamped edges)."""
+    frames, sc, _ = clip
+    _closed_loop(tmp_path, frames, 320, 192, sc, out_height=96, intra=0, subpel=2, deblock=0, search_range=R)
+
+
+def test_oracle_two_by_two_macroblocks(tmp_path):
+    """64x48 -> 32x24, coded 32x32: every macroblock touches two picture edges
+    and a row is the shortest chain that still has a left neighbour.
+    max_motion 8 leaves the search misses that a P picture codes as intra."""
+    p = tmp_path / "tiny.mp4"
+    scene.synth_write(p, width=64, height=48, n_frames=40, cut_min_s=0.7, cut_max_s=1.5, gop_max_s=0.5,
+                      max_motion=8)
+    frames, _ = oracle.decode_file(p)
+    sc = oracle.score_frames(frames.reshape(-1), frames[0].size, 40, 64, 48, 64, 48, 4, want_rgb=False)["score"]
+    r = _closed_loop(tmp_path, frames, 64, 48, sc, out_height=24, intra=1, subpel=2, deblock=1, search_range=4)
+    assert (r["coded_width"], r["coded_height"]) == (32, 32)
+    assert r["deblock_mbs"] > 0
+
+
+def crafted_frames(F=12, W=96, H=64, seed=11):
+    """Display-size NV12 frames (samples >= 1) whose P pictures need every
+    decision: per macroblock and frame a ramp (the motion search predicts it),
+    fresh noise (nothing predicts it: I_PCM at a low qp), or rows that are
+    constant along x and new in every frame (the search misses, Intra16x16
+    Horizontal predicts them from the left column)."""
+    rng = np.random.default_rng(seed)
+    fr = np.zeros((F, H * 3 // 2, W), np.uint8)
+    for f in range(F):
+        y = np.tile(np.linspace(60, 180, W).astype(np.uint8), (H, 1))
+        uv = np.full((H // 2, W), 128, np.uint8)
+        for my in range(H // 16):
+            for mx in range(W // 16):
+                kind = rng.integers(0, 4)
+                ys, xs, cs = slice(my * 16, my * 16 + 16), slice(mx * 16, mx * 16 + 16), slice(my * 8, my * 8 + 8)
+                if kind == 1:
+                    y[ys, xs] = rng.integers(1, 256, (16, 16))
+                    uv[cs, xs] = rng.integers(1, 256, (8, 16))
+                elif kind == 2:
+                    y[ys, xs] = rng.integers(1, 256, (16, 1))
+                    uv[cs, xs] = np.repeat(rng.integers(1, 256, (8, 1, 2)), 8, 1).reshape(8, 16)
+        fr[f, :H], fr[f, H:] = y, uv
+    return np.maximum(fr, 1)
+
+
+@pytest.mark.parametrize("qp,kw", [(4, dict(subpel=0, deblock=0)),
+                                   (12, dict(subpel=2, deblock=1, deblock_offsets=(6, 6))),
+                                   (4, dict(subpel=2, deblock=1, deblock_offsets=(6, 6)))])
+def test_oracle_p_pictures_with_every_macroblock_kind(tmp_path, qp, kw):
+    """P pictures that mix inter, P_Skip, Intra16x16 and (at a low qp) I_PCM
+    macroblocks: Intra16x16 with an inter or an I_PCM left neighbour (its
+    prediction, its nC, mb_type + 5), the filter across I_PCM edges (qPp 0)."""
+    fr = crafted_frames()
+    sc = np.zeros(len(fr), np.float32)
+    r = _closed_loop(tmp_path, fr, 96, 64, sc, out_height=64, intra=1, qp=qp, **kw)
+    assert r["n_idr"] == 1 and r["inter_mbs"] > 0 and r["skip_mbs"] > 0 and r["pcm_mbs"] > 0
+    if qp == 4:
+        assert r["intra_mbs"] > 24          # more than the IDR picture's 6 x 4
+    if qp == 12:
+        assert r["deblock_mbs"] > 0         # indexA 24 between coded macroblocks, 18 beside I_PCM
+
+
+class _Bits:
+    """A bit string written by hand from 7.3.3 / 7.3.5 (the test's own, not the oracle's writer)."""
+
+    def __init__(self):
+        self.s = ""
+
+    def u(self, n, v):
+        self.s += format(v, f"0{n}b") if n else ""
+        return self
+
+    def ue(self, v):
+        b = format(v + 1, "b")
+        self.s += "0" * (len(b) - 1) + b
+        return self
+
+    def se(self, v):
+        return self.ue(2 * v - 1 if v > 0 else -2 * v)
+
+    def nal(self, header):
+        s = self.s + "1"
+        s += "0" * (-len(s) % 8)
+        out, zeros = bytearray([header]), 0
+        for i in range(0, len(s), 8):
+            v = int(s[i:i + 8], 2)
+            if zeros >= 2 and v <= 3:
+                out.append(3)
+                zeros = 0
+            out.append(v)
+            zeros = zeros + 1 if v == 0 else 0
+        return len(out).to_bytes(4, "big") + bytes(out)
+
+
+def test_oracle_ties_on_a_flat_picture(tmp_path):
+    """Two frames of constant 128, where every decision is a tie, against
+    slices written out by hand.  IDR picture: macroblock 0 of a row has no
+    neighbour (Intra16x16 DC from 128, mb_type 3); to its right Horizontal and
+    DC predict the same samples and the lower mode number, Horizontal, wins
+    (mb_type 2); nothing is coded, so each macroblock is mb_type,
+    intra_chroma_pred_mode 0 (DC, the lower of its tie), mb_qp_delta 0 and an
+    empty Intra16x16DCLevel at nC 0 (coeff_token '1').  P picture: all 17
+    sub-sample candidates of both steps have SAD 0, the centre wins, the vector
+    stays (0, 0) and the row is one mb_skip_run."""
+    W, H, mbw, mbh = 64, 32, 4, 2
+    fr = np.full((2, H * 3 // 2, W), 128, np.uint8)
+    r = oracle.transcode(fr, W, H, np.zeros(2, np.float32), out_height=H, want_recon=True, intra=True, subpel=2)
+    assert (r["intra_mbs"], r["skip_mbs"], r["inter_mbs"], r["pcm_mbs"]) == (mbw * mbh, mbw * mbh, 0, 0)
+    assert (r["subpel_mbs"], r["qpel_mbs"]) == (0, 0)
+    assert np.array_equal(r["recon"], fr)
+    idr, p = b"", b""
+    for row in range(mbh):
+        b = _Bits().ue(row * mbw).ue(7).ue(0).u(16, 0).ue(0).u(2, 0).se(28 - 26).ue(1)
+        b.ue(3).ue(0).se(0).u(1, 1)
+        for _ in range(mbw - 1):
+            b.ue(2).ue(0).se(0).u(1, 1)
+        idr += b.nal(0x65)
+        p += _Bits().ue(row * mbw).ue(5).ue(0).u(16, 1).u(3, 0).se(28 - 26).ue(1).ue(mbw).nal(0x41)
+    assert r["samples"][0] == idr
+    assert r["samples"][1] == p
+    assert np.array_equal(_decode_full_samples(tmp_path, r), fr)
+
+
+def test_oracle_intra_of_all_pcm_p_pictures(tmp_path, clip):
+    """max_mb_sad < 0 leaves every P macroblock to the intra pass: rows of
+    Intra16x16 macroblocks in P slices."""
+    frames, sc, _ = clip
+    r = _closed_loop(tmp_path, frames[:30], 320, 192, sc[:30], out_height=96, intra=1, subpel=0, deblock=1,
+                     max_mb_sad=-1)
+    assert r["intra_mbs"] == 30 * 60
+
+
 @pytest.mark.parametrize("at_cuts", [False, True])
 def test_oracle_idr_at_keyint_and_optionally_cuts(clip, at_cuts):
     frames, sc, _ = clip

@@ -1,8 +1,8 @@
 """The opt-in half- and quarter-sample motion refinement of the device upload
 transcode (vts_transcode_ext.subpel).
 
-There is no byte oracle for the refined vectors.  As for Intra16x16, the pin
-is a closed loop through two independent decoders: the output of
+The bytes are pinned in tests/test_transcode_bytes_gpu.py.  As for Intra16x16,
+the pin here is a closed loop through two independent decoders: the output of
 `transcode(subpel=1 | 2)` is decoded by the CPU general oracle
 (oracle/h264_full_oracle.c) and by the device's general decoder, which both
 implement the luma interpolation of 8.4.2.2.1; the two must agree, and the
