@@ -407,7 +407,8 @@ void vts_batch_free(vts_batch *b);
  * I_PCM, or Intra16x16 with intra = 1) every keyint frames (and at scene cuts
  * if asked), P pictures of full-search
  * integer motion (P_L0_16x16 / P_Skip; refined to half or quarter samples
- * with vts_transcode_ext.subpel) with a quantised residual (qp), I_PCM
+ * with vts_transcode_ext.subpel; vector cost and early P_Skip with
+ * vts_transcode_ext3.mvcost / early_skip) with a quantised residual (qp), I_PCM
  * where that residual would cost more; one slice per macroblock row, the
  * in-loop filter off or (vts_transcode_ext2.deblock) on inside each slice; MP4
  * (moov at the end), video only.  DESIGN.md §11. */
@@ -511,6 +512,49 @@ typedef struct vts_transcode_ext_info2 {
                               one sample line (filterSamplesFlag); 0 when
                               deblock is off                                   */
 } vts_transcode_ext_info2;
+
+/* Two rate-aware decisions of the motion search and the encoder's command
+ * words, DESIGN.md §11.  As the structs above: begun with them, passed by
+ * pointer cast, struct_size = their own sizeof.  Read: mvcost when struct_size
+ * >= 28, mv_lambda16 at >= 32, early_skip at >= 36, cmd_out at >= 48, cmd_cap
+ * at >= 56 (a field the struct does not reach is 0 / NULL); written:
+ * early_skip_mbs at >= 40, cmd_words at >= 48.  Both decisions need residual
+ * coding (qp >= 0) and run only with max_mb_sad >= 0.
+ * mvcost = 1: the search orders its candidates (integer pass and both
+ * refinement steps) by 16 SAD + lambda16 * bits(mvd against a predictor guess:
+ * the left macroblock's vector in the previous picture) instead of the SAD
+ * alone.  early_skip = 1: a macroblock whose residual at vector (0, 0)
+ * quantises to nothing is P_Skip before any search.
+ * Command words (cmd_out[frame][my][mx] over the coded macroblock grid, the
+ * encoder's final decision per macroblock, with any settings): an inter
+ * macroblock's is its vector in quarter samples, (uint16_t)mvx |
+ * (uint16_t)mvy << 16 (P_Skip is 0); 0x80008000 is I_PCM; Intra16x16 is
+ * 0x80000000 | Intra16x16PredMode (1 Horizontal, 2 DC) |
+ * intra_chroma_pred_mode (0 DC, 1 Horizontal) << 2 | coded_block_pattern << 4
+ * (high half 0x8000, bit 15 clear).  Pictures whose words the
+ * encoder never writes (IDR pictures with intra = 0) are reported as I_PCM.
+ * VTS_E_INVALID, the field named: mvcost or early_skip not 0 or 1,
+ * mv_lambda16 outside 0..4096, mv_lambda16 != 0 with mvcost = 0, either flag
+ * with qp < 0.  VTS_E_CAPACITY before any encoding: cmd_out with cmd_cap <
+ * cmd_words.  recon_hash is also filled when either flag is set. */
+typedef struct vts_transcode_ext3 {
+  vts_transcode_ext2 base;
+  int32_t mvcost;          /* 0 off (every output byte as before), 1 on         */
+  int32_t mv_lambda16;     /* 16 lambda of the vector cost, 1..4096; 0 = the
+                              table's value for qp (93.7 -> 94 at qp 28)       */
+  int32_t early_skip;      /* 0 off (every output byte as before), 1 on         */
+  int32_t _pad;
+  uint32_t *cmd_out;       /* NULL, or cmd_cap words that receive the command
+                              word of every macroblock                         */
+  int64_t cmd_cap;         /* words cmd_out holds                               */
+} vts_transcode_ext3;
+
+typedef struct vts_transcode_ext_info3 {
+  vts_transcode_ext_info2 base;
+  int64_t early_skip_mbs;  /* macroblocks the early P_Skip probe decided; 0
+                              when early_skip is off                           */
+  int64_t cmd_words;       /* n_frames * macroblocks per picture               */
+} vts_transcode_ext_info3;
 
 /* vts_transcode with the settings of `ext` (NULL: none) and the further facts
  * in `ext_info` (NULL: not wanted).  vts_transcode(c, o, p, i) is

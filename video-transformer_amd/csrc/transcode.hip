@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "enc_deblock.h"
+#include "enc_rate.h"
 #include "mp4.h"
 #include "recon_full.h"
 #include "session.h"
@@ -236,8 +237,12 @@ struct SearchArgs {
   int16_t *coef;        // [entry][mb][kCoefPerMb] levels (this level's ring slot)
   int32_t cw, ch, mbw, nmb;
   int32_t range, max_sad;
-  int32_t qp, _pad;     // qp >= 1: residual coding at that QP
+  int32_t qp, rate;     // qp >= 1: residual coding at that QP; RC: bit 0 mvcost, bit 1 early_skip (enc_rate.h)
   unsigned long long *sp_stats;  // SP > 0: inter macroblocks with a fractional vector: [0] no odd component, [1] one
+  // RC only
+  const uint32_t *cmd_prev;      // the previous level's final words [entry][mb]; ent[e].w = the GOP's entry there
+  int32_t gop_pos, lambda16;     // the level's GOP position j; lambda16 of the vector cost
+  unsigned long long *es_stat;   // macroblocks the early P_Skip probe decided
 };
 
 __device__ __forceinline__ uint32_t u32_at(const uint8_t *lds_row, int off) {  // 4 bytes at any offset
@@ -292,8 +297,12 @@ __device__ __forceinline__ uint32_t avg_u8x4(uint32_t p, uint32_t q) { return (p
 // RT: compile-time search range (register-blocked path), 0 = any range.
 // SP: sub-sample refinement around the integer winner, 0 none (the code is
 // the integer-only kernel's), 1 half samples, 2 half then quarter samples.
-template <int RT, int SP>
-__global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
+// RC: the rate-aware decisions of enc_rate.h, each switched by a bit of
+// a.rate (wave-uniform); false: the code is the kernel's without them.  The
+// RC instances ask for the 5 waves/SIMD the others get by themselves (without
+// the hint the integer-only ones take 98 VGPRs, 4 waves; with it 92, no scratch).
+template <int RT, int SP, bool RC>
+__global__ void __launch_bounds__(64) VTS_SEARCH_OCC __attribute__((amdgpu_waves_per_eu(RC ? 5 : 1))) enc_search(SearchArgs a) {
   constexpr int LX = SP ? kSpLoX : 0, LY = SP ? kSpLoY : 0, HI = SP ? kSpHi : 0;  // window margins
   constexpr int WP = SP ? kWinPitchSp : kWinPitch;
   static_assert(!(SP && VTS_SEARCH_UV_LDS), "the LDS chroma window is sized for integer vectors");
@@ -314,6 +323,72 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
   // source luma: lane -> row lane / 4, 4 bytes
   srcy[lane] = *reinterpret_cast<const uint32_t *>(src + static_cast<int64_t>(my * 16 + (lane >> 2)) * a.cw +
                                                    mx * 16 + 4 * (lane & 3));
+  namespace er = full::erate;
+  int lam16 = 0;     // RC: 0 orders the candidates as the SAD alone
+  er::Mv pmv{0, 0};  // RC: the predictor guess, quarter samples
+  if constexpr (RC) {
+    const bool coded = a.qp >= 1 && a.max_sad >= 0;
+    if (coded && (a.rate & 2)) {
+      // ---- early P_Skip: the co-located prediction (vector (0, 0); chroma
+      // 8.4.2.2.2 at (0, 0) is the co-located sample) through the residual
+      // path's transform and quantiser; with no level left the macroblock is
+      // decided before the window is loaded
+      __shared__ uint32_t epy[64];
+      __shared__ uint16_t epc[64], esc[64];
+      __shared__ int edc[2][4];
+      const int64_t lo0 = static_cast<int64_t>(my * 16 + (lane >> 2)) * a.cw + mx * 16 + 4 * (lane & 3);
+      const int64_t co0 = static_cast<int64_t>(a.cw) * a.ch + static_cast<int64_t>(my * 8 + (lane >> 3)) * a.cw +
+                          2 * (mx * 8 + (lane & 7));
+      const uint32_t py0 = *reinterpret_cast<const uint32_t *>(ref + lo0);
+      const uint16_t pc0 = *reinterpret_cast<const uint16_t *>(ref + co0);
+      epy[lane] = py0;
+      epc[lane] = pc0;
+      esc[lane] = *reinterpret_cast<const uint16_t *>(src + co0);
+      __syncthreads();
+      const int qpc = kQpcTab[a.qp];
+      bool nz = false;
+      if (lane < 16) {
+        const int bx = kBlkXd[lane], by = kBlkYd[lane];
+        int x[16];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const uint32_t sv = srcy[(by * 4 + r) * 4 + bx], pv4 = epy[(by * 4 + r) * 4 + bx];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) x[r * 4 + c] = static_cast<int>((sv >> (8 * c)) & 255) - static_cast<int>((pv4 >> (8 * c)) & 255);
+        }
+        nz = !er::all_zero_block(x, a.qp, nullptr);
+      } else if (lane < 24) {
+        const int pl = (lane - 16) >> 2, k = (lane - 16) & 3, bx = (k & 1) * 4, by = (k >> 1) * 4;
+        int x[16], dc;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const int i = (by + r) * 8 + bx + c;
+            x[r * 4 + c] = static_cast<int>((esc[i] >> (8 * pl)) & 255) - static_cast<int>((epc[i] >> (8 * pl)) & 255);
+          }
+        nz = !er::all_zero_block(x, qpc, &dc);
+        edc[pl][k] = dc;
+      }
+      __syncthreads();
+      if (lane == 16 || lane == 17) nz |= !er::all_zero_chroma_dc(edc[lane - 16], qpc);
+      if (__ballot(nz) == 0) {  // wave-uniform: P_Skip, the reconstruction is the prediction
+        *reinterpret_cast<uint32_t *>(dst + lo0) = py0;
+        *reinterpret_cast<uint16_t *>(dst + co0) = pc0;
+        if (lane == 0) {
+          a.cmd[e * a.nmb + mb] = 0;
+          a.cbp[e * a.nmb + mb] = 0;
+          atomicAdd(a.es_stat, 1ull);
+        }
+        return;
+      }
+    }
+    if (coded && (a.rate & 1)) {
+      lam16 = a.lambda16;
+      pmv = er::pred_of_cmd(mx > 0 && a.gop_pos > 1 ? a.cmd_prev[static_cast<int64_t>(en.w) * a.nmb + mb - 1] : 0u, mx,
+                           a.gop_pos);
+    }
+  }
   {
     // window rows of W4 dwords (one division per lane, then carry stepping);
     // a dword wholly inside the picture row and aligned (R % 4 == 0) is one
@@ -407,7 +482,11 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
         if (dyi < SIDE) {
           const int r = dyi * SIDE + gx;
           const int c = r == center ? 0 : (r < center ? r + 1 : r);
-          const uint64_t key = (static_cast<uint64_t>(acc[g]) << 32) | static_cast<uint32_t>(c);
+          uint64_t key;
+          if constexpr (RC)
+            key = er::key_of(er::cost16(acc[g], lam16, 4 * (gx - RT), 4 * (dyi - RT), pmv.x, pmv.y), c, acc[g]);
+          else
+            key = (static_cast<uint64_t>(acc[g]) << 32) | static_cast<uint32_t>(c);
           best = key < best ? key : best;
         }
       }
@@ -432,7 +511,9 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
         s = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w3, w2, sh), sv.z, s);
         s = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w4, w3, sh), sv.w, s);
       }
-      const uint64_t key = (static_cast<uint64_t>(s) << 32) | static_cast<uint32_t>(c);
+      uint64_t key;
+      if constexpr (RC) key = er::key_of(er::cost16(s, lam16, 4 * dx, 4 * dy, pmv.x, pmv.y), c, s);
+      else key = (static_cast<uint64_t>(s) << 32) | static_cast<uint32_t>(c);
       best = key < best ? key : best;
     }
   }
@@ -441,7 +522,7 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
     const uint64_t o = __shfl_xor(best, off);
     best = o < best ? o : best;
   }
-  const int c = static_cast<int>(best & 0xffffffffu);
+  const int c = static_cast<int>(RC ? er::key_index(best) : best & 0xffffffffu);
   const int r = c == 0 ? center : (c - 1 < center ? c - 1 : c);
   const int dy = r / side - R, dx = r % side - R;
   // prediction and cost: lane -> 4 luma samples (row lane/4) and one chroma pair
@@ -496,7 +577,7 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
     // Per step the 8 candidates around the centre go to 8 lanes each (2 rows
     // a lane); the centre's SAD is known.  Key (SAD, index): centre 0, the
     // others 1 .. 8 in raster order.
-    uint32_t csad = static_cast<uint32_t>(best >> 32);
+    uint32_t csad = RC ? er::key_sad(best) : static_cast<uint32_t>(best >> 32);
 #pragma unroll
     for (int step = 2; step >= (SP == 2 ? 1 : 2); step >>= 1) {
       const int k = (lane >> 3) + 1, pos = k - 1 < 4 ? k - 1 : k;
@@ -524,20 +605,26 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC enc_search(SearchArgs a) {
       s += __shfl_xor(s, 1);
       s += __shfl_xor(s, 2);
       s += __shfl_xor(s, 4);
-      uint64_t key = (static_cast<uint64_t>(s) << 32) | static_cast<uint32_t>(k);
-      const uint64_t ckey = static_cast<uint64_t>(csad) << 32;
+      uint64_t key, ckey;
+      if constexpr (RC) {  // the centre's bits are its own: recomputed, not the integer pass's
+        key = er::key_of(er::cost16(s, lam16, 4 * dx + qx, 4 * dy + qy, pmv.x, pmv.y), k, s);
+        ckey = er::key_of(er::cost16(csad, lam16, 4 * dx + cqx, 4 * dy + cqy, pmv.x, pmv.y), 0, csad);
+      } else {
+        key = (static_cast<uint64_t>(s) << 32) | static_cast<uint32_t>(k);
+        ckey = static_cast<uint64_t>(csad) << 32;
+      }
       key = ckey < key ? ckey : key;
 #pragma unroll
       for (int off = 32; off >= 8; off >>= 1) {
         const uint64_t o = __shfl_xor(key, off);
         key = o < key ? o : key;
       }
-      const int kw = static_cast<int>(key & 0xffffffffu);
+      const int kw = static_cast<int>(RC ? er::key_index(key) : key & 0xffffffffu);
       if (kw) {  // wave-uniform
         const int pw = kw - 1 < 4 ? kw - 1 : kw;
         cqx += step * (pw % 3 - 1);
         cqy += step * (pw / 3 - 1);
-        csad = static_cast<uint32_t>(key >> 32);
+        csad = RC ? er::key_sad(key) : static_cast<uint32_t>(key >> 32);
       }
     }
     int XA, YA, XB, YB, offa, offb, pa, pb_;
@@ -1875,13 +1962,13 @@ int small_window(vts_ctx *c, int ring, int64_t f0, int64_t f1, hipStream_t s) {
 }
 
 namespace {
-template <int SP>
+template <int SP, bool RC>
 void launch_search(int R, dim3 grid, hipStream_t s, const SearchArgs &sa) {
   switch (R) {
-    case 4: hipLaunchKernelGGL((enc_search<4, SP>), grid, dim3(64), 0, s, sa); break;
-    case 8: hipLaunchKernelGGL((enc_search<8, SP>), grid, dim3(64), 0, s, sa); break;
-    case 16: hipLaunchKernelGGL((enc_search<16, SP>), grid, dim3(64), 0, s, sa); break;
-    default: hipLaunchKernelGGL((enc_search<0, SP>), grid, dim3(64), 0, s, sa); break;
+    case 4: hipLaunchKernelGGL((enc_search<4, SP, RC>), grid, dim3(64), 0, s, sa); break;
+    case 8: hipLaunchKernelGGL((enc_search<8, SP, RC>), grid, dim3(64), 0, s, sa); break;
+    case 16: hipLaunchKernelGGL((enc_search<16, SP, RC>), grid, dim3(64), 0, s, sa); break;
+    default: hipLaunchKernelGGL((enc_search<0, SP, RC>), grid, dim3(64), 0, s, sa); break;
   }
 }
 }  // namespace
@@ -1902,6 +1989,9 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   if (!c || !out_path) return fail(VTS_E_INVALID, "NULL argument");
   // size-tagged structs: only the prefix known here is read or written
   int subpel = 0, deblock = 0, dbk_alpha = 0, dbk_beta = 0;
+  int mvcost = 0, mv_lambda16 = 0, early_skip = 0;
+  uint32_t *cmd_out = nullptr;
+  int64_t cmd_cap = 0;
   if (ext) {
     if (ext->struct_size < 8) return fail(VTS_E_INVALID, "vts_transcode_ext.struct_size %u < 8", ext->struct_size);
     subpel = ext->subpel;
@@ -1916,7 +2006,19 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
     if (dbk_beta < -6 || dbk_beta > 6) return fail(VTS_E_INVALID, "deblock_beta %d: -6 .. 6", dbk_beta);
     if (!deblock && dbk_alpha) return fail(VTS_E_INVALID, "deblock_alpha %d without deblock = 1", dbk_alpha);
     if (!deblock && dbk_beta) return fail(VTS_E_INVALID, "deblock_beta %d without deblock = 1", dbk_beta);
+    // vts_transcode_ext3, the same way
+    const vts_transcode_ext3 *x3 = reinterpret_cast<const vts_transcode_ext3 *>(ext);
+    if (ext->struct_size >= 28) mvcost = x3->mvcost;
+    if (ext->struct_size >= 32) mv_lambda16 = x3->mv_lambda16;
+    if (ext->struct_size >= 36) early_skip = x3->early_skip;
+    if (ext->struct_size >= 48) cmd_out = x3->cmd_out;
+    if (ext->struct_size >= 56) cmd_cap = x3->cmd_cap;
+    if (mvcost != 0 && mvcost != 1) return fail(VTS_E_INVALID, "mvcost %d: 0 or 1", mvcost);
+    if (early_skip != 0 && early_skip != 1) return fail(VTS_E_INVALID, "early_skip %d: 0 or 1", early_skip);
+    if (mv_lambda16 < 0 || mv_lambda16 > 4096) return fail(VTS_E_INVALID, "mv_lambda16 %d: 0 .. 4096", mv_lambda16);
+    if (!mvcost && mv_lambda16) return fail(VTS_E_INVALID, "mv_lambda16 %d without mvcost = 1", mv_lambda16);
   }
+  const int rate = mvcost | (early_skip << 1);  // SearchArgs.rate
   if (xinfo && xinfo->struct_size < 8)
     return fail(VTS_E_INVALID, "vts_transcode_ext_info.struct_size %u < 8", xinfo->struct_size);
   using clk = std::chrono::steady_clock;
@@ -1929,9 +2031,11 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   if (qp > 51) return fail(VTS_E_INVALID, "qp %d > 51", qp);
   if (p.intra != 0 && p.intra != 1) return fail(VTS_E_INVALID, "intra %d: 0 or 1", p.intra);
   const bool intra = p.intra == 1;
-  const bool hashed = intra || subpel != 0 || deblock;  // recon_hash is computed
+  const bool hashed = intra || subpel != 0 || deblock || rate;  // recon_hash is computed
   if (intra && qp < 1) return fail(VTS_E_INVALID, "intra = 1 needs residual coding (qp >= 0)");
   if (deblock && qp < 1) return fail(VTS_E_INVALID, "deblock = 1 needs residual coding (qp >= 0)");
+  if (mvcost && qp < 1) return fail(VTS_E_INVALID, "mvcost = 1 needs residual coding (qp >= 0)");
+  if (early_skip && qp < 1) return fail(VTS_E_INVALID, "early_skip = 1 needs residual coding (qp >= 0)");
   const int keyint = p.keyint > 0 ? p.keyint : 250;
   const float thr = p.cut_threshold > 0 ? p.cut_threshold : c->params.cut_threshold;
   if ((sh & 1) || sh < 16 || sh > c->height)
@@ -1949,6 +2053,12 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   const SmallStore &S = c->small;
   const int mbw = S.cw / 16, mbh = S.ch / 16, nmb = mbw * mbh;
   double ms[4] = {0, 0, 0, 0};
+  // the command words of every macroblock, [frame][my][mx]: reported always, copied out when asked
+  const int64_t cmd_words = c->n_frames * nmb;
+  if (xinfo && xinfo->struct_size >= 48) reinterpret_cast<vts_transcode_ext_info3 *>(xinfo)->cmd_words = cmd_words;
+  if (cmd_out && cmd_cap < cmd_words)
+    return fail(VTS_E_CAPACITY, "cmd_cap %lld < %lld command words", static_cast<long long>(cmd_cap),
+                static_cast<long long>(cmd_words));
 
   // 1. decode + score + downscale
   auto t0 = clk::now();
@@ -1974,14 +2084,19 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   // per level j: search entries (frame, ref slot, dst slot) and write entries (frame, j, idr parity)
   std::vector<int4> sent, went;
   std::vector<int64_t> lvl_off(static_cast<size_t>(maxlen) + 1, 0);
+  // with a rate-aware search, w of a search entry: the GOP's entry index in the previous level (GOPs of
+  // different lengths: the indices differ between levels), where enc_search finds the previous picture's words
+  std::vector<int> lvl_idx(static_cast<size_t>(ngop), 0);
   for (int64_t j = 0; j < maxlen; ++j) {
     lvl_off[j] = static_cast<int64_t>(went.size());
     for (int64_t g = 0; g < ngop; ++g) {
       if (gop_len[g] <= j) continue;
       const int f = static_cast<int>(gop_start[g] + j);
+      const int prev_idx = rate ? lvl_idx[g] : 0;
+      lvl_idx[g] = static_cast<int>(static_cast<int64_t>(went.size()) - lvl_off[j]);
       // level 1 predicts from the IDR picture: its source (all I_PCM) or, with intra, its reconstruction
       sent.push_back(make_int4(f, j == 1 && !intra ? -1 : static_cast<int>(2 * g + ((j - 1) & 1)),
-                               static_cast<int>(2 * g + (j & 1)), 0));
+                               static_cast<int>(2 * g + (j & 1)), prev_idx));
       went.push_back(make_int4(f, static_cast<int>(j), static_cast<int>(g & 1),
                                static_cast<int>(static_cast<int64_t>(went.size()) - lvl_off[j])));
     }
@@ -2024,8 +2139,8 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   VTS_TRY(B.get(&d_sizes, static_cast<size_t>(max_chunk * mbh)));
   VTS_TRY(B.get(&d_offs, static_cast<size_t>(max_chunk * mbh)));
   // pcm, inter, skip, intra macroblocks; the reconstruction hash; enc_search's two sub-sample counts;
-  // enc_deblock's filtered macroblocks
-  VTS_TRY(B.get(&d_stats, 8));
+  // enc_deblock's filtered macroblocks; enc_search's early P_Skip macroblocks
+  VTS_TRY(B.get(&d_stats, 9));
   VTS_TRY(B.get(&d_err, 1));
   uint4 *d_jobs;
   uint32_t *d_njobs;
@@ -2049,7 +2164,7 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   }
   HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), s2));
   // enc_hash, enc_search<., SP > 0> and enc_deblock (s1) add into these
-  if (hashed) HIP_TRY(hipMemsetAsync(d_stats + 4, 0, 4 * sizeof(unsigned long long), s1));
+  if (hashed) HIP_TRY(hipMemsetAsync(d_stats + 4, 0, (rate ? 5 : 4) * sizeof(unsigned long long), s1));
   HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(uint32_t), s2));
   const int64_t nchunks = (maxlen + kChunkLevels - 1) / kChunkLevels;
   std::vector<hipEvent_t> ev(static_cast<size_t>(maxlen + 5 + nchunks), nullptr);
@@ -2149,10 +2264,23 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
       sa.qp = qp;
       sa.sp_stats = d_stats + 5;
       const dim3 grid(static_cast<unsigned>(ne * nmb));
-      switch (subpel) {
-        case 1: launch_search<1>(R, grid, s1, sa); break;
-        case 2: launch_search<2>(R, grid, s1, sa); break;
-        default: launch_search<0>(R, grid, s1, sa); break;
+      if (rate) {  // the instances with the rate-aware decisions compiled in
+        sa.rate = rate;
+        sa.cmd_prev = d_cmd + lvl_off[j - 1] * nmb;
+        sa.gop_pos = static_cast<int32_t>(j);
+        sa.lambda16 = full::erate::lambda16(qp, mv_lambda16);
+        sa.es_stat = d_stats + 8;
+        switch (subpel) {
+          case 1: launch_search<1, true>(R, grid, s1, sa); break;
+          case 2: launch_search<2, true>(R, grid, s1, sa); break;
+          default: launch_search<0, true>(R, grid, s1, sa); break;
+        }
+      } else {
+        switch (subpel) {
+          case 1: launch_search<1, false>(R, grid, s1, sa); break;
+          case 2: launch_search<2, false>(R, grid, s1, sa); break;
+          default: launch_search<0, false>(R, grid, s1, sa); break;
+        }
       }
       if (intra) enqueue_intra(j);
       if (deblock) enqueue_deblock(j);
@@ -2284,10 +2412,19 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   }
   VTS_TRY(status);
   uint32_t err = 0;
-  unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long st[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   HIP_TRY(hipMemcpy(&err, d_err, sizeof err, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost));
   if (err) return fail(VTS_E_CAPACITY, "a slice exceeded its %lld-byte staging slot", static_cast<long long>(cap));
+  if (cmd_out) {  // entry order -> frame order; a level the encoder writes no words for (the I_PCM IDR pictures) is I_PCM
+    std::vector<uint32_t> words(went.size() * static_cast<size_t>(nmb));
+    HIP_TRY(hipMemcpy(words.data(), d_cmd, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < went.size(); ++i) {
+      uint32_t *o = cmd_out + static_cast<int64_t>(went[i].x) * nmb;
+      if (went[i].y == 0 && !intra) std::fill(o, o + nmb, kPcmCmd);
+      else std::memcpy(o, words.data() + i * static_cast<size_t>(nmb), static_cast<size_t>(nmb) * sizeof(uint32_t));
+    }
+  }
 
   // 4. MP4 sample table (display order) over the mdat written above
   t0 = clk::now();
@@ -2326,6 +2463,8 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
     if (xinfo->struct_size >= 24) xinfo->qpel_mbs = subpel ? static_cast<int64_t>(st[6]) : 0;
     if (xinfo->struct_size >= 32)
       reinterpret_cast<vts_transcode_ext_info2 *>(xinfo)->deblock_mbs = deblock ? static_cast<int64_t>(st[7]) : 0;
+    if (xinfo->struct_size >= 40)
+      reinterpret_cast<vts_transcode_ext_info3 *>(xinfo)->early_skip_mbs = early_skip ? static_cast<int64_t>(st[8]) : 0;
   }
   return VTS_OK;
 }

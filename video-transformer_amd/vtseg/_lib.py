@@ -146,6 +146,19 @@ class TranscodeExtInfo2(C.Structure):
     _fields_ = [("base", TranscodeExtInfo), ("deblock_mbs", C.c_int64)]
 
 
+class TranscodeExt3(C.Structure):
+    """vts_transcode_ext3: begins with TranscodeExt2; passed to
+    vts_transcode_ex by pointer cast with base.base.struct_size = sizeof(TranscodeExt3)."""
+    _fields_ = [("base", TranscodeExt2), ("mvcost", C.c_int32), ("mv_lambda16", C.c_int32),
+                ("early_skip", C.c_int32), ("_pad", C.c_int32),
+                ("cmd_out", C.POINTER(C.c_uint32)), ("cmd_cap", C.c_int64)]
+
+
+class TranscodeExtInfo3(C.Structure):
+    """vts_transcode_ext_info3: begins with TranscodeExtInfo2; as TranscodeExt3."""
+    _fields_ = [("base", TranscodeExtInfo2), ("early_skip_mbs", C.c_int64), ("cmd_words", C.c_int64)]
+
+
 class ManifestArgs(C.Structure):
     _fields_ = [("video_id", C.c_char_p), ("segment_dir", C.c_char_p),
                 ("created_at", C.c_char_p), ("duration", C.c_double),

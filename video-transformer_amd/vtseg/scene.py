@@ -263,7 +263,8 @@ class VideoScorer:
                   max_mb_sad: int = 1536, keyint: int = 250, idr_at_cuts: bool = False,
                   cut_threshold: float = 0.0, qp: int = 28, intra: bool = False,
                   subpel: int = 0, deblock: bool = False,
-                  deblock_offsets: tuple[int, int] = (0, 0)) -> dict:
+                  deblock_offsets: tuple[int, int] = (0, 0), mvcost: bool = False,
+                  early_skip: bool = False, mv_lambda16: int = 0, want_commands: bool = False) -> dict:
         """360p upload transcode of this video into `out_path`
         (vts_transcode_ex): decode + score + area downscale +
         device H.264 encode with a quantised residual at `qp` (<= 0: none, the
@@ -276,8 +277,18 @@ class VideoScorer:
         inside each macroblock row's slice (disable_deblocking_filter_idc 2),
         with `deblock_offsets` = (slice_alpha_c0_offset_div2,
         slice_beta_offset_div2), each -6..6; needs `qp` > 0; off, every byte
-        is as before.  Returns the facts (with `intra`, `subpel` or `deblock`
-        also the encoder's `recon_hash`) and per-stage milliseconds."""
+        is as before.  `mvcost`: the motion search charges every candidate
+        vector its bits (16 SAD + lambda16 * bits(mvd) against the left
+        macroblock's vector in the previous picture; `mv_lambda16` > 0
+        replaces the table's lambda); `early_skip`: a macroblock whose
+        residual at vector (0, 0) quantises to nothing is P_Skip before any
+        search; both need `qp` > 0 and off, every byte is as before.
+        `want_commands`: the result also holds `commands`, the encoder's
+        final word per macroblock (vtseg.h) as a uint32 array (n_frames, mbh,
+        mbw).  Returns the facts (with `intra`, `subpel`, `deblock`, `mvcost`
+        or `early_skip` also the encoder's `recon_hash`) and per-stage
+        milliseconds; with one of the last four keywords also
+        `early_skip_mbs`."""
         prm = _lib.TranscodeParams()
         prm.height = height
         prm.search_range = search_range if search_range != 0 else -1
@@ -288,15 +299,35 @@ class VideoScorer:
         prm.qp = qp if qp > 0 else -1
         prm.intra = 1 if intra else 0
         info = _lib.TranscodeInfo()
-        ext = _lib.TranscodeExt2(_lib.TranscodeExt(C.sizeof(_lib.TranscodeExt2), subpel),
-                                 1 if deblock else 0, int(deblock_offsets[0]), int(deblock_offsets[1]))
-        xinfo2 = _lib.TranscodeExtInfo2(_lib.TranscodeExtInfo(C.sizeof(_lib.TranscodeExtInfo2)))
+        ext = _lib.TranscodeExt3(
+            _lib.TranscodeExt2(_lib.TranscodeExt(C.sizeof(_lib.TranscodeExt3), subpel),
+                               1 if deblock else 0, int(deblock_offsets[0]), int(deblock_offsets[1])),
+            1 if mvcost else 0, int(mv_lambda16), 1 if early_skip else 0)
+        xinfo3 = _lib.TranscodeExtInfo3(_lib.TranscodeExtInfo2(
+            _lib.TranscodeExtInfo(C.sizeof(_lib.TranscodeExtInfo3))))
+        xinfo2 = xinfo3.base
         xinfo = xinfo2.base
+        commands = None
+        if want_commands:
+            # the coded macroblock grid of the output: width as ffmpeg's scale=-2, both 16-aligned
+            w, h = int(self.info.width), int(self.info.height)
+            sw = (height * w + h) // (2 * h) * 2
+            mbw, mbh = (sw + 15) // 16, (height + 15) // 16
+            commands = np.zeros((int(self.info.n_frames), mbh, mbw), np.uint32)
+            ext.cmd_out = commands.ctypes.data_as(C.POINTER(C.c_uint32))
+            ext.cmd_cap = commands.size
         _lib.check(self._lib.vts_transcode_ex(self._ctx, str(out_path).encode(), C.byref(prm),
                                               C.cast(C.pointer(ext), C.POINTER(_lib.TranscodeExt)),
                                               C.byref(info),
-                                              C.cast(C.pointer(xinfo2), C.POINTER(_lib.TranscodeExtInfo))))
-        return {"width": info.width, "height": info.height, "n_frames": info.n_frames,
+                                              C.cast(C.pointer(xinfo3), C.POINTER(_lib.TranscodeExtInfo))))
+        extra = {}
+        if mvcost or early_skip or mv_lambda16 or want_commands:   # only with a new keyword
+            extra["early_skip_mbs"] = xinfo3.early_skip_mbs
+        if want_commands:
+            if xinfo3.cmd_words != commands.size:
+                raise RuntimeError(f"{xinfo3.cmd_words} command words, expected {commands.size}")
+            extra["commands"] = commands
+        return {**extra, "width": info.width, "height": info.height, "n_frames": info.n_frames,
                 "n_idr": info.n_idr, "pcm_mbs": info.pcm_mbs, "inter_mbs": info.inter_mbs,
                 "skip_mbs": info.skip_mbs, "intra_mbs": info.intra_mbs,
                 "subpel_mbs": xinfo.subpel_mbs, "qpel_mbs": xinfo.qpel_mbs,
