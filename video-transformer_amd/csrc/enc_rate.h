@@ -8,7 +8,8 @@
 //               macroblocks search in parallel (pred_of_cmd).
 //   early_skip: before the search, the residual of the prediction at vector
 //               (0, 0) goes through the transform and the quantiser; when no
-//               level survives the macroblock is P_Skip (all_zero_*).
+//               level survives the macroblock is P_Skip (all_zero_*: the
+//               quantiser's own answer, enc_residual.h).
 //
 // Nothing here depends on the device: the kernel and the harness call the
 // same functions.
@@ -16,6 +17,7 @@
 #include <cstdint>
 
 #include "enc_deblock.h"
+#include "enc_residual.h"
 
 namespace vts {
 namespace full {
@@ -76,57 +78,10 @@ VTS_HD VTS_INLINE Mv pred_of_cmd(uint32_t left_prev, int mx, int j) {
 }
 
 // ---- the early P_Skip probe: does any level of a residual survive the
-// quantiser (transcode.hip: fwd4, quant1)?
-VTS_HD VTS_INLINE int mf_of(int qp, int i, int j) {  // flat-matrix MF of position (i, j)
-  static constexpr int kMf[6][3] = {{13107, 5243, 8066}, {11916, 4660, 7490}, {10082, 4194, 6554},
-                                    {9362, 3647, 5825},  {8192, 3355, 5243},  {7282, 2893, 4559}};
-  return kMf[qp % 6][(!(i & 1) && !(j & 1)) ? 0 : ((i & 1) && (j & 1) ? 1 : 2)];
-}
-VTS_HD VTS_INLINE void fwd4(const int *x, int *w) {  // W = Cf X Cf^T, raster
-  int t[16];
-  for (int i = 0; i < 4; ++i) {
-    const int a = x[i * 4], b = x[i * 4 + 1], c = x[i * 4 + 2], d = x[i * 4 + 3];
-    t[i * 4] = a + b + c + d;
-    t[i * 4 + 1] = 2 * a + b - c - 2 * d;
-    t[i * 4 + 2] = a - b - c + d;
-    t[i * 4 + 3] = a - 2 * b + 2 * c - d;
-  }
-  for (int j = 0; j < 4; ++j) {
-    const int a = t[j], b = t[4 + j], c = t[8 + j], d = t[12 + j];
-    w[j] = a + b + c + d;
-    w[4 + j] = 2 * a + b - c - 2 * d;
-    w[8 + j] = a - b - c + d;
-    w[12 + j] = a - 2 * b + 2 * c - d;
-  }
-}
-// quant1(w, mf, qbits, f) != 0
-VTS_HD VTS_INLINE bool level_nz(int w, int mf, int qbits, int64_t f) {
-  return ((static_cast<int64_t>(w < 0 ? -w : w) * mf + f) >> qbits) != 0;
-}
-// A 4x4 residual block x (raster) at QP qp: true when every level is zero.
-// Luma (dc == nullptr): all 16; chroma: the 15 AC levels, and *dc receives
-// the DC coefficient for all_zero_chroma_dc.
-VTS_HD VTS_INLINE bool all_zero_block(const int *x, int qp, int *dc) {
-  int w[16];
-  fwd4(x, w);
-  bool nz = false;
-  const int qbits = 15 + qp / 6;
-  const int64_t f = (int64_t(1) << qbits) / 6;
-  for (int q = dc ? 1 : 0; q < 16; ++q) nz |= level_nz(w[q], mf_of(qp, q >> 2, q & 3), qbits, f);
-  if (dc) *dc = w[0];
-  return !nz;
-}
-// The four DC coefficients of a chroma plane: the 2x2 Hadamard, quantised at
-// qbits + 1 (with 2f)
-VTS_HD VTS_INLINE bool all_zero_chroma_dc(const int *c, int qpc) {
-  const int fd[4] = {c[0] + c[1] + c[2] + c[3], c[0] - c[1] + c[2] - c[3], c[0] + c[1] - c[2] - c[3],
-                     c[0] - c[1] - c[2] + c[3]};
-  bool nz = false;
-  const int qbits = 15 + qpc / 6;
-  const int64_t f = (int64_t(1) << qbits) / 6;
-  for (int k = 0; k < 4; ++k) nz |= level_nz(fd[k], mf_of(qpc, 0, 0), qbits + 1, 2 * f);
-  return !nz;
-}
+// quantiser?  Not restated here: enc_residual.h's code_block / code_chroma_dc
+// asked whether a level is left.
+using eres::all_zero_block;
+using eres::all_zero_chroma_dc;
 
 }  // namespace erate
 }  // namespace full

@@ -190,33 +190,8 @@ __device__ __constant__ static const uint8_t kCbpInterTab[48] = VTS_CBPP_DATA;
 __device__ __constant__ static const uint8_t kQpcTab[52] = VTS_QPC_DATA;
 __device__ __constant__ static const uint8_t kBlkXd[16] = {0, 1, 0, 1, 2, 3, 2, 3, 0, 1, 0, 1, 2, 3, 2, 3};
 __device__ __constant__ static const uint8_t kBlkYd[16] = {0, 0, 1, 1, 0, 0, 1, 1, 2, 2, 3, 3, 2, 2, 3, 3};
-__device__ __constant__ static const int kMf[6][3] = {{13107, 5243, 8066}, {11916, 4660, 7490}, {10082, 4194, 6554},
-                                                      {9362, 3647, 5825},  {8192, 3355, 5243},  {7282, 2893, 4559}};
-
-__device__ __forceinline__ int pos_class(int i, int j) { return (!(i & 1) && !(j & 1)) ? 0 : ((i & 1) && (j & 1) ? 1 : 2); }
-__device__ __forceinline__ void fwd4(const int *x, int *w) {  // W = Cf X Cf^T, raster
-  int t[16];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int a = x[i * 4], b = x[i * 4 + 1], c = x[i * 4 + 2], d = x[i * 4 + 3];
-    t[i * 4] = a + b + c + d;
-    t[i * 4 + 1] = 2 * a + b - c - 2 * d;
-    t[i * 4 + 2] = a - b - c + d;
-    t[i * 4 + 3] = a - 2 * b + 2 * c - d;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int a = t[j], b = t[4 + j], c = t[8 + j], d = t[12 + j];
-    w[j] = a + b + c + d;
-    w[4 + j] = 2 * a + b - c - 2 * d;
-    w[8 + j] = a - b - c + d;
-    w[12 + j] = a - 2 * b + 2 * c - d;
-  }
-}
-__device__ __forceinline__ int quant1(int w, int mf, int qbits, int64_t f) {
-  const int64_t z = min(static_cast<int64_t>(2047), (static_cast<int64_t>(abs(w)) * mf + f) >> qbits);
-  return w < 0 ? -static_cast<int>(z) : static_cast<int>(z);
-}
+namespace er = full::erate;
+namespace eres = full::eres;  // the transform, the quantiser and the reconstruction (enc_residual.h)
 
 // bits of residual_block_cavlc (7.3.5.3.2, 9.2) of levels lv[0, maxNum) in
 // scan order with nC (-1: chroma DC); nC < -1: an upper bound (coeff_token
@@ -250,24 +225,302 @@ __device__ __forceinline__ uint32_t u32_at(const uint8_t *lds_row, int off) {  /
   return __builtin_amdgcn_alignbyte(p[1], p[0], off & 3);  // byte shift
 }
 
-// One wave per macroblock: the reference window (16 + 2R)^2 and the source
-// block go to LDS; each lane takes candidates c = lane, lane + 64, ...;
-// (least luma SAD, candidate index) is a 64-bit min over the wave.
-#ifndef VTS_SEARCH_WAVES
-#define VTS_SEARCH_WAVES 0
-#endif
-#ifndef VTS_SEARCH_UV_LDS
-#define VTS_SEARCH_UV_LDS 0  // 1: chroma reference window staged in LDS (measured slower: 45 vs 37 ms)
-#endif
-#ifndef VTS_SEARCH_SRC_LDS
-#define VTS_SEARCH_SRC_LDS 1  // source rows read from LDS per use, rolled row loop: 47 VGPRs (vs 163), 33 vs 37 ms
-#endif
-#if VTS_SEARCH_WAVES
-#define VTS_SEARCH_OCC __attribute__((amdgpu_waves_per_eu(VTS_SEARCH_WAVES)))
-#else
-#define VTS_SEARCH_OCC
-#endif
-constexpr int kUvPitch = 8 + 2 * kMaxRange + 2;  // chroma window row pitch (Cb|Cr pairs)
+// enc_search, one wave per macroblock, in stages (each a function below, in
+// the kernel's order): the early P_Skip probe; the window load — the
+// reference window (16 + 2R)^2 and the source block go to LDS; the integer
+// search — each lane takes candidates, the least key is a 64-bit min over
+// the wave; the sub-sample refinement; the chroma prediction; and one of two
+// epilogues, without or with residual coding.
+
+// Window margins and row pitch by SP
+template <int SP>
+struct WinGeo {
+  static constexpr int LX = SP ? kSpLoX : 0, LY = SP ? kSpLoY : 0, HI = SP ? kSpHi : 0;
+  static constexpr int WP = SP ? kWinPitchSp : kWinPitch;
+  static constexpr int kBytes = (16 + 2 * kMaxRange + LY + HI) * WP;
+};
+
+// The key every pass orders its candidates by: make(sad, index, vx, vy) of
+// the candidate vector (vx, vy) in quarter samples, and the winner's index
+// and SAD back out of the reduced key.  RC: (16 SAD + lambda16 bits(v - p),
+// index) with the SAD riding below (enc_rate.h); else (SAD, index).
+template <bool RC>
+struct SearchKey {
+  int lam16 = 0;   // RC: 0 orders the candidates as the SAD alone
+  er::Mv p{0, 0};  // RC: the predictor guess, quarter samples
+  __device__ __forceinline__ uint64_t make(uint32_t sad, uint32_t index, int vx, int vy) const {
+    if constexpr (RC) return er::key_of(er::cost16(sad, lam16, vx, vy, p.x, p.y), index, sad);
+    else return (static_cast<uint64_t>(sad) << 32) | index;
+  }
+  __device__ __forceinline__ static uint32_t index(uint64_t key) { return RC ? er::key_index(key) : static_cast<uint32_t>(key); }
+  __device__ __forceinline__ static uint32_t sad(uint64_t key) { return RC ? er::key_sad(key) : static_cast<uint32_t>(key >> 32); }
+};
+
+// Integer candidates: index 0 is the centre, the others follow in raster
+// order of the (2R + 1)^2 square (position r)
+__device__ __forceinline__ int cand_of_raster(int r, int center) { return r == center ? 0 : (r < center ? r + 1 : r); }
+__device__ __forceinline__ int raster_of_cand(int c, int center) { return c == 0 ? center : (c - 1 < center ? c - 1 : c); }
+
+// Where a lane's samples of macroblock (mx, my) lie in a picture: 4 luma
+// samples of row lane / 4, and one Cb|Cr pair of chroma row lane / 8
+__device__ __forceinline__ int64_t luma_off(const SearchArgs &a, int lane, int mx, int my) {
+  return static_cast<int64_t>(my * 16 + (lane >> 2)) * a.cw + mx * 16 + 4 * (lane & 3);
+}
+__device__ __forceinline__ int64_t chroma_off(const SearchArgs &a, int lane, int mx, int my) {
+  return static_cast<int64_t>(a.cw) * a.ch + static_cast<int64_t>(my * 8 + (lane >> 3)) * a.cw + 2 * (mx * 8 + (lane & 7));
+}
+
+// The 4x4 residual blocks of a macroblock in the layout every residual stage
+// uses: lanes 0..15 the luma blocks (luma4x4BlkIdx), lanes 16..23 the chroma
+// blocks (plane pl, block k).  They take the prediction from y(row, bx), the 4
+// packed luma samples of row `row` in 4x4 column bx, and c(pl, i), sample i
+// (raster 8x8) of chroma plane pl.
+// Inter: the prediction (and the chroma source) in LDS, in the lanes' own
+// layout (luma_off / chroma_off)
+struct MbPred {
+  uint32_t py[64];
+  uint16_t pc[64], srcc[64];
+  __device__ __forceinline__ uint32_t y(int row, int bx) const { return py[row * 4 + bx]; }
+  __device__ __forceinline__ int c(int pl, int i) const { return eres::byte_of(pc[i], pl); }
+};
+// Intra16x16: both modes are constant along a row
+struct IntraPred {
+  const int *py, (*pc)[8];  // per row: luma [16], chroma [plane][8]
+  __device__ __forceinline__ uint32_t y(int row, int) const { return static_cast<uint32_t>(py[row]) * 0x01010101u; }
+  __device__ __forceinline__ int c(int pl, int i) const { return pc[pl][i >> 3]; }
+};
+struct ChromaLane {
+  int pl, k, bx, by;  // (bx, by): the block's first sample in the 8x8 plane
+};
+__device__ __forceinline__ ChromaLane chroma_lane(int lane) {
+  const int k = (lane - 16) & 3;
+  return {(lane - 16) >> 2, k, (k & 1) * 4, (k >> 1) * 4};
+}
+// lane < 16: the luma block's residual, and its reconstruction into recy
+template <class Pred>
+__device__ __forceinline__ void luma_block_diff(int lane, const uint32_t *srcy, const Pred &pred, int *x) {
+  const int bx = kBlkXd[lane], by = kBlkYd[lane];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) eres::diff_row4(srcy[(by * 4 + r) * 4 + bx], pred.y(by * 4 + r, bx), x + 4 * r);
+}
+template <class Pred>
+__device__ __forceinline__ void luma_block_recon(int lane, const Pred &pred, const int *res, uint32_t *recy) {
+  const int bx = kBlkXd[lane], by = kBlkYd[lane];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) recy[(by * 4 + r) * 4 + bx] = eres::recon_row4(pred.y(by * 4 + r, bx), res + 4 * r);
+}
+// lane 16..23: the chroma block's residual; its AC levels (true: one is
+// non-zero) with the DC coefficient to dcw[pl][k]; its reconstruction into
+// recc[pl] from the plane's DC levels dcl[pl] and (ac) those AC levels
+template <class Pred>
+__device__ __forceinline__ ChromaLane chroma_block_diff(int lane, const uint16_t *srcc, const Pred &pred, int *x) {
+  const ChromaLane cl = chroma_lane(lane);
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int i = (cl.by + r) * 8 + cl.bx + c;
+      x[r * 4 + c] = eres::byte_of(srcc[i], cl.pl) - pred.c(cl.pl, i);
+    }
+  return cl;
+}
+template <class Pred>
+__device__ __forceinline__ bool chroma_block_code(int lane, const uint16_t *srcc, const Pred &pred, int qpc, int *z, int *lv,
+                                                  int (*dcw)[4]) {
+  int x[16];
+  const ChromaLane cl = chroma_block_diff(lane, srcc, pred, x);
+  return eres::code_block<true>(x, qpc, z, lv, &dcw[cl.pl][cl.k]);
+}
+template <class Pred>
+__device__ __forceinline__ void chroma_block_recon(int lane, const Pred &pred, const int (*dcl)[4], const int *z, bool ac,
+                                                   int qpc, uint8_t (*recc)[64]) {
+  const ChromaLane cl = chroma_lane(lane);
+  int res[16];
+  eres::chroma_residual(dcl[cl.pl], cl.k, z, ac, qpc, res);
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int i = (cl.by + r) * 8 + cl.bx + c;
+      recc[cl.pl][i] = static_cast<uint8_t>(full::clip1(pred.c(cl.pl, i) + res[r * 4 + c]));
+    }
+}
+// chroma coded_block_pattern class: 2 with an AC level (ballot bits 16..23), 1 with a DC level only
+__device__ __forceinline__ int chroma_cbp(uint64_t nzm, const int (*dcl)[4]) {
+  bool dcnz = false;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) dcnz |= dcl[k >> 2][k & 3] != 0;
+  return ((nzm >> 16) & 0xffu) ? 2 : (dcnz ? 1 : 0);
+}
+// the chroma levels the slice writer codes: lanes 16..23 the AC blocks, 24 / 25 the planes' DC
+__device__ __forceinline__ void store_chroma_levels(int16_t *cp, int lane, const int *lv, const int (*dcl)[4]) {
+  if (lane >= 16 && lane < 24) {
+#pragma unroll
+    for (int q = 0; q < 15; ++q) cp[264 + 15 * (lane - 16) + q] = static_cast<int16_t>(lv[q]);
+  } else if (lane >= 24 && lane < 26) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) cp[256 + 4 * (lane - 24) + q] = static_cast<int16_t>(dcl[lane - 24][q]);
+  }
+}
+
+// ---- stage: early P_Skip.  The co-located prediction (vector (0, 0);
+// chroma 8.4.2.2.2 at (0, 0) is the co-located sample) goes through the
+// residual path's transform and quantiser; with no level left the macroblock
+// is decided before the window is loaded: true, and everything is written
+__device__ __forceinline__ bool probe_skip(const SearchArgs &a, int lane, int64_t mbi, int mx, int my, const uint8_t *src,
+                                           const uint8_t *ref, uint8_t *dst, const uint32_t *srcy, MbPred &P) {
+  __shared__ int edc[2][4];
+  const int64_t lo = luma_off(a, lane, mx, my), co = chroma_off(a, lane, mx, my);
+  const uint32_t py = *reinterpret_cast<const uint32_t *>(ref + lo);
+  const uint16_t pc = *reinterpret_cast<const uint16_t *>(ref + co);
+  P.py[lane] = py;
+  P.pc[lane] = pc;
+  P.srcc[lane] = *reinterpret_cast<const uint16_t *>(src + co);
+  __syncthreads();
+  const int qpc = kQpcTab[a.qp];
+  bool nz = false;
+  if (lane < 16) {
+    int x[16];
+    luma_block_diff(lane, srcy, P, x);
+    nz = !eres::all_zero_block(x, a.qp, nullptr);
+  } else if (lane < 24) {
+    int x[16], dc;  // a local: its address is known not to be null
+    const ChromaLane cl = chroma_block_diff(lane, P.srcc, P, x);
+    nz = !eres::all_zero_block(x, qpc, &dc);
+    edc[cl.pl][cl.k] = dc;
+  }
+  __syncthreads();
+  if (lane == 16 || lane == 17) nz |= !eres::all_zero_chroma_dc(edc[lane - 16], qpc);
+  if (__ballot(nz) != 0) return false;
+  // wave-uniform: P_Skip, the reconstruction is the prediction
+  *reinterpret_cast<uint32_t *>(dst + lo) = py;
+  *reinterpret_cast<uint16_t *>(dst + co) = pc;
+  if (lane == 0) {
+    a.cmd[mbi] = 0;
+    a.cbp[mbi] = 0;
+    atomicAdd(a.es_stat, 1ull);
+  }
+  return true;
+}
+
+// ---- stage: the window load.  Rows of W4 dwords (one division per lane,
+// then carry stepping); a dword wholly inside the picture row and aligned
+// (R % 4 == 0) is one load, else 4 edge-clamped byte loads
+template <int SP>
+__device__ __forceinline__ void load_window(const SearchArgs &a, int lane, const uint8_t *ref, int mx, int my, uint8_t *win) {
+  using G = WinGeo<SP>;
+  const int R = a.range, wsz = 16 + 2 * R + G::LX + G::HI, wrows = 16 + 2 * R + G::LY + G::HI;
+  const int x0 = mx * 16 - R - G::LX, y0 = my * 16 - R - G::LY;
+  const int W4 = (wsz + 3) >> 2, total = wrows * W4;
+  int r = lane / W4, cd = lane - r * W4;
+  const int dr = 64 / W4, dc = 64 - dr * W4;
+  for (int k = lane; k < total; k += 64) {
+    const uint8_t *rowp = ref + static_cast<int64_t>(min(max(y0 + r, 0), a.ch - 1)) * a.cw;
+    const int sx = x0 + 4 * cd;
+    uint32_t v;
+    if (sx >= 0 && sx + 3 < a.cw && !(sx & 3)) {
+      v = *reinterpret_cast<const uint32_t *>(rowp + sx);
+    } else {
+      v = 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v |= static_cast<uint32_t>(rowp[min(max(sx + q, 0), a.cw - 1)]) << (8 * q);
+    }
+    *reinterpret_cast<uint32_t *>(win + r * G::WP + 4 * cd) = v;
+    r += dr;
+    cd += dc;
+    if (cd >= W4) {
+      cd -= W4;
+      ++r;
+    }
+  }
+}
+
+// ---- stage: the integer search.  The window holds edge-clamped samples:
+// every candidate is valid.  The winner's offset and luma SAD.
+struct IntegerMv {
+  int dx, dy;
+  uint32_t sad;
+};
+template <int RT, int SP, bool RC>
+__device__ __forceinline__ IntegerMv integer_search(int lane, int R, const uint8_t *win, const uint32_t *srcy,
+                                                    const SearchKey<RC> &key) {
+  using G = WinGeo<SP>;
+  constexpr int LX = G::LX, LY = G::LY, WP = G::WP;
+  const int side = 2 * R + 1, ncand = side * side, center = R * side + R;
+  uint64_t best = ~0ull;
+  if constexpr (RT > 0) {
+    // Register blocking: lane (gx, gy) owns the NB candidates dx = gx - R,
+    // dy in [gy NB, gy NB + NB) - R.  Each of their 16 + NB - 1 window rows is
+    // read from LDS once (5 dwords, 4 byte-aligns) and SAD'd against every
+    // source row it meets (a broadcast LDS read per use): ~4.6x fewer LDS
+    // reads and ~2x fewer VALU instructions than one candidate per pass.
+    constexpr int SIDE = 2 * RT + 1, NG = 64 / SIDE, NB = (SIDE + NG - 1) / NG;
+    const int gx = lane % SIDE, gy = lane / SIDE, dy0 = gy * NB;
+    if (gy < NG && dy0 < SIDE) {
+      uint32_t acc[NB];
+#pragma unroll
+      for (int g = 0; g < NB; ++g) acc[g] = 0;
+      const int sh = gx & 3;
+      const uint32_t *wb = reinterpret_cast<const uint32_t *>(win + (dy0 + LY) * WP + LX + (gx & ~3));
+#pragma unroll 2
+      for (int w = 0; w < 16 + NB - 1; ++w) {
+        const uint32_t *wr = wb + w * (WP / 4);
+        const uint32_t w0 = wr[0], w1 = wr[1], w2 = wr[2], w3 = wr[3], w4 = wr[4];
+        const uint32_t r0 = __builtin_amdgcn_alignbyte(w1, w0, sh), r1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
+        const uint32_t r2 = __builtin_amdgcn_alignbyte(w3, w2, sh), r3 = __builtin_amdgcn_alignbyte(w4, w3, sh);
+#pragma unroll
+        for (int g = 0; g < NB; ++g) {
+          const int yy = w - g;
+          if (yy >= 0 && yy < 16) {
+            const uint4 q = reinterpret_cast<const uint4 *>(srcy)[yy];  // broadcast read
+            acc[g] = __builtin_amdgcn_sad_u8(r0, q.x, acc[g]);
+            acc[g] = __builtin_amdgcn_sad_u8(r1, q.y, acc[g]);
+            acc[g] = __builtin_amdgcn_sad_u8(r2, q.z, acc[g]);
+            acc[g] = __builtin_amdgcn_sad_u8(r3, q.w, acc[g]);
+          }
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < NB; ++g) {
+        const int dyi = dy0 + g;
+        if (dyi < SIDE) {
+          const uint64_t k = key.make(acc[g], cand_of_raster(dyi * SIDE + gx, center), 4 * (gx - RT), 4 * (dyi - RT));
+          best = k < best ? k : best;
+        }
+      }
+    }
+  } else {
+    for (int c = lane; c < ncand; c += 64) {
+      const int r = raster_of_cand(c, center);
+      const int dy = r / side - R, dx = r % side - R;
+      uint32_t s = 0;
+      const int ox = dx + R, sh = ox & 3;
+      // per row: the 5 dwords covering the 16 candidate bytes, 4 byte-aligns,
+      // the source row as one 16-byte broadcast read, 4 v_sad_u8
+      const uint32_t *wr = reinterpret_cast<const uint32_t *>(win + (dy + R + LY) * WP + LX + (ox & ~3));
+      const uint4 *sr = reinterpret_cast<const uint4 *>(srcy);
+#pragma unroll 4
+      for (int yy = 0; yy < 16; ++yy) {
+        const uint32_t *w = wr + yy * (WP / 4);
+        const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
+        const uint4 sv = sr[yy];
+        s = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, sh), sv.x, s);
+        s = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w2, w1, sh), sv.y, s);
+        s = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w3, w2, sh), sv.z, s);
+        s = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w4, w3, sh), sv.w, s);
+      }
+      const uint64_t k = key.make(s, c, 4 * dx, 4 * dy);
+      best = k < best ? k : best;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint64_t o = __shfl_xor(best, off);
+    best = o < best ? o : best;
+  }
+  const int r = raster_of_cand(static_cast<int>(key.index(best)), center);
+  return {r % side - R, r / side - R, key.sad(best)};
+}
 
 // The prediction of quarter-sample offset (qx, qy) from an integer position
 // (8.4.2.2.1, Table 8-12) in terms of the half-sample grid around it, where
@@ -294,251 +547,27 @@ __device__ __forceinline__ void sp_pair(int qx, int qy, int &XA, int &YA, int &X
 // rounding byte average of two dwords, no unpacking
 __device__ __forceinline__ uint32_t avg_u8x4(uint32_t p, uint32_t q) { return (p | q) - (((p ^ q) >> 1) & 0x7f7f7f7fu); }
 
-// RT: compile-time search range (register-blocked path), 0 = any range.
-// SP: sub-sample refinement around the integer winner, 0 none (the code is
-// the integer-only kernel's), 1 half samples, 2 half then quarter samples.
-// RC: the rate-aware decisions of enc_rate.h, each switched by a bit of
-// a.rate (wave-uniform); false: the code is the kernel's without them.  The
-// RC instances ask for the 5 waves/SIMD the others get by themselves (without
-// the hint the integer-only ones take 98 VGPRs, 4 waves; with it 92, no scratch).
-template <int RT, int SP, bool RC>
-__global__ void __launch_bounds__(64) VTS_SEARCH_OCC __attribute__((amdgpu_waves_per_eu(RC ? 5 : 1))) enc_search(SearchArgs a) {
-  constexpr int LX = SP ? kSpLoX : 0, LY = SP ? kSpLoY : 0, HI = SP ? kSpHi : 0;  // window margins
-  constexpr int WP = SP ? kWinPitchSp : kWinPitch;
-  static_assert(!(SP && VTS_SEARCH_UV_LDS), "the LDS chroma window is sized for integer vectors");
-  __shared__ __attribute__((aligned(16))) uint8_t win[(16 + 2 * kMaxRange + LY + HI) * WP];
-  __shared__ __attribute__((aligned(16))) uint32_t srcy[64];
-  __shared__ uint16_t winuv[kUvPitch * kUvPitch];
-  const int lane = threadIdx.x;
-  const int64_t e = blockIdx.x / a.nmb;
-  const int mb = static_cast<int>(blockIdx.x % a.nmb);
-  const int mx = mb % a.mbw, my = mb / a.mbw;
-  const int4 en = a.ent[e];
-  const uint8_t *src = a.small + static_cast<int64_t>(en.x) * a.stride;
-  const uint8_t *ref = en.y < 0 ? a.small + static_cast<int64_t>(en.x - 1) * a.stride
-                                : a.recon + static_cast<int64_t>(en.y) * a.stride;
-  uint8_t *dst = a.recon + static_cast<int64_t>(en.z) * a.stride;
-  const int R = a.range, side = 2 * R + 1, wsz = 16 + 2 * R + LX + HI, wrows = 16 + 2 * R + LY + HI;
-  const int x0 = mx * 16 - R - LX, y0 = my * 16 - R - LY;
-  // source luma: lane -> row lane / 4, 4 bytes
-  srcy[lane] = *reinterpret_cast<const uint32_t *>(src + static_cast<int64_t>(my * 16 + (lane >> 2)) * a.cw +
-                                                   mx * 16 + 4 * (lane & 3));
-  namespace er = full::erate;
-  int lam16 = 0;     // RC: 0 orders the candidates as the SAD alone
-  er::Mv pmv{0, 0};  // RC: the predictor guess, quarter samples
-  if constexpr (RC) {
-    const bool coded = a.qp >= 1 && a.max_sad >= 0;
-    if (coded && (a.rate & 2)) {
-      // ---- early P_Skip: the co-located prediction (vector (0, 0); chroma
-      // 8.4.2.2.2 at (0, 0) is the co-located sample) through the residual
-      // path's transform and quantiser; with no level left the macroblock is
-      // decided before the window is loaded
-      __shared__ uint32_t epy[64];
-      __shared__ uint16_t epc[64], esc[64];
-      __shared__ int edc[2][4];
-      const int64_t lo0 = static_cast<int64_t>(my * 16 + (lane >> 2)) * a.cw + mx * 16 + 4 * (lane & 3);
-      const int64_t co0 = static_cast<int64_t>(a.cw) * a.ch + static_cast<int64_t>(my * 8 + (lane >> 3)) * a.cw +
-                          2 * (mx * 8 + (lane & 7));
-      const uint32_t py0 = *reinterpret_cast<const uint32_t *>(ref + lo0);
-      const uint16_t pc0 = *reinterpret_cast<const uint16_t *>(ref + co0);
-      epy[lane] = py0;
-      epc[lane] = pc0;
-      esc[lane] = *reinterpret_cast<const uint16_t *>(src + co0);
-      __syncthreads();
-      const int qpc = kQpcTab[a.qp];
-      bool nz = false;
-      if (lane < 16) {
-        const int bx = kBlkXd[lane], by = kBlkYd[lane];
-        int x[16];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const uint32_t sv = srcy[(by * 4 + r) * 4 + bx], pv4 = epy[(by * 4 + r) * 4 + bx];
-#pragma unroll
-          for (int c = 0; c < 4; ++c) x[r * 4 + c] = static_cast<int>((sv >> (8 * c)) & 255) - static_cast<int>((pv4 >> (8 * c)) & 255);
-        }
-        nz = !er::all_zero_block(x, a.qp, nullptr);
-      } else if (lane < 24) {
-        const int pl = (lane - 16) >> 2, k = (lane - 16) & 3, bx = (k & 1) * 4, by = (k >> 1) * 4;
-        int x[16], dc;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const int i = (by + r) * 8 + bx + c;
-            x[r * 4 + c] = static_cast<int>((esc[i] >> (8 * pl)) & 255) - static_cast<int>((epc[i] >> (8 * pl)) & 255);
-          }
-        nz = !er::all_zero_block(x, qpc, &dc);
-        edc[pl][k] = dc;
-      }
-      __syncthreads();
-      if (lane == 16 || lane == 17) nz |= !er::all_zero_chroma_dc(edc[lane - 16], qpc);
-      if (__ballot(nz) == 0) {  // wave-uniform: P_Skip, the reconstruction is the prediction
-        *reinterpret_cast<uint32_t *>(dst + lo0) = py0;
-        *reinterpret_cast<uint16_t *>(dst + co0) = pc0;
-        if (lane == 0) {
-          a.cmd[e * a.nmb + mb] = 0;
-          a.cbp[e * a.nmb + mb] = 0;
-          atomicAdd(a.es_stat, 1ull);
-        }
-        return;
-      }
-    }
-    if (coded && (a.rate & 1)) {
-      lam16 = a.lambda16;
-      pmv = er::pred_of_cmd(mx > 0 && a.gop_pos > 1 ? a.cmd_prev[static_cast<int64_t>(en.w) * a.nmb + mb - 1] : 0u, mx,
-                           a.gop_pos);
-    }
-  }
-  {
-    // window rows of W4 dwords (one division per lane, then carry stepping);
-    // a dword wholly inside the picture row and aligned (R % 4 == 0) is one
-    // load, else 4 edge-clamped byte loads
-    const int W4 = (wsz + 3) >> 2, total = wrows * W4;
-    int r = lane / W4, cd = lane - r * W4;
-    const int dr = 64 / W4, dc = 64 - dr * W4;
-    for (int k = lane; k < total; k += 64) {
-      const uint8_t *rowp = ref + static_cast<int64_t>(min(max(y0 + r, 0), a.ch - 1)) * a.cw;
-      const int sx = x0 + 4 * cd;
-      uint32_t v;
-      if (sx >= 0 && sx + 3 < a.cw && !(sx & 3)) {
-        v = *reinterpret_cast<const uint32_t *>(rowp + sx);
-      } else {
-        v = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v |= static_cast<uint32_t>(rowp[min(max(sx + q, 0), a.cw - 1)]) << (8 * q);
-      }
-      *reinterpret_cast<uint32_t *>(win + r * WP + 4 * cd) = v;
-      r += dr;
-      cd += dc;
-      if (cd >= W4) {
-        cd -= W4;
-        ++r;
-      }
-    }
-  }
-  // edge-clamped chroma window (Cb|Cr pairs) covering every candidate's
-  // 8.4.2.2.2 taps: origin (mx 8, my 8) - ceil(R/2), 8 + R + 2 pairs square;
-  // loaded beside the luma window so the epilogue reads LDS, not HBM
-  const int cwn = 8 + R + 2, cox = mx * 8 - ((R + 1) >> 1), coy = my * 8 - ((R + 1) >> 1);
-  const int ccw = a.cw / 2, cch = a.ch / 2;
-  const uint8_t *ruv = ref + static_cast<int64_t>(a.cw) * a.ch;
-  for (int i = lane; VTS_SEARCH_UV_LDS && i < cwn * cwn; i += 64) {
-    const int yy = i / cwn, xx = i - yy * cwn;
-    const int sy = min(max(coy + yy, 0), cch - 1), sx = min(max(cox + xx, 0), ccw - 1);
-    winuv[yy * kUvPitch + xx] = *reinterpret_cast<const uint16_t *>(ruv + static_cast<int64_t>(sy) * a.cw + 2 * sx);
-  }
-  __syncthreads();
-  const int ncand = side * side, center = R * side + R;
-  uint64_t best = ~0ull;
-  if constexpr (RT > 0) {
-    // Register blocking: lane (gx, gy) owns the G candidates dx = gx - R,
-    // dy in [gy G, gy G + G) - R.  Each of their 16 + G - 1 window rows is
-    // read from LDS once (5 dwords, 4 byte-aligns) and SAD'd against every
-    // source row (held in VGPRs) it meets: ~4.6x fewer LDS reads and ~2x
-    // fewer VALU instructions than one candidate per pass.
-    constexpr int SIDE = 2 * RT + 1, NG = 64 / SIDE, G = (SIDE + NG - 1) / NG;
-    const int gx = lane % SIDE, gy = lane / SIDE, dy0 = gy * G;
-    if (gy < NG && dy0 < SIDE) {
-#if !VTS_SEARCH_SRC_LDS
-      uint32_t sv[64];
-#pragma unroll
-      for (int i = 0; i < 64; ++i) sv[i] = srcy[i];
-#endif
-      uint32_t acc[G];
-#pragma unroll
-      for (int g = 0; g < G; ++g) acc[g] = 0;
-      const int sh = gx & 3;
-      const uint32_t *wb = reinterpret_cast<const uint32_t *>(win + (dy0 + LY) * WP + LX + (gx & ~3));
-#if VTS_SEARCH_SRC_LDS
-#pragma unroll 2
-#else
-#pragma unroll
-#endif
-      for (int w = 0; w < 16 + G - 1; ++w) {
-        const uint32_t *wr = wb + w * (WP / 4);
-        const uint32_t w0 = wr[0], w1 = wr[1], w2 = wr[2], w3 = wr[3], w4 = wr[4];
-        const uint32_t r0 = __builtin_amdgcn_alignbyte(w1, w0, sh), r1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
-        const uint32_t r2 = __builtin_amdgcn_alignbyte(w3, w2, sh), r3 = __builtin_amdgcn_alignbyte(w4, w3, sh);
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          const int yy = w - g;
-          if (yy >= 0 && yy < 16) {
-#if VTS_SEARCH_SRC_LDS
-            const uint4 q = reinterpret_cast<const uint4 *>(srcy)[yy];  // broadcast read
-            const uint32_t s0 = q.x, s1 = q.y, s2 = q.z, s3 = q.w;
-#else
-            const uint32_t s0 = sv[4 * yy], s1 = sv[4 * yy + 1], s2 = sv[4 * yy + 2], s3 = sv[4 * yy + 3];
-#endif
-            acc[g] = __builtin_amdgcn_sad_u8(r0, s0, acc[g]);
-            acc[g] = __builtin_amdgcn_sad_u8(r1, s1, acc[g]);
-            acc[g] = __builtin_amdgcn_sad_u8(r2, s2, acc[g]);
-            acc[g] = __builtin_amdgcn_sad_u8(r3, s3, acc[g]);
-          }
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const int dyi = dy0 + g;
-        if (dyi < SIDE) {
-          const int r = dyi * SIDE + gx;
-          const int c = r == center ? 0 : (r < center ? r + 1 : r);
-          uint64_t key;
-          if constexpr (RC)
-            key = er::key_of(er::cost16(acc[g], lam16, 4 * (gx - RT), 4 * (dyi - RT), pmv.x, pmv.y), c, acc[g]);
-          else
-            key = (static_cast<uint64_t>(acc[g]) << 32) | static_cast<uint32_t>(c);
-          best = key < best ? key : best;
-        }
-      }
-    }
-  } else {
-    for (int c = lane; c < ncand; c += 64) {
-      const int r = c == 0 ? center : (c - 1 < center ? c - 1 : c);
-      const int dy = r / side - R, dx = r % side - R;
-      uint32_t s = 0;  // the window holds edge-clamped samples: every candidate is valid
-      const int ox = dx + R, sh = ox & 3;
-      // per row: the 5 dwords covering the 16 candidate bytes, 4 byte-aligns,
-      // the source row as one 16-byte broadcast read, 4 v_sad_u8
-      const uint32_t *wr = reinterpret_cast<const uint32_t *>(win + (dy + R + LY) * WP + LX + (ox & ~3));
-      const uint4 *sr = reinterpret_cast<const uint4 *>(srcy);
-  #pragma unroll 4
-      for (int yy = 0; yy < 16; ++yy) {
-        const uint32_t *w = wr + yy * (WP / 4);
-        const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
-        const uint4 sv = sr[yy];
-        s = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, sh), sv.x, s);
-        s = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w2, w1, sh), sv.y, s);
-        s = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w3, w2, sh), sv.z, s);
-        s = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w4, w3, sh), sv.w, s);
-      }
-      uint64_t key;
-      if constexpr (RC) key = er::key_of(er::cost16(s, lam16, 4 * dx, 4 * dy, pmv.x, pmv.y), c, s);
-      else key = (static_cast<uint64_t>(s) << 32) | static_cast<uint32_t>(c);
-      best = key < best ? key : best;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint64_t o = __shfl_xor(best, off);
-    best = o < best ? o : best;
-  }
-  const int c = static_cast<int>(RC ? er::key_index(best) : best & 0xffffffffu);
-  const int r = c == 0 ? center : (c - 1 < center ? c - 1 : c);
-  const int dy = r / side - R, dx = r % side - R;
-  // prediction and cost: lane -> 4 luma samples (row lane/4) and one chroma pair
+// ---- stage: the luma prediction at the winning vector, after (SP > 0) the
+// sub-sample refinement around the integer winner w: (cqx, cqy) receives the
+// refined vector in quarter samples from w; returned, the lane's 4 samples
+template <int SP, bool RC>
+__device__ __forceinline__ uint32_t refine_and_predict(int lane, int R, const uint8_t *win, const uint32_t *srcy,
+                                                       const IntegerMv &w, const SearchKey<RC> &key, int &cqx, int &cqy) {
+  using G = WinGeo<SP>;
+  constexpr int WP = G::WP;
   const int ly = lane >> 2, lx = 4 * (lane & 3);
-  int cqx = 0, cqy = 0;  // the refined vector, in quarter samples from the integer winner
-  uint32_t py;
-  if constexpr (SP > 0) {
-    // ---- sub-sample refinement.  With (x, y) relative to the integer
-    // winner's block, whose sample (0, 0) is win[oy][ox]: the half-sample
-    // planes b(x + 1/2, y), h(x, y + 1/2), j(x + 1/2, y + 1/2) for every
-    // position a candidate of either step reads, x, y in -1 .. 16 (the planes'
-    // index is x + 1, y + 1).  j is filtered from the unclipped horizontal
-    // intermediates of rows -3 .. 18, which also give b.
+  cqx = cqy = 0;
+  if constexpr (SP == 0) {
+    return u32_at(win + (w.dy + R + ly) * WP, w.dx + R + lx);
+  } else {
+    // With (x, y) relative to the integer winner's block, whose sample (0, 0)
+    // is win[oy][ox]: the half-sample planes b(x + 1/2, y), h(x, y + 1/2),
+    // j(x + 1/2, y + 1/2) for every position a candidate of either step reads,
+    // x, y in -1 .. 16 (the planes' index is x + 1, y + 1).  j is filtered from
+    // the unclipped horizontal intermediates of rows -3 .. 18, which also give b.
     __shared__ int16_t hmid[22 * 18];
     __shared__ __attribute__((aligned(16))) uint8_t pb[18 * kSpPitch], ph[17 * kSpPitch], pj[17 * kSpPitch];
-    const int ox = LX + R + dx, oy = LY + R + dy;
+    const int ox = G::LX + R + w.dx, oy = G::LY + R + w.dy;
     for (int i = lane; i < 22 * 17; i += 64) {  // x = xx - 1 in -1 .. 15, row yy - 3
       const int yy = i / 17, xx = i - yy * 17;
       const uint8_t *p = win + (oy - 3 + yy) * WP + ox + xx - 3;
@@ -560,43 +589,43 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC __attribute__((amdgpu_waves
       pj[yy * kSpPitch + xx] = static_cast<uint8_t>(full::clip1((t + 512) >> 10));
     }
     __syncthreads();
-    // the 4-aligned LDS row, byte offset and pitch at which block row 0 of
-    // the grid sample (X, Y), X, Y in -2 .. 2, starts
-    auto operand = [&](int X, int Y, const uint8_t *&row, int &off, int &pitch) {
+    // One of the two grid samples a prediction averages: the 4-aligned LDS
+    // row, byte offset and pitch at which its block row 0 starts
+    struct Operand {
+      const uint8_t *row;
+      int off, pitch;
+    };
+    auto operand = [&](int X, int Y) -> Operand {  // X, Y in -2 .. 2
       const int cx = X >> 1, cy = Y >> 1;
-      if (!((X | Y) & 1)) {
-        row = win + (oy + cy) * WP;
-        off = ox + cx;
-        pitch = WP;
-      } else {
-        row = ((X & 1) ? ((Y & 1) ? pj : pb) : ph) + (cy + 1) * kSpPitch;
-        off = cx + 1;
-        pitch = kSpPitch;
-      }
+      if (!((X | Y) & 1)) return {win + (oy + cy) * WP, ox + cx, WP};
+      return {((X & 1) ? ((Y & 1) ? pj : pb) : ph) + (cy + 1) * kSpPitch, cx + 1, kSpPitch};
+    };
+    auto operands = [&](int qx, int qy, Operand &A, Operand &B) {
+      int XA, YA, XB, YB;
+      sp_pair(qx, qy, XA, YA, XB, YB);
+      A = operand(XA, YA);
+      B = operand(XB, YB);
     };
     // Per step the 8 candidates around the centre go to 8 lanes each (2 rows
-    // a lane); the centre's SAD is known.  Key (SAD, index): centre 0, the
-    // others 1 .. 8 in raster order.
-    uint32_t csad = RC ? er::key_sad(best) : static_cast<uint32_t>(best >> 32);
+    // a lane); the centre's SAD is known.  Index: centre 0, the others 1 .. 8
+    // in raster order.
+    uint32_t csad = w.sad;
+    Operand A, B;
 #pragma unroll
     for (int step = 2; step >= (SP == 2 ? 1 : 2); step >>= 1) {
       const int k = (lane >> 3) + 1, pos = k - 1 < 4 ? k - 1 : k;
       const int qx = cqx + step * (pos % 3 - 1), qy = cqy + step * (pos / 3 - 1);
-      int XA, YA, XB, YB, offa, offb, pa, pb_;
-      const uint8_t *ra, *rb;
-      sp_pair(qx, qy, XA, YA, XB, YB);
-      operand(XA, YA, ra, offa, pa);
-      operand(XB, YB, rb, offb, pb_);
+      operands(qx, qy, A, B);
       uint32_t s = 0;
 #pragma unroll
       for (int rr = 0; rr < 2; ++rr) {
         const int row = 2 * (lane & 7) + rr;
-        const uint32_t *wa = reinterpret_cast<const uint32_t *>(ra + row * pa + (offa & ~3));
-        const uint32_t *wb = reinterpret_cast<const uint32_t *>(rb + row * pb_ + (offb & ~3));
+        const uint32_t *wa = reinterpret_cast<const uint32_t *>(A.row + row * A.pitch + (A.off & ~3));
+        const uint32_t *wb = reinterpret_cast<const uint32_t *>(B.row + row * B.pitch + (B.off & ~3));
         const uint4 sv = reinterpret_cast<const uint4 *>(srcy)[row];
         const uint32_t a0 = wa[0], a1 = wa[1], a2 = wa[2], a3 = wa[3], a4 = wa[4];
         const uint32_t b0 = wb[0], b1 = wb[1], b2 = wb[2], b3 = wb[3], b4 = wb[4];
-        const int sa = offa & 3, sb = offb & 3;
+        const int sa = A.off & 3, sb = B.off & 3;
         s = __builtin_amdgcn_sad_u8(avg_u8x4(__builtin_amdgcn_alignbyte(a1, a0, sa), __builtin_amdgcn_alignbyte(b1, b0, sb)), sv.x, s);
         s = __builtin_amdgcn_sad_u8(avg_u8x4(__builtin_amdgcn_alignbyte(a2, a1, sa), __builtin_amdgcn_alignbyte(b2, b1, sb)), sv.y, s);
         s = __builtin_amdgcn_sad_u8(avg_u8x4(__builtin_amdgcn_alignbyte(a3, a2, sa), __builtin_amdgcn_alignbyte(b3, b2, sb)), sv.z, s);
@@ -605,48 +634,39 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC __attribute__((amdgpu_waves
       s += __shfl_xor(s, 1);
       s += __shfl_xor(s, 2);
       s += __shfl_xor(s, 4);
-      uint64_t key, ckey;
-      if constexpr (RC) {  // the centre's bits are its own: recomputed, not the integer pass's
-        key = er::key_of(er::cost16(s, lam16, 4 * dx + qx, 4 * dy + qy, pmv.x, pmv.y), k, s);
-        ckey = er::key_of(er::cost16(csad, lam16, 4 * dx + cqx, 4 * dy + cqy, pmv.x, pmv.y), 0, csad);
-      } else {
-        key = (static_cast<uint64_t>(s) << 32) | static_cast<uint32_t>(k);
-        ckey = static_cast<uint64_t>(csad) << 32;
-      }
-      key = ckey < key ? ckey : key;
+      // the centre's key is its own at this vector, not the integer pass's
+      uint64_t best = key.make(s, k, 4 * w.dx + qx, 4 * w.dy + qy);
+      const uint64_t ckey = key.make(csad, 0, 4 * w.dx + cqx, 4 * w.dy + cqy);
+      best = ckey < best ? ckey : best;
 #pragma unroll
       for (int off = 32; off >= 8; off >>= 1) {
-        const uint64_t o = __shfl_xor(key, off);
-        key = o < key ? o : key;
+        const uint64_t o = __shfl_xor(best, off);
+        best = o < best ? o : best;
       }
-      const int kw = static_cast<int>(RC ? er::key_index(key) : key & 0xffffffffu);
+      const int kw = static_cast<int>(key.index(best));
       if (kw) {  // wave-uniform
         const int pw = kw - 1 < 4 ? kw - 1 : kw;
         cqx += step * (pw % 3 - 1);
         cqy += step * (pw / 3 - 1);
-        csad = RC ? er::key_sad(key) : static_cast<uint32_t>(key >> 32);
+        csad = key.sad(best);
       }
     }
-    int XA, YA, XB, YB, offa, offb, pa, pb_;
-    const uint8_t *ra, *rb;
-    sp_pair(cqx, cqy, XA, YA, XB, YB);
-    operand(XA, YA, ra, offa, pa);
-    operand(XB, YB, rb, offb, pb_);
-    py = avg_u8x4(u32_at(ra + ly * pa, offa + lx), u32_at(rb + ly * pb_, offb + lx));
-  } else {
-    py = u32_at(win + (dy + R + ly) * kWinPitch, dx + R + lx);
+    operands(cqx, cqy, A, B);
+    return avg_u8x4(u32_at(A.row + ly * A.pitch, A.off + lx), u32_at(B.row + ly * B.pitch, B.off + lx));
   }
-  const uint32_t sy4 = srcy[lane];
-  uint32_t cost = __builtin_amdgcn_sad_u8(py, sy4, 0);
-  const int ci = lane & 7, cj = lane >> 3;
-  const int mvx = 4 * dx + cqx, mvy = 4 * dy + cqy, fx = mvx & 7, fy = mvy & 7;
-  // window coordinates of taps (xi, yi) and (xi + 1, yi + 1); the window holds
-  // the clamped samples, so this equals the decoder's per-tap clamping
-#if VTS_SEARCH_UV_LDS
-  const int wx = ci + (mvx >> 3) + ((R + 1) >> 1), wy = cj + (mvy >> 3) + ((R + 1) >> 1);
-  const uint16_t A = winuv[wy * kUvPitch + wx], B = winuv[wy * kUvPitch + wx + 1];
-  const uint16_t Cc = winuv[(wy + 1) * kUvPitch + wx], D = winuv[(wy + 1) * kUvPitch + wx + 1];
-#else
+}
+
+// ---- stage: the chroma prediction (8.4.2.2.2) of the lane's Cb|Cr pair at
+// the quarter-sample luma vector (mvx, mvy); taps clamped to the picture as
+// the decoder clamps them
+struct ChromaPx {
+  int u, v;
+};
+__device__ __forceinline__ ChromaPx chroma_pred(const SearchArgs &a, int lane, const uint8_t *ref, int mx, int my, int mvx,
+                                                int mvy) {
+  const int ci = lane & 7, cj = lane >> 3, fx = mvx & 7, fy = mvy & 7;
+  const int ccw = a.cw / 2, cch = a.ch / 2;
+  const uint8_t *ruv = ref + static_cast<int64_t>(a.cw) * a.ch;
   const int xi = mx * 8 + ci + (mvx >> 3), yi = my * 8 + cj + (mvy >> 3);
   const int xa = min(max(xi, 0), ccw - 1), xb = min(max(xi + 1, 0), ccw - 1);
   const int ya = min(max(yi, 0), cch - 1), yb = min(max(yi + 1, 0), cch - 1);
@@ -654,113 +674,74 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC __attribute__((amdgpu_waves
   const uint16_t B = *reinterpret_cast<const uint16_t *>(ruv + static_cast<int64_t>(ya) * a.cw + 2 * xb);
   const uint16_t Cc = *reinterpret_cast<const uint16_t *>(ruv + static_cast<int64_t>(yb) * a.cw + 2 * xa);
   const uint16_t D = *reinterpret_cast<const uint16_t *>(ruv + static_cast<int64_t>(yb) * a.cw + 2 * xb);
-#endif
   const int wa = (8 - fx) * (8 - fy), wb = fx * (8 - fy), wc = (8 - fx) * fy, wd = fx * fy;
-  const int pu = (wa * (A & 255) + wb * (B & 255) + wc * (Cc & 255) + wd * (D & 255) + 32) >> 6;
-  const int pv = (wa * (A >> 8) + wb * (B >> 8) + wc * (Cc >> 8) + wd * (D >> 8) + 32) >> 6;
-  const int64_t co = static_cast<int64_t>(a.cw) * a.ch + static_cast<int64_t>(my * 8 + cj) * a.cw + 2 * (mx * 8 + ci);
-  const uint16_t suv = *reinterpret_cast<const uint16_t *>(src + co);
-  cost += static_cast<uint32_t>(abs(pu - (suv & 255)) + abs(pv - (suv >> 8)));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) cost += __shfl_xor(cost, off);
-  const int64_t lo = static_cast<int64_t>(my * 16 + ly) * a.cw + mx * 16 + lx;
-  const uint32_t mvw =
-      static_cast<uint32_t>(static_cast<uint16_t>(mvx)) | (static_cast<uint32_t>(static_cast<uint16_t>(mvy)) << 16);
-  if (a.qp < 1 || a.max_sad < 0) {  // no residual: inter within max_sad, else I_PCM
-    const bool inter = a.max_sad >= 0 && cost <= static_cast<uint32_t>(a.max_sad);
-    *reinterpret_cast<uint32_t *>(dst + lo) = inter ? py : sy4;
-    *reinterpret_cast<uint16_t *>(dst + co) = inter ? static_cast<uint16_t>(pu | (pv << 8)) : suv;
-    if (lane == 0) {
-      a.cmd[e * a.nmb + mb] = inter ? mvw : kPcmCmd;
-      if (a.cbp) a.cbp[e * a.nmb + mb] = 0;
-      if constexpr (SP > 0)
-        if (inter && ((mvx | mvy) & 3)) atomicAdd(&a.sp_stats[(mvx | mvy) & 1], 1ull);
-    }
-    return;
-  }
-  // ---- residual coding: lanes 0..15 the luma blocks (luma4x4BlkIdx), 16..23
-  // the chroma blocks (Cb 0..3, Cr 0..3), 24 / 25 the chroma DC blocks
-  __shared__ uint32_t predy[64], recy[64];
-  __shared__ uint16_t predc[64], srcc[64];
+  return {(wa * (A & 255) + wb * (B & 255) + wc * (Cc & 255) + wd * (D & 255) + 32) >> 6,
+          (wa * (A >> 8) + wb * (B >> 8) + wc * (Cc >> 8) + wd * (D >> 8) + 32) >> 6};
+}
+
+// What both epilogues decide between and where it goes: the lane's samples
+// of the prediction and of the source, and the macroblock's vector
+struct MbOut {
+  uint8_t *dst;
+  int64_t lo, co, mbi;  // luma_off, chroma_off, the macroblock's index in cmd / cbp / coef
+  uint32_t py, sy4;
+  uint16_t pc, suv;
+  uint32_t mvw;  // the vector's word, mvx | mvy << 16
+  int frac;      // mvx | mvy
+};
+// the macroblock's words: inter with its vector, else I_PCM
+template <int SP>
+__device__ __forceinline__ void write_words(const SearchArgs &a, const MbOut &o, bool inter, int cbp) {
+  a.cmd[o.mbi] = inter ? o.mvw : kPcmCmd;
+  if (a.cbp) a.cbp[o.mbi] = static_cast<uint8_t>(inter ? cbp : 0);
+  if constexpr (SP > 0)
+    if (inter && (o.frac & 3)) atomicAdd(&a.sp_stats[o.frac & 1], 1ull);
+}
+
+// ---- epilogue without residual coding: inter within max_sad, else I_PCM
+template <int SP>
+__device__ __forceinline__ void finish_plain(const SearchArgs &a, int lane, const MbOut &o, uint32_t cost) {
+  const bool inter = a.max_sad >= 0 && cost <= static_cast<uint32_t>(a.max_sad);
+  *reinterpret_cast<uint32_t *>(o.dst + o.lo) = inter ? o.py : o.sy4;
+  *reinterpret_cast<uint16_t *>(o.dst + o.co) = inter ? o.pc : o.suv;
+  if (lane == 0) write_words<SP>(a, o, inter, 0);
+}
+
+// ---- epilogue with residual coding: the blocks by lane as MbPred lays them
+// out, then lanes 16 / 17 the chroma DC levels and 24 / 25 their bits; inter
+// when the residual's CAVLC bound is within an I_PCM payload, else I_PCM
+template <int SP>
+__device__ __forceinline__ void finish_residual(const SearchArgs &a, int lane, const MbOut &o, const uint32_t *srcy, MbPred &P) {
+  __shared__ uint32_t recy[64];
   __shared__ uint8_t recc[2][64];
   __shared__ int dcw[2][4], dcl[2][4];
-  predy[lane] = py;
-  predc[lane] = static_cast<uint16_t>(pu | (pv << 8));
-  srcc[lane] = suv;
+  P.py[lane] = o.py;
+  P.pc[lane] = o.pc;
+  P.srcc[lane] = o.suv;
   __syncthreads();
   const int qp = a.qp, qpc = kQpcTab[qp];
-  const int qbits = 15 + qp / 6, cqb = 15 + qpc / 6;
-  const int64_t f = (int64_t(1) << qbits) / 6, cf = (int64_t(1) << cqb) / 6;
   int lv[16], z[16], nzb = 0, bits = 0;
 #pragma unroll
   for (int i = 0; i < 16; ++i) lv[i] = z[i] = 0;
   if (lane < 16) {
-    const int bx = kBlkXd[lane], by = kBlkYd[lane];
-    int x[16], w[16];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const uint32_t sv = srcy[(by * 4 + r) * 4 + bx], pv4 = predy[(by * 4 + r) * 4 + bx];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) x[r * 4 + c] = static_cast<int>((sv >> (8 * c)) & 255) - static_cast<int>((pv4 >> (8 * c)) & 255);
-    }
-    fwd4(x, w);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      z[q] = quant1(w[q], kMf[qp % 6][pos_class(q >> 2, q & 3)], qbits, f);
-      nzb |= z[q] != 0;
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) lv[q] = z[kZz4[q]];
-    int res[16];
+    int x[16], res[16];
+    luma_block_diff(lane, srcy, P, x);
+    nzb = eres::code_block<false>(x, qp, z, lv, nullptr);
     full::scale_idct4(z, qp, false, res);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const uint32_t pv4 = predy[(by * 4 + r) * 4 + bx];
-      uint32_t o = 0;
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        o |= static_cast<uint32_t>(min(max(static_cast<int>((pv4 >> (8 * c)) & 255) + res[r * 4 + c], 0), 255)) << (8 * c);
-      recy[(by * 4 + r) * 4 + bx] = o;
-    }
+    luma_block_recon(lane, P, res, recy);
     bits = cavlc_block<false>(nullptr, lv, 16, -2);
   } else if (lane < 24) {
-    const int pl = (lane - 16) >> 2, k = (lane - 16) & 3, bx = (k & 1) * 4, by = (k >> 1) * 4;
-    int x[16], w[16];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int i = (by + r) * 8 + bx + c;
-        x[r * 4 + c] = static_cast<int>((srcc[i] >> (8 * pl)) & 255) - static_cast<int>((predc[i] >> (8 * pl)) & 255);
-      }
-    fwd4(x, w);
-    dcw[pl][k] = w[0];
-#pragma unroll
-    for (int q = 1; q < 16; ++q) {
-      z[q] = quant1(w[q], kMf[qpc % 6][pos_class(q >> 2, q & 3)], cqb, cf);
-      nzb |= z[q] != 0;
-    }
-#pragma unroll
-    for (int q = 1; q < 16; ++q) lv[q - 1] = z[kZz4[q]];
+    nzb = chroma_block_code(lane, P.srcc, P, qpc, z, lv, dcw);
   }
   __syncthreads();
-  if (lane == 16 || lane == 17) {  // chroma DC: 2x2 Hadamard, quantised at (qbits + 1, 2f)
-    const int pl = lane - 16;
-    const int c0 = dcw[pl][0], c1 = dcw[pl][1], c2 = dcw[pl][2], c3 = dcw[pl][3];
-    const int fd[4] = {c0 + c1 + c2 + c3, c0 - c1 + c2 - c3, c0 + c1 - c2 - c3, c0 - c1 - c2 + c3};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) dcl[pl][k] = quant1(fd[k], kMf[qpc % 6][0], cqb + 1, 2 * cf);
-  }
+  if (lane == 16 || lane == 17) eres::code_chroma_dc(dcw[lane - 16], qpc, dcl[lane - 16]);
   __syncthreads();
   const uint64_t nzm = __ballot(nzb);
   int cbp = 0;
 #pragma unroll
   for (int q = 0; q < 4; ++q)
     if ((nzm >> (4 * q)) & 15u) cbp |= 1 << q;
-  bool dcnz = false;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) dcnz |= dcl[k >> 2][k & 3] != 0;
-  const int cc = ((nzm >> 16) & 0xffu) ? 2 : (dcnz ? 1 : 0);
+  const int cc = chroma_cbp(nzm, dcl);
   cbp |= cc << 4;
   int contrib = 0;  // this lane's share of the residual's CAVLC bound
   if (lane < 16) {
@@ -774,47 +755,76 @@ __global__ void __launch_bounds__(64) VTS_SEARCH_OCC __attribute__((amdgpu_waves
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) contrib += __shfl_xor(contrib, off);
   const bool inter = contrib <= kPcmBits;
-  if (lane >= 16 && lane < 24) {  // chroma reconstruction (8.5.11 DC, then 8.5.12)
-    const int pl = (lane - 16) >> 2, k = (lane - 16) & 3, bx = (k & 1) * 4, by = (k >> 1) * 4;
-    const int *c = dcl[pl];
-    const int F = k == 0 ? c[0] + c[1] + c[2] + c[3]
-                         : (k == 1 ? c[0] - c[1] + c[2] - c[3] : (k == 2 ? c[0] + c[1] - c[2] - c[3] : c[0] - c[1] - c[2] + c[3]));
-    int co[16], res[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) co[q] = cc == 2 ? z[q] : 0;
-    co[0] = ((F * full::level_scale(qpc % 6, 0, 0)) << (qpc / 6)) >> 5;
-    full::scale_idct4(co, qpc, true, res);
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int cx = 0; cx < 4; ++cx) {
-        const int i = (by + r) * 8 + bx + cx;
-        recc[pl][i] = static_cast<uint8_t>(min(max(static_cast<int>((predc[i] >> (8 * pl)) & 255) + res[r * 4 + cx], 0), 255));
-      }
-  }
+  if (lane >= 16 && lane < 24) chroma_block_recon(lane, P, dcl, z, cc == 2, qpc, recc);  // 8.5.11 DC, then 8.5.12
   __syncthreads();
-  *reinterpret_cast<uint32_t *>(dst + lo) = inter ? recy[lane] : sy4;
-  *reinterpret_cast<uint16_t *>(dst + co) =
-      inter ? static_cast<uint16_t>(recc[0][lane] | (recc[1][lane] << 8)) : suv;
+  *reinterpret_cast<uint32_t *>(o.dst + o.lo) = inter ? recy[lane] : o.sy4;
+  *reinterpret_cast<uint16_t *>(o.dst + o.co) = inter ? static_cast<uint16_t>(recc[0][lane] | (recc[1][lane] << 8)) : o.suv;
   if (inter && cbp) {  // the levels the slice writer codes
-    int16_t *cp = a.coef + (e * a.nmb + mb) * kCoefPerMb;
+    int16_t *cp = a.coef + o.mbi * kCoefPerMb;
     if (lane < 16) {
 #pragma unroll
       for (int q = 0; q < 16; ++q) cp[16 * lane + q] = static_cast<int16_t>(lv[q]);
-    } else if (lane < 24) {
-#pragma unroll
-      for (int q = 0; q < 15; ++q) cp[264 + 15 * (lane - 16) + q] = static_cast<int16_t>(lv[q]);
-    } else if (lane < 26) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) cp[256 + 4 * (lane - 24) + q] = static_cast<int16_t>(dcl[lane - 24][q]);
+    }
+    store_chroma_levels(cp, lane, lv, dcl);
+  }
+  if (lane == 0) write_words<SP>(a, o, inter, cbp);
+}
+
+// RT: compile-time search range (register-blocked path), 0 = any range.
+// SP: sub-sample refinement around the integer winner, 0 none (the code is
+// the integer-only kernel's), 1 half samples, 2 half then quarter samples.
+// RC: the rate-aware decisions of enc_rate.h, each switched by a bit of
+// a.rate (wave-uniform); false: the code is the kernel's without them.  Every
+// instance asks for 5 waves/SIMD: they fit (88 .. 90 VGPRs, no scratch), but
+// left to itself the register allocator settles at 98 .. 102 and 4 waves.
+template <int RT, int SP, bool RC>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) enc_search(SearchArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t win[WinGeo<SP>::kBytes];
+  __shared__ __attribute__((aligned(16))) uint32_t srcy[64];
+  __shared__ MbPred P;
+  const int lane = threadIdx.x;
+  const int64_t e = blockIdx.x / a.nmb;
+  const int mb = static_cast<int>(blockIdx.x % a.nmb);
+  const int mx = mb % a.mbw, my = mb / a.mbw;
+  const int4 en = a.ent[e];
+  const uint8_t *src = a.small + static_cast<int64_t>(en.x) * a.stride;
+  const uint8_t *ref = en.y < 0 ? a.small + static_cast<int64_t>(en.x - 1) * a.stride
+                                : a.recon + static_cast<int64_t>(en.y) * a.stride;
+  MbOut o;
+  o.dst = a.recon + static_cast<int64_t>(en.z) * a.stride;
+  o.mbi = e * a.nmb + mb;
+  srcy[lane] = *reinterpret_cast<const uint32_t *>(src + luma_off(a, lane, mx, my));
+  SearchKey<RC> key;
+  if constexpr (RC) {
+    const bool coded = a.qp >= 1 && a.max_sad >= 0;
+    if (coded && (a.rate & 2) && probe_skip(a, lane, o.mbi, mx, my, src, ref, o.dst, srcy, P)) return;
+    if (coded && (a.rate & 1)) {
+      key.lam16 = a.lambda16;
+      key.p = er::pred_of_cmd(mx > 0 && a.gop_pos > 1 ? a.cmd_prev[static_cast<int64_t>(en.w) * a.nmb + mb - 1] : 0u, mx,
+                              a.gop_pos);
     }
   }
-  if (lane == 0) {
-    a.cmd[e * a.nmb + mb] = inter ? mvw : kPcmCmd;
-    a.cbp[e * a.nmb + mb] = static_cast<uint8_t>(inter ? cbp : 0);
-    if constexpr (SP > 0)
-      if (inter && ((mvx | mvy) & 3)) atomicAdd(&a.sp_stats[(mvx | mvy) & 1], 1ull);
-  }
+  load_window<SP>(a, lane, ref, mx, my, win);
+  __syncthreads();
+  const IntegerMv w = integer_search<RT, SP, RC>(lane, a.range, win, srcy, key);
+  int cqx, cqy;
+  o.py = refine_and_predict<SP, RC>(lane, a.range, win, srcy, w, key, cqx, cqy);
+  const int mvx = 4 * w.dx + cqx, mvy = 4 * w.dy + cqy;
+  o.mvw = static_cast<uint32_t>(static_cast<uint16_t>(mvx)) | (static_cast<uint32_t>(static_cast<uint16_t>(mvy)) << 16);
+  o.frac = mvx | mvy;
+  // the macroblock's cost at that vector: luma and chroma SAD
+  o.sy4 = srcy[lane];
+  uint32_t cost = __builtin_amdgcn_sad_u8(o.py, o.sy4, 0);
+  const ChromaPx pc = chroma_pred(a, lane, ref, mx, my, mvx, mvy);
+  o.pc = static_cast<uint16_t>(pc.u | (pc.v << 8));
+  o.co = chroma_off(a, lane, mx, my);
+  o.suv = *reinterpret_cast<const uint16_t *>(src + o.co);
+  cost += static_cast<uint32_t>(abs(pc.u - (o.suv & 255)) + abs(pc.v - (o.suv >> 8)));
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) cost += __shfl_xor(cost, off);
+  o.lo = luma_off(a, lane, mx, my);
+  if (a.qp < 1 || a.max_sad < 0) finish_plain<SP>(a, lane, o, cost);
+  else finish_residual<SP>(a, lane, o, srcy, P);
 }
 
 // ------------------------------------------------------ slice writer
@@ -1024,8 +1034,6 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
   uint8_t *dst = a.recon + static_cast<int64_t>(en.z) * a.stride;
   const int64_t mb0 = (static_cast<int64_t>(e) * a.mbh + my) * a.mbw;
   const int qp = a.qp, qpc = kQpcTab[qp];
-  const int qbits = 15 + qp / 6, cqb = 15 + qpc / 6;
-  const int64_t f = (int64_t(1) << qbits) / 6, cf = (int64_t(1) << cqb) / 6;
   const int ly = lane >> 2, lx = 4 * (lane & 3), ci = lane & 7, cj = lane >> 3;
   if (lane < 4) lnz[lane] = -1;
   if (lane < 4) lnzc[lane >> 1][lane & 1] = -1;
@@ -1114,75 +1122,27 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) lv[i] = z[i] = 0;
     const int bxl = lane < 16 ? kBlkXd[lane] : 0, byl = lane < 16 ? kBlkYd[lane] : 0;
+    const IntraPred pred{pred_y, pred_c};
     if (lane < 16) {
-      int x[16], w[16];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const uint32_t sv = srcy[(byl * 4 + r) * 4 + bxl];
-        const int p = pred_y[byl * 4 + r];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) x[r * 4 + c] = static_cast<int>((sv >> (8 * c)) & 255) - p;
-      }
-      fwd4(x, w);
-      ydw[byl * 4 + bxl] = w[0];
-#pragma unroll
-      for (int q = 1; q < 16; ++q) {
-        z[q] = quant1(w[q], kMf[qp % 6][pos_class(q >> 2, q & 3)], qbits, f);
-        nzb |= z[q] != 0;
-      }
-#pragma unroll
-      for (int q = 1; q < 16; ++q) lv[q - 1] = z[kZz4[q]];
+      int x[16];
+      luma_block_diff(lane, srcy, pred, x);
+      nzb = eres::code_block<true>(x, qp, z, lv, &ydw[byl * 4 + bxl]);
     } else if (lane < 24) {
-      const int pl = (lane - 16) >> 2, k = (lane - 16) & 3, bx = (k & 1) * 4, by = (k >> 1) * 4;
-      int x[16], w[16];
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          x[r * 4 + c] = static_cast<int>((srcc[(by + r) * 8 + bx + c] >> (8 * pl)) & 255) - pred_c[pl][by + r];
-      fwd4(x, w);
-      dcw[pl][k] = w[0];
-#pragma unroll
-      for (int q = 1; q < 16; ++q) {
-        z[q] = quant1(w[q], kMf[qpc % 6][pos_class(q >> 2, q & 3)], cqb, cf);
-        nzb |= z[q] != 0;
-      }
-#pragma unroll
-      for (int q = 1; q < 16; ++q) lv[q - 1] = z[kZz4[q]];
+      nzb = chroma_block_code(lane, srcc, pred, qpc, z, lv, dcw);
     }
     __syncthreads();
     if (lane == 24) {
-      // luma DC: (H D H) / 2 of the 16 DC terms (D by block row, column),
-      // quantised at (qbits + 1, 2f); then the decoder's 8.5.10 for the
-      // reconstruction
-      int t[16], lev[16], sc[16];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int a0 = ydw[i * 4], a1 = ydw[i * 4 + 1], a2 = ydw[i * 4 + 2], a3 = ydw[i * 4 + 3];
-        t[i * 4] = a0 + a1 + a2 + a3;
-        t[i * 4 + 1] = a0 + a1 - a2 - a3;
-        t[i * 4 + 2] = a0 - a1 - a2 + a3;
-        t[i * 4 + 3] = a0 - a1 + a2 - a3;
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int a0 = t[j], a1 = t[4 + j], a2 = t[8 + j], a3 = t[12 + j];
-        const int h[4] = {a0 + a1 + a2 + a3, a0 + a1 - a2 - a3, a0 - a1 - a2 + a3, a0 - a1 + a2 - a3};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) lev[i * 4 + j] = quant1((h[i] + 1) >> 1, kMf[qp % 6][0], qbits + 1, 2 * f);
-      }
+      // luma DC: its levels, then the decoder's 8.5.10 for the reconstruction
+      int lev[16], sc[16];
+      eres::code_i16_dc(ydw, qp, lev);
       full::i16_dc_inverse(lev, qp, full::level_scale(qp % 6, 0, 0), sc);
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
         ydl[k] = lev[k];
         yds[k] = sc[k];
       }
-    } else if (lane == 16 || lane == 17) {  // chroma DC: 2x2 Hadamard, quantised at (qbits + 1, 2f)
-      const int pl = lane - 16;
-      const int c0 = dcw[pl][0], c1 = dcw[pl][1], c2 = dcw[pl][2], c3 = dcw[pl][3];
-      const int fd[4] = {c0 + c1 + c2 + c3, c0 - c1 + c2 - c3, c0 + c1 - c2 - c3, c0 - c1 - c2 + c3};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) dcl[pl][k] = quant1(fd[k], kMf[qpc % 6][0], cqb + 1, 2 * cf);
+    } else if (lane == 16 || lane == 17) {
+      eres::code_chroma_dc(dcw[lane - 16], qpc, dcl[lane - 16]);
     }
     const uint64_t nzm = __ballot(nzb);
     const bool ac = (nzm & 0xffffu) != 0;  // Intra16x16: the luma coded_block_pattern is 0 or 15
@@ -1190,10 +1150,7 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
 #pragma unroll
     for (int q = 0; q < 15; ++q) tc += lv[q] != 0;
     __syncthreads();
-    bool dcnz = false;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) dcnz |= dcl[k >> 2][k & 3] != 0;
-    const int cc = ((nzm >> 16) & 0xffu) ? 2 : (dcnz ? 1 : 0);
+    const int cc = chroma_cbp(nzm, dcl);
     const int cbp = (ac ? 15 : 0) | (cc << 4);
     if (lane < 16) tcy[byl * 4 + bxl] = ac ? tc : 0;
     else if (lane < 24) tcc[(lane - 16) >> 2][(lane - 16) & 3] = cc == 2 ? tc : 0;
@@ -1233,50 +1190,22 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
     if (intra) {
       // ---- reconstruction through the decoder's inverse path
       if (lane < 16) {
-        int cfs[16], res[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) cfs[q] = ac ? z[q] : 0;
-        cfs[0] = yds[byl * 4 + bxl];
-        full::scale_idct4(cfs, qp, true, res);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int p = pred_y[byl * 4 + r];
-          uint32_t o = 0;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) o |= static_cast<uint32_t>(min(max(p + res[r * 4 + c], 0), 255)) << (8 * c);
-          recy[(byl * 4 + r) * 4 + bxl] = o;
-        }
+        int res[16];
+        eres::residual_dc_done(yds[byl * 4 + bxl], z, ac, qp, res);
+        luma_block_recon(lane, pred, res, recy);
       } else if (lane < 24) {  // chroma (8.5.11 DC, then 8.5.12)
-        const int pl = (lane - 16) >> 2, k = (lane - 16) & 3, bx = (k & 1) * 4, by = (k >> 1) * 4;
-        const int *c = dcl[pl];
-        const int F = k == 0 ? c[0] + c[1] + c[2] + c[3]
-                             : (k == 1 ? c[0] - c[1] + c[2] - c[3] : (k == 2 ? c[0] + c[1] - c[2] - c[3] : c[0] - c[1] - c[2] + c[3]));
-        int cfs[16], res[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) cfs[q] = cc == 2 ? z[q] : 0;
-        cfs[0] = ((F * full::level_scale(qpc % 6, 0, 0)) << (qpc / 6)) >> 5;
-        full::scale_idct4(cfs, qpc, true, res);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int cx = 0; cx < 4; ++cx)
-            recc[pl][(by + r) * 8 + bx + cx] = static_cast<uint8_t>(min(max(pred_c[pl][by + r] + res[r * 4 + cx], 0), 255));
+        chroma_block_recon(lane, pred, dcl, z, cc == 2, qpc, recc);
       }
       // the levels the slice writer codes: luma DC [0, 16), AC block b at 16 + 15 b, chroma as enc_search
       int16_t *cp = a.coef + (mb0 + mx) * kCoefPerMb;
       if (lane < 16) {
 #pragma unroll
         for (int q = 0; q < 15; ++q) cp[16 + 15 * lane + q] = static_cast<int16_t>(lv[q]);
-      } else if (lane < 24) {
-#pragma unroll
-        for (int q = 0; q < 15; ++q) cp[264 + 15 * (lane - 16) + q] = static_cast<int16_t>(lv[q]);
-      } else if (lane < 26) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cp[256 + 4 * (lane - 24) + q] = static_cast<int16_t>(dcl[lane - 24][q]);
       } else if (lane == 26) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) cp[q] = static_cast<int16_t>(dlv[q]);
       }
+      store_chroma_levels(cp, lane, lv, dcl);
     }
     __syncthreads();
     if (intra || a.all) {
@@ -1971,6 +1900,116 @@ void launch_search(int R, dim3 grid, hipStream_t s, const SearchArgs &sa) {
     default: hipLaunchKernelGGL((enc_search<0, SP, RC>), grid, dim3(64), 0, s, sa); break;
   }
 }
+
+// What a vts_transcode_ex call asks for, defaults applied and checked.
+struct TranscodeOpts {
+  int subpel = 0, deblock = 0, dbk_alpha = 0, dbk_beta = 0;
+  int mvcost = 0, mv_lambda16 = 0, early_skip = 0;
+  uint32_t *cmd_out = nullptr;
+  int64_t cmd_cap = 0;
+  int rate = 0;         // SearchArgs.rate: mvcost | early_skip << 1
+  int sh = 0, R = 0, T = 0, qp = 0, keyint = 0;  // output height, search range, max SAD, residual QP (0: none)
+  bool intra = false, idr_at_cuts = false;
+  bool hashed = false;  // recon_hash is computed
+  float thr = 0;        // scene-cut threshold of idr_at_cuts
+};
+// The size-tagged structs (only the prefix known here is read) and the
+// parameters into `o`; VTS_OK or the error
+int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_transcode_ext *ext,
+              const vts_transcode_ext_info *xinfo, TranscodeOpts *out) {
+  TranscodeOpts &o = *out;
+  if (ext) {
+    if (ext->struct_size < 8) return fail(VTS_E_INVALID, "vts_transcode_ext.struct_size %u < 8", ext->struct_size);
+    o.subpel = ext->subpel;
+    if (o.subpel < 0 || o.subpel > 2) return fail(VTS_E_INVALID, "subpel %d: 0, 1 or 2", o.subpel);
+    // vts_transcode_ext2: each field only when the caller's struct holds it
+    const vts_transcode_ext2 *x2 = reinterpret_cast<const vts_transcode_ext2 *>(ext);
+    if (ext->struct_size >= 12) o.deblock = x2->deblock;
+    if (ext->struct_size >= 16) o.dbk_alpha = x2->deblock_alpha;
+    if (ext->struct_size >= 20) o.dbk_beta = x2->deblock_beta;
+    if (o.deblock != 0 && o.deblock != 1) return fail(VTS_E_INVALID, "deblock %d: 0 or 1", o.deblock);
+    if (o.dbk_alpha < -6 || o.dbk_alpha > 6) return fail(VTS_E_INVALID, "deblock_alpha %d: -6 .. 6", o.dbk_alpha);
+    if (o.dbk_beta < -6 || o.dbk_beta > 6) return fail(VTS_E_INVALID, "deblock_beta %d: -6 .. 6", o.dbk_beta);
+    if (!o.deblock && o.dbk_alpha) return fail(VTS_E_INVALID, "deblock_alpha %d without deblock = 1", o.dbk_alpha);
+    if (!o.deblock && o.dbk_beta) return fail(VTS_E_INVALID, "deblock_beta %d without deblock = 1", o.dbk_beta);
+    // vts_transcode_ext3, the same way
+    const vts_transcode_ext3 *x3 = reinterpret_cast<const vts_transcode_ext3 *>(ext);
+    if (ext->struct_size >= 28) o.mvcost = x3->mvcost;
+    if (ext->struct_size >= 32) o.mv_lambda16 = x3->mv_lambda16;
+    if (ext->struct_size >= 36) o.early_skip = x3->early_skip;
+    if (ext->struct_size >= 48) o.cmd_out = x3->cmd_out;
+    if (ext->struct_size >= 56) o.cmd_cap = x3->cmd_cap;
+    if (o.mvcost != 0 && o.mvcost != 1) return fail(VTS_E_INVALID, "mvcost %d: 0 or 1", o.mvcost);
+    if (o.early_skip != 0 && o.early_skip != 1) return fail(VTS_E_INVALID, "early_skip %d: 0 or 1", o.early_skip);
+    if (o.mv_lambda16 < 0 || o.mv_lambda16 > 4096) return fail(VTS_E_INVALID, "mv_lambda16 %d: 0 .. 4096", o.mv_lambda16);
+    if (!o.mvcost && o.mv_lambda16) return fail(VTS_E_INVALID, "mv_lambda16 %d without mvcost = 1", o.mv_lambda16);
+  }
+  o.rate = o.mvcost | (o.early_skip << 1);
+  if (xinfo && xinfo->struct_size < 8)
+    return fail(VTS_E_INVALID, "vts_transcode_ext_info.struct_size %u < 8", xinfo->struct_size);
+  vts_transcode_params p{};
+  if (pin) p = *pin;
+  o.sh = p.height > 0 ? p.height : 360;
+  o.R = p.search_range == 0 ? 8 : std::max(0, p.search_range);
+  o.T = p.max_mb_sad == 0 ? 1536 : p.max_mb_sad;
+  o.qp = p.qp == 0 ? 28 : (p.qp < 0 ? 0 : p.qp);  // 0: no residual coding (the round-2 encoder)
+  if (o.qp > 51) return fail(VTS_E_INVALID, "qp %d > 51", o.qp);
+  if (p.intra != 0 && p.intra != 1) return fail(VTS_E_INVALID, "intra %d: 0 or 1", p.intra);
+  o.intra = p.intra == 1;
+  o.hashed = o.intra || o.subpel != 0 || o.deblock || o.rate;
+  if (o.intra && o.qp < 1) return fail(VTS_E_INVALID, "intra = 1 needs residual coding (qp >= 0)");
+  if (o.deblock && o.qp < 1) return fail(VTS_E_INVALID, "deblock = 1 needs residual coding (qp >= 0)");
+  if (o.mvcost && o.qp < 1) return fail(VTS_E_INVALID, "mvcost = 1 needs residual coding (qp >= 0)");
+  if (o.early_skip && o.qp < 1) return fail(VTS_E_INVALID, "early_skip = 1 needs residual coding (qp >= 0)");
+  o.keyint = p.keyint > 0 ? p.keyint : 250;
+  o.idr_at_cuts = p.idr_at_cuts != 0;
+  o.thr = p.cut_threshold > 0 ? p.cut_threshold : c->params.cut_threshold;
+  if ((o.sh & 1) || o.sh < 16 || o.sh > c->height)
+    return fail(VTS_E_INVALID, "output height %d: even, 16 .. source height %d", o.sh, c->height);
+  if (o.R > kMaxRange) return fail(VTS_E_INVALID, "search_range %d > %d", o.R, kMaxRange);
+  return VTS_OK;
+}
+
+// The GOPs (IDR at frame 0, at cuts, every keyint frames) and their levels:
+// level j holds position j of every GOP that long, as search entries (frame,
+// ref slot, dst slot, w) and write entries (frame, j, idr parity, index within
+// the level); level j's entries are [lvl_off[j], lvl_off[j + 1]).
+struct GopPlan {
+  std::vector<int64_t> gop_start;
+  int64_t ngop = 0, maxlen = 0;  // GOPs; frames of the longest = levels
+  std::vector<int4> sent, went;
+  std::vector<int64_t> lvl_off;
+};
+GopPlan plan_gops(int64_t n, const std::vector<float> &scores, const TranscodeOpts &o) {
+  GopPlan g;
+  for (int64_t f = 0; f < n; ++f)
+    if (f == 0 || (o.idr_at_cuts && scores[f] > o.thr) || f - g.gop_start.back() >= o.keyint) g.gop_start.push_back(f);
+  g.ngop = static_cast<int64_t>(g.gop_start.size());
+  std::vector<int64_t> gop_len(static_cast<size_t>(g.ngop));
+  for (int64_t k = 0; k < g.ngop; ++k) {
+    gop_len[k] = (k + 1 < g.ngop ? g.gop_start[k + 1] : n) - g.gop_start[k];
+    g.maxlen = std::max(g.maxlen, gop_len[k]);
+  }
+  g.lvl_off.assign(static_cast<size_t>(g.maxlen) + 1, 0);
+  // with a rate-aware search, w of a search entry: the GOP's entry index in the previous level (GOPs of
+  // different lengths: the indices differ between levels), where enc_search finds the previous picture's words
+  std::vector<int> lvl_idx(static_cast<size_t>(g.ngop), 0);
+  for (int64_t j = 0; j < g.maxlen; ++j) {
+    g.lvl_off[j] = static_cast<int64_t>(g.went.size());
+    for (int64_t k = 0; k < g.ngop; ++k) {
+      if (gop_len[k] <= j) continue;
+      const int f = static_cast<int>(g.gop_start[k] + j);
+      const int prev_idx = o.rate ? lvl_idx[k] : 0;
+      lvl_idx[k] = static_cast<int>(static_cast<int64_t>(g.went.size()) - g.lvl_off[j]);
+      // level 1 predicts from the IDR picture: its source (all I_PCM) or, with intra, its reconstruction
+      g.sent.push_back(make_int4(f, j == 1 && !o.intra ? -1 : static_cast<int>(2 * k + ((j - 1) & 1)),
+                                 static_cast<int>(2 * k + (j & 1)), prev_idx));
+      g.went.push_back(make_int4(f, static_cast<int>(j), static_cast<int>(k & 1), lvl_idx[k]));
+    }
+  }
+  g.lvl_off[g.maxlen] = static_cast<int64_t>(g.went.size());
+  return g;
+}
 }  // namespace
 
 }  // namespace vts
@@ -1987,60 +2026,9 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
                                 vts_transcode_ext_info *xinfo) {
   clear_error();
   if (!c || !out_path) return fail(VTS_E_INVALID, "NULL argument");
-  // size-tagged structs: only the prefix known here is read or written
-  int subpel = 0, deblock = 0, dbk_alpha = 0, dbk_beta = 0;
-  int mvcost = 0, mv_lambda16 = 0, early_skip = 0;
-  uint32_t *cmd_out = nullptr;
-  int64_t cmd_cap = 0;
-  if (ext) {
-    if (ext->struct_size < 8) return fail(VTS_E_INVALID, "vts_transcode_ext.struct_size %u < 8", ext->struct_size);
-    subpel = ext->subpel;
-    if (subpel < 0 || subpel > 2) return fail(VTS_E_INVALID, "subpel %d: 0, 1 or 2", subpel);
-    // vts_transcode_ext2: each field only when the caller's struct holds it
-    const vts_transcode_ext2 *x2 = reinterpret_cast<const vts_transcode_ext2 *>(ext);
-    if (ext->struct_size >= 12) deblock = x2->deblock;
-    if (ext->struct_size >= 16) dbk_alpha = x2->deblock_alpha;
-    if (ext->struct_size >= 20) dbk_beta = x2->deblock_beta;
-    if (deblock != 0 && deblock != 1) return fail(VTS_E_INVALID, "deblock %d: 0 or 1", deblock);
-    if (dbk_alpha < -6 || dbk_alpha > 6) return fail(VTS_E_INVALID, "deblock_alpha %d: -6 .. 6", dbk_alpha);
-    if (dbk_beta < -6 || dbk_beta > 6) return fail(VTS_E_INVALID, "deblock_beta %d: -6 .. 6", dbk_beta);
-    if (!deblock && dbk_alpha) return fail(VTS_E_INVALID, "deblock_alpha %d without deblock = 1", dbk_alpha);
-    if (!deblock && dbk_beta) return fail(VTS_E_INVALID, "deblock_beta %d without deblock = 1", dbk_beta);
-    // vts_transcode_ext3, the same way
-    const vts_transcode_ext3 *x3 = reinterpret_cast<const vts_transcode_ext3 *>(ext);
-    if (ext->struct_size >= 28) mvcost = x3->mvcost;
-    if (ext->struct_size >= 32) mv_lambda16 = x3->mv_lambda16;
-    if (ext->struct_size >= 36) early_skip = x3->early_skip;
-    if (ext->struct_size >= 48) cmd_out = x3->cmd_out;
-    if (ext->struct_size >= 56) cmd_cap = x3->cmd_cap;
-    if (mvcost != 0 && mvcost != 1) return fail(VTS_E_INVALID, "mvcost %d: 0 or 1", mvcost);
-    if (early_skip != 0 && early_skip != 1) return fail(VTS_E_INVALID, "early_skip %d: 0 or 1", early_skip);
-    if (mv_lambda16 < 0 || mv_lambda16 > 4096) return fail(VTS_E_INVALID, "mv_lambda16 %d: 0 .. 4096", mv_lambda16);
-    if (!mvcost && mv_lambda16) return fail(VTS_E_INVALID, "mv_lambda16 %d without mvcost = 1", mv_lambda16);
-  }
-  const int rate = mvcost | (early_skip << 1);  // SearchArgs.rate
-  if (xinfo && xinfo->struct_size < 8)
-    return fail(VTS_E_INVALID, "vts_transcode_ext_info.struct_size %u < 8", xinfo->struct_size);
+  TranscodeOpts opt;
+  VTS_TRY(read_opts(c, pin, ext, xinfo, &opt));
   using clk = std::chrono::steady_clock;
-  vts_transcode_params p{};
-  if (pin) p = *pin;
-  const int sh = p.height > 0 ? p.height : 360;
-  const int R = p.search_range == 0 ? 8 : std::max(0, p.search_range);
-  const int T = p.max_mb_sad == 0 ? 1536 : p.max_mb_sad;
-  const int qp = p.qp == 0 ? 28 : (p.qp < 0 ? 0 : p.qp);  // 0: no residual coding (the round-2 encoder)
-  if (qp > 51) return fail(VTS_E_INVALID, "qp %d > 51", qp);
-  if (p.intra != 0 && p.intra != 1) return fail(VTS_E_INVALID, "intra %d: 0 or 1", p.intra);
-  const bool intra = p.intra == 1;
-  const bool hashed = intra || subpel != 0 || deblock || rate;  // recon_hash is computed
-  if (intra && qp < 1) return fail(VTS_E_INVALID, "intra = 1 needs residual coding (qp >= 0)");
-  if (deblock && qp < 1) return fail(VTS_E_INVALID, "deblock = 1 needs residual coding (qp >= 0)");
-  if (mvcost && qp < 1) return fail(VTS_E_INVALID, "mvcost = 1 needs residual coding (qp >= 0)");
-  if (early_skip && qp < 1) return fail(VTS_E_INVALID, "early_skip = 1 needs residual coding (qp >= 0)");
-  const int keyint = p.keyint > 0 ? p.keyint : 250;
-  const float thr = p.cut_threshold > 0 ? p.cut_threshold : c->params.cut_threshold;
-  if ((sh & 1) || sh < 16 || sh > c->height)
-    return fail(VTS_E_INVALID, "output height %d: even, 16 .. source height %d", sh, c->height);
-  if (R > kMaxRange) return fail(VTS_E_INVALID, "search_range %d > %d", R, kMaxRange);
   // constant frame rate (the writer's stts is one entry)
   const int64_t n = c->n_frames;
   int64_t delta = n > 1 ? c->pts[1] - c->pts[0] : std::max<int64_t>(1, c->info.track_timescale / 30);
@@ -2049,15 +2037,15 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
       return fail(VTS_E_UNSUPPORTED, "variable frame rate (frame %lld) is not transcoded",
                   static_cast<long long>(i));
   HIP_TRY(hipSetDevice(c->device));
-  VTS_TRY(setup_small(c, sh));
+  VTS_TRY(setup_small(c, opt.sh));
   const SmallStore &S = c->small;
   const int mbw = S.cw / 16, mbh = S.ch / 16, nmb = mbw * mbh;
   double ms[4] = {0, 0, 0, 0};
   // the command words of every macroblock, [frame][my][mx]: reported always, copied out when asked
   const int64_t cmd_words = c->n_frames * nmb;
   if (xinfo && xinfo->struct_size >= 48) reinterpret_cast<vts_transcode_ext_info3 *>(xinfo)->cmd_words = cmd_words;
-  if (cmd_out && cmd_cap < cmd_words)
-    return fail(VTS_E_CAPACITY, "cmd_cap %lld < %lld command words", static_cast<long long>(cmd_cap),
+  if (opt.cmd_out && opt.cmd_cap < cmd_words)
+    return fail(VTS_E_CAPACITY, "cmd_cap %lld < %lld command words", static_cast<long long>(opt.cmd_cap),
                 static_cast<long long>(cmd_words));
 
   // 1. decode + score + downscale
@@ -2069,39 +2057,8 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   VTS_TRY(fetch_scores(c));
   ms[0] = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
 
-  // 2. GOPs: IDR at frame 0, at cuts, every keyint frames
-  std::vector<int64_t> gop_start;
-  for (int64_t f = 0; f < n; ++f)
-    if (f == 0 || (p.idr_at_cuts && c->host_scores[f] > thr) || f - gop_start.back() >= keyint)
-      gop_start.push_back(f);
-  const int64_t ngop = static_cast<int64_t>(gop_start.size());
-  std::vector<int64_t> gop_len(static_cast<size_t>(ngop));
-  int64_t maxlen = 0;
-  for (int64_t g = 0; g < ngop; ++g) {
-    gop_len[g] = (g + 1 < ngop ? gop_start[g + 1] : n) - gop_start[g];
-    maxlen = std::max(maxlen, gop_len[g]);
-  }
-  // per level j: search entries (frame, ref slot, dst slot) and write entries (frame, j, idr parity)
-  std::vector<int4> sent, went;
-  std::vector<int64_t> lvl_off(static_cast<size_t>(maxlen) + 1, 0);
-  // with a rate-aware search, w of a search entry: the GOP's entry index in the previous level (GOPs of
-  // different lengths: the indices differ between levels), where enc_search finds the previous picture's words
-  std::vector<int> lvl_idx(static_cast<size_t>(ngop), 0);
-  for (int64_t j = 0; j < maxlen; ++j) {
-    lvl_off[j] = static_cast<int64_t>(went.size());
-    for (int64_t g = 0; g < ngop; ++g) {
-      if (gop_len[g] <= j) continue;
-      const int f = static_cast<int>(gop_start[g] + j);
-      const int prev_idx = rate ? lvl_idx[g] : 0;
-      lvl_idx[g] = static_cast<int>(static_cast<int64_t>(went.size()) - lvl_off[j]);
-      // level 1 predicts from the IDR picture: its source (all I_PCM) or, with intra, its reconstruction
-      sent.push_back(make_int4(f, j == 1 && !intra ? -1 : static_cast<int>(2 * g + ((j - 1) & 1)),
-                               static_cast<int>(2 * g + (j & 1)), prev_idx));
-      went.push_back(make_int4(f, static_cast<int>(j), static_cast<int>(g & 1),
-                               static_cast<int>(static_cast<int64_t>(went.size()) - lvl_off[j])));
-    }
-  }
-  lvl_off[maxlen] = static_cast<int64_t>(went.size());
+  // 2. GOPs and their levels
+  const GopPlan plan = plan_gops(n, c->host_scores, opt);
 
   // 3. device encode, level by level
   // staging slot per slice: an I_PCM macroblock is < 400 bytes, and so is an
@@ -2115,21 +2072,21 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   int32_t *d_sizes;
   int64_t *d_offs;
   unsigned long long *d_stats;
-  VTS_TRY(B.get(&d_sent, sent.size()));
-  VTS_TRY(B.get(&d_went, went.size()));
-  VTS_TRY(B.get(&d_recon, static_cast<size_t>(2 * ngop * S.stride + 256)));
-  VTS_TRY(B.get(&d_cmd, static_cast<size_t>(went.size()) * nmb));  // every frame: searches run ahead
+  VTS_TRY(B.get(&d_sent, plan.sent.size()));
+  VTS_TRY(B.get(&d_went, plan.went.size()));
+  VTS_TRY(B.get(&d_recon, static_cast<size_t>(2 * plan.ngop * S.stride + 256)));
+  VTS_TRY(B.get(&d_cmd, static_cast<size_t>(plan.went.size()) * nmb));  // every frame: searches run ahead
   uint8_t *d_cbp;
-  VTS_TRY(B.get(&d_cbp, static_cast<size_t>(went.size()) * nmb));
+  VTS_TRY(B.get(&d_cbp, static_cast<size_t>(plan.went.size()) * nmb));
   // residual levels: a ring of kRing levels (the searches run at most kRing
   // levels ahead of the slice writing that reads them)
   constexpr int64_t kRing = 32;
   int16_t *d_coef = nullptr;
-  if (qp >= 1) VTS_TRY(B.get(&d_coef, static_cast<size_t>(kRing * ngop * nmb * kCoefPerMb)));
+  if (opt.qp >= 1) VTS_TRY(B.get(&d_coef, static_cast<size_t>(kRing * plan.ngop * nmb * kCoefPerMb)));
   constexpr int64_t kChunkLevels = 16;  // levels written and drained together
   int64_t max_chunk = 0;                 // entries of the largest chunk
-  for (int64_t j0 = 0; j0 < maxlen; j0 += kChunkLevels)
-    max_chunk = std::max(max_chunk, lvl_off[std::min(maxlen, j0 + kChunkLevels)] - lvl_off[j0]);
+  for (int64_t j0 = 0; j0 < plan.maxlen; j0 += kChunkLevels)
+    max_chunk = std::max(max_chunk, plan.lvl_off[std::min(plan.maxlen, j0 + kChunkLevels)] - plan.lvl_off[j0]);
   VTS_TRY(B.get(&d_stage, static_cast<size_t>(max_chunk * mbh * cap)));
   VTS_TRY(B.get(&d_out, static_cast<size_t>(max_chunk * mbh * cap)));
   int64_t *d_total, *d_base, *d_fr;
@@ -2153,21 +2110,21 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   // overlapping the searches of later chunks.
   hipStream_t s1 = c->s_dec, s2 = c->s_score;
   B.streams = {s1, s2};
-  HIP_TRY(hipMemcpy(d_sent, sent.data(), sent.size() * sizeof(int4), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_went, went.data(), went.size() * sizeof(int4), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_sent, plan.sent.data(), plan.sent.size() * sizeof(int4), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_went, plan.went.data(), plan.went.size() * sizeof(int4), hipMemcpyHostToDevice));
   int4 *d_hent = nullptr;  // level 0's entries with the frame as the slot (enqueue_hash)
-  if (hashed && !intra) {
-    std::vector<int4> hent(sent.begin(), sent.begin() + lvl_off[1]);
+  if (opt.hashed && !opt.intra) {
+    std::vector<int4> hent(plan.sent.begin(), plan.sent.begin() + plan.lvl_off[1]);
     for (int4 &h : hent) h.z = h.x;
     VTS_TRY(B.get(&d_hent, hent.size()));
     HIP_TRY(hipMemcpy(d_hent, hent.data(), hent.size() * sizeof(int4), hipMemcpyHostToDevice));
   }
   HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), s2));
   // enc_hash, enc_search<., SP > 0> and enc_deblock (s1) add into these
-  if (hashed) HIP_TRY(hipMemsetAsync(d_stats + 4, 0, (rate ? 5 : 4) * sizeof(unsigned long long), s1));
+  if (opt.hashed) HIP_TRY(hipMemsetAsync(d_stats + 4, 0, (opt.rate ? 5 : 4) * sizeof(unsigned long long), s1));
   HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(uint32_t), s2));
-  const int64_t nchunks = (maxlen + kChunkLevels - 1) / kChunkLevels;
-  std::vector<hipEvent_t> ev(static_cast<size_t>(maxlen + 5 + nchunks), nullptr);
+  const int64_t nchunks = (plan.maxlen + kChunkLevels - 1) / kChunkLevels;
+  std::vector<hipEvent_t> ev(static_cast<size_t>(plan.maxlen + 5 + nchunks), nullptr);
   struct EvGuard {
     std::vector<hipEvent_t> &v;
     ~EvGuard() {
@@ -2176,27 +2133,27 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
     }
   } ev_guard{ev};
   for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-  hipEvent_t es0 = ev[maxlen], es1 = ev[maxlen + 1], ew0 = ev[maxlen + 2], ew1 = ev[maxlen + 3];
-  hipEvent_t *wev = &ev[maxlen + 5];  // per chunk: its slices written (its ring slots free again)
+  hipEvent_t es0 = ev[plan.maxlen], es1 = ev[plan.maxlen + 1], ew0 = ev[plan.maxlen + 2], ew1 = ev[plan.maxlen + 3];
+  hipEvent_t *wev = &ev[plan.maxlen + 5];  // per chunk: its slices written (its ring slots free again)
   HIP_TRY(hipEventRecord(es0, s1));
   // intra: the level's kPcmCmd macroblocks (level 0: every macroblock) become
   // Intra16x16 where cheaper, then the level's reconstruction is hashed; both
   // on the search stream, before the next level's search reads the slots
   auto enqueue_intra = [&](int64_t j) {
-    const int64_t ne = lvl_off[j + 1] - lvl_off[j];
+    const int64_t ne = plan.lvl_off[j + 1] - plan.lvl_off[j];
     IntraArgs ia{};
-    ia.ent = d_sent + lvl_off[j];
+    ia.ent = d_sent + plan.lvl_off[j];
     ia.small = S.d;
     ia.stride = S.stride;
     ia.recon = d_recon;
-    ia.cmd = d_cmd + lvl_off[j] * nmb;
-    ia.cbp = d_cbp + lvl_off[j] * nmb;
-    ia.coef = d_coef + (j % kRing) * ngop * nmb * kCoefPerMb;
+    ia.cmd = d_cmd + plan.lvl_off[j] * nmb;
+    ia.cbp = d_cbp + plan.lvl_off[j] * nmb;
+    ia.coef = d_coef + (j % kRing) * plan.ngop * nmb * kCoefPerMb;
     ia.cw = S.cw;
     ia.ch = S.ch;
     ia.mbw = mbw;
     ia.mbh = mbh;
-    ia.qp = qp;
+    ia.qp = opt.qp;
     ia.all = j == 0;
     hipLaunchKernelGGL(enc_intra, dim3(static_cast<unsigned>(ne * mbh)), dim3(64), 0, s1, ia);
   };
@@ -2205,21 +2162,21 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   // hashed and the next level predicts from it.  Level 0 without intra is all
   // I_PCM (qPav 0, alpha' 0: nothing is filtered) and is not launched
   auto enqueue_deblock = [&](int64_t j) {
-    const int64_t ne = lvl_off[j + 1] - lvl_off[j];
+    const int64_t ne = plan.lvl_off[j + 1] - plan.lvl_off[j];
     DeblockArgs da{};
-    da.ent = d_sent + lvl_off[j];
+    da.ent = d_sent + plan.lvl_off[j];
     da.recon = d_recon;
     da.stride = S.stride;
-    da.cmd = d_cmd + lvl_off[j] * nmb;
-    da.cbp = d_cbp + lvl_off[j] * nmb;
-    da.coef = d_coef + (j % kRing) * ngop * nmb * kCoefPerMb;
+    da.cmd = d_cmd + plan.lvl_off[j] * nmb;
+    da.cbp = d_cbp + plan.lvl_off[j] * nmb;
+    da.coef = d_coef + (j % kRing) * plan.ngop * nmb * kCoefPerMb;
     da.cw = S.cw;
     da.ch = S.ch;
     da.mbw = mbw;
     da.mbh = mbh;
-    da.qp = qp;
-    da.off_a = 2 * dbk_alpha;
-    da.off_b = 2 * dbk_beta;
+    da.qp = opt.qp;
+    da.off_a = 2 * opt.dbk_alpha;
+    da.off_b = 2 * opt.dbk_beta;
     da.count = d_stats + 7;
     hipLaunchKernelGGL(enc_deblock, dim3(static_cast<unsigned>(ne * mbh)), dim3(64), 0, s1, da);
   };
@@ -2227,73 +2184,73 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   // reconstruction slots, or (level 0 without intra: the IDR pictures are
   // their source) the small store, through entries whose slot is the frame
   auto enqueue_hash = [&](int64_t j) {
-    const int64_t ne = lvl_off[j + 1] - lvl_off[j];
-    const bool from_source = j == 0 && !intra;
+    const int64_t ne = plan.lvl_off[j + 1] - plan.lvl_off[j];
+    const bool from_source = j == 0 && !opt.intra;
     const int hb = std::max(1, std::min(64, (S.w * S.h * 3 / 2 + 4095) / 4096));
     hipLaunchKernelGGL(enc_hash, dim3(static_cast<unsigned>(hb * ne)), dim3(256), 0, s1,
-                       from_source ? d_hent : d_sent + lvl_off[j], from_source ? S.d : d_recon, S.stride, S.cw, S.ch,
+                       from_source ? d_hent : d_sent + plan.lvl_off[j], from_source ? S.d : d_recon, S.stride, S.cw, S.ch,
                        S.w, S.h, hb, d_stats + 4);
   };
-  if (intra) enqueue_intra(0);
-  if (intra && deblock) enqueue_deblock(0);
-  if (hashed) enqueue_hash(0);
-  if (intra) HIP_TRY(hipEventRecord(ev[0], s1));
+  if (opt.intra) enqueue_intra(0);
+  if (opt.intra && opt.deblock) enqueue_deblock(0);
+  if (opt.hashed) enqueue_hash(0);
+  if (opt.intra) HIP_TRY(hipEventRecord(ev[0], s1));
   int64_t next_search = 1;
   bool searches_done = false;
   // enqueue the searches of levels < upto; level j reuses the ring slot of
   // level j - kRing, whose chunk's slice writing must have finished
   auto enqueue_searches = [&](int64_t upto) -> int {
-    for (; next_search < std::min(maxlen, upto); ++next_search) {
+    for (; next_search < std::min(plan.maxlen, upto); ++next_search) {
       const int64_t j = next_search;
-      if (qp >= 1 && j >= kRing) HIP_TRY(hipStreamWaitEvent(s1, wev[(j - kRing) / kChunkLevels], 0));
-      const int64_t ne = lvl_off[j + 1] - lvl_off[j];
+      if (opt.qp >= 1 && j >= kRing) HIP_TRY(hipStreamWaitEvent(s1, wev[(j - kRing) / kChunkLevels], 0));
+      const int64_t ne = plan.lvl_off[j + 1] - plan.lvl_off[j];
       SearchArgs sa{};
-      sa.ent = d_sent + lvl_off[j];
+      sa.ent = d_sent + plan.lvl_off[j];
       sa.small = S.d;
       sa.stride = S.stride;
       sa.recon = d_recon;
-      sa.cmd = d_cmd + lvl_off[j] * nmb;
-      sa.cbp = d_cbp + lvl_off[j] * nmb;
-      sa.coef = d_coef ? d_coef + (j % kRing) * ngop * nmb * kCoefPerMb : nullptr;
+      sa.cmd = d_cmd + plan.lvl_off[j] * nmb;
+      sa.cbp = d_cbp + plan.lvl_off[j] * nmb;
+      sa.coef = d_coef ? d_coef + (j % kRing) * plan.ngop * nmb * kCoefPerMb : nullptr;
       sa.cw = S.cw;
       sa.ch = S.ch;
       sa.mbw = mbw;
       sa.nmb = nmb;
-      sa.range = R;
-      sa.max_sad = T;
-      sa.qp = qp;
+      sa.range = opt.R;
+      sa.max_sad = opt.T;
+      sa.qp = opt.qp;
       sa.sp_stats = d_stats + 5;
       const dim3 grid(static_cast<unsigned>(ne * nmb));
-      if (rate) {  // the instances with the rate-aware decisions compiled in
-        sa.rate = rate;
-        sa.cmd_prev = d_cmd + lvl_off[j - 1] * nmb;
+      if (opt.rate) {  // the instances with the rate-aware decisions compiled in
+        sa.rate = opt.rate;
+        sa.cmd_prev = d_cmd + plan.lvl_off[j - 1] * nmb;
         sa.gop_pos = static_cast<int32_t>(j);
-        sa.lambda16 = full::erate::lambda16(qp, mv_lambda16);
+        sa.lambda16 = full::erate::lambda16(opt.qp, opt.mv_lambda16);
         sa.es_stat = d_stats + 8;
-        switch (subpel) {
-          case 1: launch_search<1, true>(R, grid, s1, sa); break;
-          case 2: launch_search<2, true>(R, grid, s1, sa); break;
-          default: launch_search<0, true>(R, grid, s1, sa); break;
+        switch (opt.subpel) {
+          case 1: launch_search<1, true>(opt.R, grid, s1, sa); break;
+          case 2: launch_search<2, true>(opt.R, grid, s1, sa); break;
+          default: launch_search<0, true>(opt.R, grid, s1, sa); break;
         }
       } else {
-        switch (subpel) {
-          case 1: launch_search<1, false>(R, grid, s1, sa); break;
-          case 2: launch_search<2, false>(R, grid, s1, sa); break;
-          default: launch_search<0, false>(R, grid, s1, sa); break;
+        switch (opt.subpel) {
+          case 1: launch_search<1, false>(opt.R, grid, s1, sa); break;
+          case 2: launch_search<2, false>(opt.R, grid, s1, sa); break;
+          default: launch_search<0, false>(opt.R, grid, s1, sa); break;
         }
       }
-      if (intra) enqueue_intra(j);
-      if (deblock) enqueue_deblock(j);
-      if (hashed) enqueue_hash(j);
+      if (opt.intra) enqueue_intra(j);
+      if (opt.deblock) enqueue_deblock(j);
+      if (opt.hashed) enqueue_hash(j);
       HIP_TRY(hipEventRecord(ev[j], s1));
     }
-    if (next_search >= maxlen && !searches_done) {
+    if (next_search >= plan.maxlen && !searches_done) {
       HIP_TRY(hipEventRecord(es1, s1));
       searches_done = true;
     }
     return VTS_OK;
   };
-  VTS_TRY(enqueue_searches(qp >= 1 ? kRing : maxlen));
+  VTS_TRY(enqueue_searches(opt.qp >= 1 ? kRing : plan.maxlen));
   HIP_TRY(hipGetLastError());
   // Output drained to the host every chunk (absolute bytes [chunk_start[c],
   // chunk_start[c+1])) and appended to the MP4's mdat while the GPU works on
@@ -2303,7 +2260,7 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   if (!e.empty()) return fail(VTS_E_IO, "%s: %s", out_path, e.c_str());
   std::vector<std::unique_ptr<uint8_t[]>> host;
   std::vector<int64_t> chunk_start{0}, chunk_file;  // chunk c's file offset
-  hipEvent_t ev_d2h = ev[maxlen + 4];              // reused: the last chunk's D2H
+  hipEvent_t ev_d2h = ev[plan.maxlen + 4];              // reused: the last chunk's D2H
   bool pending = false;                            // a chunk's D2H not yet written out
   double mux_ms = 0;
   auto write_pending = [&]() -> int {
@@ -2323,13 +2280,13 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   int status = VTS_OK;
   HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(int64_t), s2));
   HIP_TRY(hipEventRecord(ew0, s2));
-  for (int64_t j0 = 0; j0 < maxlen && status == VTS_OK; j0 += kChunkLevels) {
+  for (int64_t j0 = 0; j0 < plan.maxlen && status == VTS_OK; j0 += kChunkLevels) {
     // one chunk of levels = one contiguous run of entries: written, scanned,
     // gathered and drained together (wide launches instead of one per level)
-    const int64_t j1 = std::min(maxlen, j0 + kChunkLevels);
-    const int64_t e0 = lvl_off[j0], ne = lvl_off[j1] - e0;
+    const int64_t j1 = std::min(plan.maxlen, j0 + kChunkLevels);
+    const int64_t e0 = plan.lvl_off[j0], ne = plan.lvl_off[j1] - e0;
     const int ns = static_cast<int>(ne * mbh);
-    if (j1 - 1 > 0 || intra) HIP_TRY(hipStreamWaitEvent(s2, ev[j1 - 1], 0));  // searches run in level order
+    if (j1 - 1 > 0 || opt.intra) HIP_TRY(hipStreamWaitEvent(s2, ev[j1 - 1], 0));  // searches run in level order
     HIP_TRY(hipMemcpyAsync(d_base, d_total, sizeof(int64_t), hipMemcpyDeviceToDevice, s2));
     HIP_TRY(hipMemsetAsync(d_njobs, 0, sizeof(uint32_t), s2));
     WriteArgs wa{};
@@ -2337,9 +2294,9 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
     wa.cmd = d_cmd + e0 * nmb;
     wa.cbp = d_cbp + e0 * nmb;
     wa.coef = d_coef;
-    wa.coef_per_level = ngop;
+    wa.coef_per_level = plan.ngop;
     wa.ring = static_cast<int32_t>(kRing);
-    wa.qp = qp;
+    wa.qp = opt.qp;
     wa.small = S.d;
     wa.stride = S.stride;
     wa.cw = S.cw;
@@ -2354,14 +2311,14 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
     wa.jobs = d_jobs;
     wa.n_jobs = d_njobs;
     wa.n_slices = ns;
-    wa.dbk_alpha = dbk_alpha;
-    wa.dbk_beta = dbk_beta;
+    wa.dbk_alpha = opt.dbk_alpha;
+    wa.dbk_beta = opt.dbk_beta;
     const dim3 wgrid(static_cast<unsigned>((ns + 63) / 64));
-    if (deblock) {
-      if (intra) hipLaunchKernelGGL((enc_write<true, true>), wgrid, dim3(64), 0, s2, wa);
+    if (opt.deblock) {
+      if (opt.intra) hipLaunchKernelGGL((enc_write<true, true>), wgrid, dim3(64), 0, s2, wa);
       else hipLaunchKernelGGL((enc_write<false, true>), wgrid, dim3(64), 0, s2, wa);
     } else {
-      if (intra) hipLaunchKernelGGL((enc_write<true, false>), wgrid, dim3(64), 0, s2, wa);
+      if (opt.intra) hipLaunchKernelGGL((enc_write<true, false>), wgrid, dim3(64), 0, s2, wa);
       else hipLaunchKernelGGL((enc_write<false, false>), wgrid, dim3(64), 0, s2, wa);
     }
     HIP_TRY(hipEventRecord(wev[j0 / kChunkLevels], s2));
@@ -2416,12 +2373,12 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   HIP_TRY(hipMemcpy(&err, d_err, sizeof err, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost));
   if (err) return fail(VTS_E_CAPACITY, "a slice exceeded its %lld-byte staging slot", static_cast<long long>(cap));
-  if (cmd_out) {  // entry order -> frame order; a level the encoder writes no words for (the I_PCM IDR pictures) is I_PCM
-    std::vector<uint32_t> words(went.size() * static_cast<size_t>(nmb));
+  if (opt.cmd_out) {  // entry order -> frame order; a level the encoder writes no words for (the I_PCM IDR pictures) is I_PCM
+    std::vector<uint32_t> words(plan.went.size() * static_cast<size_t>(nmb));
     HIP_TRY(hipMemcpy(words.data(), d_cmd, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < went.size(); ++i) {
-      uint32_t *o = cmd_out + static_cast<int64_t>(went[i].x) * nmb;
-      if (went[i].y == 0 && !intra) std::fill(o, o + nmb, kPcmCmd);
+    for (size_t i = 0; i < plan.went.size(); ++i) {
+      uint32_t *o = opt.cmd_out + static_cast<int64_t>(plan.went[i].x) * nmb;
+      if (plan.went[i].y == 0 && !opt.intra) std::fill(o, o + nmb, kPcmCmd);
       else std::memcpy(o, words.data() + i * static_cast<size_t>(nmb), static_cast<size_t>(nmb) * sizeof(uint32_t));
     }
   }
@@ -2432,7 +2389,7 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   const double fps = static_cast<double>(c->info.track_timescale) / static_cast<double>(delta);
   make_sps_pps(mbw, mbh, S.cw - S.w, S.ch - S.h, h264_pick_level(nmb, nmb * fps), &sps, &pps);
   std::vector<uint8_t> is_idr(static_cast<size_t>(n), 0);
-  for (int64_t f : gop_start) is_idr[f] = 1;
+  for (int64_t f : plan.gop_start) is_idr[f] = 1;
   for (int64_t f = 0; f < n && e.empty(); ++f) {
     const int64_t off = fr[f], size = fr[n + f];
     const size_t ci = static_cast<size_t>(std::upper_bound(chunk_start.begin(), chunk_start.end(), off) -
@@ -2449,22 +2406,22 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
     info->width = S.w;
     info->height = S.h;
     info->n_frames = n;
-    info->n_idr = ngop;
+    info->n_idr = plan.ngop;
     info->pcm_mbs = static_cast<int64_t>(st[0]);
     info->inter_mbs = static_cast<int64_t>(st[1]);
     info->skip_mbs = static_cast<int64_t>(st[2]);
     info->intra_mbs = static_cast<int64_t>(st[3]);
-    info->recon_hash = hashed ? st[4] : 0;
+    info->recon_hash = opt.hashed ? st[4] : 0;
     info->bytes_written = mw.bytes_written();
     for (int i = 0; i < 4; ++i) info->ms[i] = ms[i];
   }
   if (xinfo) {
-    if (xinfo->struct_size >= 16) xinfo->subpel_mbs = subpel ? static_cast<int64_t>(st[5] + st[6]) : 0;
-    if (xinfo->struct_size >= 24) xinfo->qpel_mbs = subpel ? static_cast<int64_t>(st[6]) : 0;
+    if (xinfo->struct_size >= 16) xinfo->subpel_mbs = opt.subpel ? static_cast<int64_t>(st[5] + st[6]) : 0;
+    if (xinfo->struct_size >= 24) xinfo->qpel_mbs = opt.subpel ? static_cast<int64_t>(st[6]) : 0;
     if (xinfo->struct_size >= 32)
-      reinterpret_cast<vts_transcode_ext_info2 *>(xinfo)->deblock_mbs = deblock ? static_cast<int64_t>(st[7]) : 0;
+      reinterpret_cast<vts_transcode_ext_info2 *>(xinfo)->deblock_mbs = opt.deblock ? static_cast<int64_t>(st[7]) : 0;
     if (xinfo->struct_size >= 40)
-      reinterpret_cast<vts_transcode_ext_info3 *>(xinfo)->early_skip_mbs = early_skip ? static_cast<int64_t>(st[8]) : 0;
+      reinterpret_cast<vts_transcode_ext_info3 *>(xinfo)->early_skip_mbs = opt.early_skip ? static_cast<int64_t>(st[8]) : 0;
   }
   return VTS_OK;
 }
