@@ -403,7 +403,8 @@ void vts_batch_free(vts_batch *b);
  * (src/analyzer/content_analyzer.py:167-236: `ffmpeg -vf scale=-2:360
  * -c:v libx264 -crf 28`).  The session's device decoder decodes every frame,
  * an area filter downscales it to (w, height) with w = ffmpeg's scale=-2
- * width, and a device encoder writes H.264 Constrained Baseline: IDR (all
+ * width, and a device encoder writes H.264 Constrained Baseline (CAVLC; Main
+ * with CABAC when vts_transcode_ext4.cabac = 1): IDR (all
  * I_PCM, or Intra16x16 with intra = 1) every keyint frames (and at scene cuts
  * if asked), P pictures of full-search
  * integer motion (P_L0_16x16 / P_Skip; refined to half or quarter samples
@@ -555,6 +556,25 @@ typedef struct vts_transcode_ext_info3 {
                               when early_skip is off                           */
   int64_t cmd_words;       /* n_frames * macroblocks per picture               */
 } vts_transcode_ext_info3;
+
+/* CABAC entropy coding (9.3) in the encoder, DESIGN.md §11.  As the structs
+ * above: begun with them, passed by pointer cast, struct_size = its own
+ * sizeof; cabac is read when struct_size >= 60 (a 56-byte vts_transcode_ext3
+ * or anything smaller: 0).  cabac = 1: the SPS says Main (profile_idc 77,
+ * constraint_set1), the PPS entropy_coding_mode_flag = 1, P slices carry
+ * cabac_init_idc 0, and the slice data of every slice is written by 7.3.4 /
+ * 9.3 instead of CAVLC.  Entropy coding is lossless: every decision of the
+ * encoder (still made with the CAVLC bit counts), every count, command word
+ * and recon_hash is that of the same call with cabac = 0; only the bytes of
+ * the slices and the two parameter sets differ.  A slice's staging slot grows
+ * to the CABAC worst case, 9024 bytes per macroblock.  Needs residual coding
+ * (qp >= 0).  VTS_E_INVALID, the field named: cabac not 0 or 1, cabac = 1 with
+ * qp < 0. */
+typedef struct vts_transcode_ext4 {
+  vts_transcode_ext3 base;
+  int32_t cabac;           /* 0 CAVLC (every output byte as before), 1 CABAC    */
+  int32_t _pad2;
+} vts_transcode_ext4;
 
 /* vts_transcode with the settings of `ext` (NULL: none) and the further facts
  * in `ext_info` (NULL: not wanted).  vts_transcode(c, o, p, i) is

@@ -249,10 +249,10 @@ int h264_pick_level(int mbs, double mbps) {
 // Build the SPS/PPS RBSPs for the stream (also used by tests via the file).
 void make_sps_pps(int mbw, int mbh, int crop_r, int crop_b, int level,
                          std::vector<uint8_t> *sps_nal, std::vector<uint8_t> *pps_nal,
-                         int chroma_qp_index_offset) {
+                         int chroma_qp_index_offset, bool cabac) {
   BitWriter s;
-  s.u(8, 66);        // profile_idc: Baseline
-  s.u(8, 0xC0);      // constraint_set0 + set1: Constrained Baseline
+  s.u(8, cabac ? 77 : 66);      // profile_idc: Baseline, or Main for entropy_coding_mode_flag = 1
+  s.u(8, cabac ? 0x40 : 0xC0);  // constraint_set0 + set1: Constrained Baseline; set1 alone: Main
   s.u(8, static_cast<uint32_t>(level));
   s.ue(0);           // seq_parameter_set_id
   s.ue(12);          // log2_max_frame_num_minus4 -> 16 bits
@@ -281,7 +281,7 @@ void make_sps_pps(int mbw, int mbh, int crop_r, int crop_b, int level,
   BitWriter p;
   p.ue(0);           // pic_parameter_set_id
   p.ue(0);           // seq_parameter_set_id
-  p.u(1, 0);         // entropy_coding_mode_flag: CAVLC
+  p.u(1, cabac ? 1 : 0);  // entropy_coding_mode_flag: CAVLC, or CABAC
   p.u(1, 0);         // bottom_field_pic_order_in_frame_present_flag
   p.ue(0);           // num_slice_groups_minus1
   p.ue(0);           // num_ref_idx_l0_default_active_minus1
@@ -513,7 +513,7 @@ extern "C" int vts_synth_write(const char *path, const vts_synth_params *prm,
   const int level = h264_pick_level(mbw * mbh, mbw * mbh * fps);
   std::vector<uint8_t> sps, pps;
   if (P.coding == 1) make_sps_pps_full(P, level, &sps, &pps);
-  else make_sps_pps(mbw, mbh, cw - P.width, ch - P.height, level, &sps, &pps, (P.edge_cases & 512) ? 12 : 0);
+  else make_sps_pps(mbw, mbh, cw - P.width, ch - P.height, level, &sps, &pps, (P.edge_cases & 512) ? 12 : 0, false);
 
   Mp4Writer mw;
   std::string e = mw.open(path);

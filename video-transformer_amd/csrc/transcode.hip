@@ -21,7 +21,9 @@
 //      level's reconstruction; then per chunk of 16 levels on a second stream:
 //      `enc_write` — one lane per slice (macroblock row) writes the CAVLC
 //      slice NAL with emulation prevention into a fixed-capacity staging slot,
-//      leaving I_PCM payloads as gaps; `enc_scan` — device offsets;
+//      leaving I_PCM payloads as gaps (opt-in, vts_transcode_ext4.cabac:
+//      `enc_write_cabac` — one wave per slice writes it as CABAC through
+//      enc_cabac.h instead); `enc_scan` — device offsets;
 //      `enc_gather` + `enc_pcm` — packed output, one D2H copy per chunk;
 //   4. host: MP4 mux (Mp4Writer) in display order.
 #include <hip/hip_runtime.h>
@@ -34,6 +36,7 @@
 #include <string>
 #include <vector>
 
+#include "enc_cabac.h"
 #include "enc_deblock.h"
 #include "enc_rate.h"
 #include "mp4.h"
@@ -1656,6 +1659,115 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   if (nintra) atomicAdd(&a.stats[3], nintra);
 }
 
+// The slices with entropy_coding_mode_flag = 1 (vts_transcode_ext4.cabac,
+// DESIGN.md §11): enc_write's arguments, staging slots, sizes, counters, error
+// word and I_PCM jobs, the slice data by 7.3.4 / 9.3 through enc_cabac.h.  One
+// wave per slice: a slice is a serial chain of bins, so lane 0 walks it; the
+// wave initialises the 277 context variables in LDS (9.3.1.1), counts the
+// slice's I_PCM jobs and stages each macroblock's levels in LDS ahead of
+// lane 0's walk.  Lane 0 records a macroblock's bins in an LDS ring
+// (ecab::BinRing: one 16-bit entry per bin) and codes them in ecab::drain's one
+// loop, at the latest where the ring has less than a block's worst case free.
+// Ordering is program order inside the wave and the two workgroup barriers
+// around the walk of a macroblock; no wave waits on another.
+//
+// I_PCM: mb_type ends in the terminate bin 1 and the flush (9.3.4.5), whose
+// last bit is 1; pcm_alignment_zero_bits follow in the same byte or none at
+// all, so the byte before the samples is non-zero, the samples are >= 1
+// (downscale clamp), and pcm_gap's argument holds as it does for CAVLC: no
+// emulation prevention byte falls in or next to the samples and the zero run
+// after them is 0.  The encoder restarts behind them (9.3.1.2).
+template <bool kIntra, bool kDbk>
+__global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
+  namespace ec = full::ecab;
+  __shared__ uint8_t st[320];             // ec::kNumCtx context variables
+  __shared__ uint32_t lvw[kCoefPerMb / 2];  // the macroblock's levels
+  __shared__ uint16_t ring[ec::kRingBins];
+  const int s = blockIdx.x, lane = threadIdx.x;  // the grid is n_slices waves
+  const int e = s / a.mbh, row = s % a.mbh;
+  const int4 en = a.ent[e];
+  const bool idr = en.y == 0;
+  for (int i = lane; i < ec::kNumCtx; i += 64) st[i] = ec::init_context(i, idr, a.qp);
+  const uint32_t *cmd = a.cmd + static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw;
+  const uint8_t *cbpr = a.cbp + static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw;
+  const int16_t *coef_row =
+      a.coef + ((static_cast<int64_t>(en.y % a.ring) * a.coef_per_level + en.w) * a.mbh + row) * a.mbw * kCoefPerMb;
+  const bool all_pcm = idr && !kIntra;  // level 0 without intra holds no commands
+  uint32_t njob = 0;
+  if (all_pcm) {
+    njob = static_cast<uint32_t>(a.mbw);
+  } else {
+    for (int mx = lane; mx < a.mbw; mx += 64) njob += cmd[mx] == kPcmCmd;
+    for (int off = 32; off > 0; off >>= 1) njob += __shfl_xor(njob, off);
+  }
+  uint8_t *slot = a.staging + static_cast<int64_t>(s) * a.cap;
+  NalOut o{reinterpret_cast<uint32_t *>(slot + 4), a.cap - 4, 0, 0, 0, 0, 0, false};
+  ec::Encoder<NalOut> coder{&o, st, 0, 510, 0, true};
+  ec::BinRing<NalOut> enc{&coder, ring, 0};
+  ec::Left left = ec::left_none();
+  uint4 *job = a.jobs;
+  unsigned long long npcm = 0, ninter = 0, nskip = 0, nintra = 0;
+  bool a_ok = false;
+  int amx = 0, amy = 0;
+  if (lane == 0) {
+    if (njob) job += atomicAdd(a.n_jobs, njob);
+    ec::slice_header(o, idr, row * a.mbw, en.y, en.z, a.qp, kDbk, a.dbk_alpha, a.dbk_beta);
+  }
+  const int16_t *lv = reinterpret_cast<const int16_t *>(lvw);
+  for (int mx = 0; mx < a.mbw; ++mx) {
+    const uint32_t c = all_pcm ? kPcmCmd : cmd[mx];  // wave-uniform
+    const bool intra = kIntra && is_intra_cmd(c);
+    const int cbp = (c == kPcmCmd || intra) ? 0 : cbpr[mx];
+    __syncthreads();  // lane 0 is done with the previous macroblock's levels (and, first, the contexts are set)
+    if (intra || cbp) {
+      const uint32_t *src = reinterpret_cast<const uint32_t *>(coef_row + static_cast<int64_t>(mx) * kCoefPerMb);
+      for (int i = lane; i < kCoefPerMb / 2; i += 64) lvw[i] = src[i];
+    }
+    __syncthreads();
+    if (lane != 0) continue;
+    const bool last = mx == a.mbw - 1;
+    if (c == kPcmCmd) {
+      ec::mb_pcm_begin(enc, idr, left);
+      pcm_gap(o, job++, s, mx);
+      ec::mb_pcm_end(enc, left, last);
+      a_ok = false;
+      ++npcm;
+    } else if (intra) {
+      ec::mb_intra16(enc, idr, left, c, lv, last);
+      a_ok = false;
+      ++nintra;
+    } else {
+      const int mvx = static_cast<int16_t>(c & 0xffffu), mvy = static_cast<int16_t>(c >> 16);
+      if (mvx == 0 && mvy == 0 && cbp == 0) {  // P_Skip
+        ec::mb_skip(enc, left, last);
+        ++nskip;
+      } else {
+        ec::mb_inter(enc, left, mvx - (a_ok ? amx : 0), mvy - (a_ok ? amy : 0), cbp, lv, last);  // 8.4.1.3, A alone
+        ++ninter;
+      }
+      a_ok = true;
+      amx = mvx;
+      amy = mvy;
+    }
+  }
+  if (lane != 0) return;
+  enc.sync();
+  o.align();  // the flush of the last end_of_slice_flag ended in rbsp_stop_one_bit
+  o.flush();
+  const int64_t len = o.n;
+  if (o.over) {
+    atomicOr(a.err, 1u);
+    a.sizes[s] = 0;
+    return;
+  }
+  *reinterpret_cast<uint32_t *>(slot) = __builtin_bswap32(static_cast<uint32_t>(len));  // big-endian length
+  a.sizes[s] = static_cast<int32_t>(len + 4);
+  atomicAdd(&a.stats[0], npcm);
+  atomicAdd(&a.stats[1], ninter);
+  atomicAdd(&a.stats[2], nskip);
+  if (nintra) atomicAdd(&a.stats[3], nintra);
+}
+
 // Slice offsets of one level on the device: offs[s] = running output total +
 // exclusive scan of the slice sizes (one 1024-thread workgroup), each frame's
 // (offset, size), and the running total advanced.  No host round trip.
@@ -1905,6 +2017,7 @@ void launch_search(int R, dim3 grid, hipStream_t s, const SearchArgs &sa) {
 struct TranscodeOpts {
   int subpel = 0, deblock = 0, dbk_alpha = 0, dbk_beta = 0;
   int mvcost = 0, mv_lambda16 = 0, early_skip = 0;
+  int cabac = 0;
   uint32_t *cmd_out = nullptr;
   int64_t cmd_cap = 0;
   int rate = 0;         // SearchArgs.rate: mvcost | early_skip << 1
@@ -1943,6 +2056,9 @@ int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_trans
     if (o.early_skip != 0 && o.early_skip != 1) return fail(VTS_E_INVALID, "early_skip %d: 0 or 1", o.early_skip);
     if (o.mv_lambda16 < 0 || o.mv_lambda16 > 4096) return fail(VTS_E_INVALID, "mv_lambda16 %d: 0 .. 4096", o.mv_lambda16);
     if (!o.mvcost && o.mv_lambda16) return fail(VTS_E_INVALID, "mv_lambda16 %d without mvcost = 1", o.mv_lambda16);
+    // vts_transcode_ext4, the same way
+    if (ext->struct_size >= 60) o.cabac = reinterpret_cast<const vts_transcode_ext4 *>(ext)->cabac;
+    if (o.cabac != 0 && o.cabac != 1) return fail(VTS_E_INVALID, "cabac %d: 0 or 1", o.cabac);
   }
   o.rate = o.mvcost | (o.early_skip << 1);
   if (xinfo && xinfo->struct_size < 8)
@@ -1961,6 +2077,7 @@ int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_trans
   if (o.deblock && o.qp < 1) return fail(VTS_E_INVALID, "deblock = 1 needs residual coding (qp >= 0)");
   if (o.mvcost && o.qp < 1) return fail(VTS_E_INVALID, "mvcost = 1 needs residual coding (qp >= 0)");
   if (o.early_skip && o.qp < 1) return fail(VTS_E_INVALID, "early_skip = 1 needs residual coding (qp >= 0)");
+  if (o.cabac && o.qp < 1) return fail(VTS_E_INVALID, "cabac = 1 needs residual coding (qp >= 0)");
   o.keyint = p.keyint > 0 ? p.keyint : 250;
   o.idr_at_cuts = p.idr_at_cuts != 0;
   o.thr = p.cut_threshold > 0 ? p.cut_threshold : c->params.cut_threshold;
@@ -2063,8 +2180,12 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   // 3. device encode, level by level
   // staging slot per slice: an I_PCM macroblock is < 400 bytes, and so is an
   // inter one (its residual is coded only under a 3072-bit bound); the rest
-  // is headroom for emulation prevention bytes in residual data
-  const int64_t cap = ((64 + static_cast<int64_t>(mbw) * 600) + 255) & ~int64_t(255);
+  // is headroom for emulation prevention bytes in residual data.  With cabac
+  // the decisions are still bounded in CAVLC bits, which bounds no CABAC
+  // length: the slot holds the worst case of the bins themselves
+  // (full::ecab::kMbBytes, derived there; the larger of the two bounds)
+  const int64_t cap =
+      ((64 + static_cast<int64_t>(mbw) * (opt.cabac ? std::max(600, full::ecab::kMbBytes) : 600)) + 255) & ~int64_t(255);
   DevBufs B;
   int4 *d_sent, *d_went;
   uint8_t *d_recon, *d_stage, *d_out;
@@ -2314,7 +2435,16 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
     wa.dbk_alpha = opt.dbk_alpha;
     wa.dbk_beta = opt.dbk_beta;
     const dim3 wgrid(static_cast<unsigned>((ns + 63) / 64));
-    if (opt.deblock) {
+    if (opt.cabac) {  // one wave per slice
+      const dim3 cgrid(static_cast<unsigned>(ns));
+      if (opt.deblock) {
+        if (opt.intra) hipLaunchKernelGGL((enc_write_cabac<true, true>), cgrid, dim3(64), 0, s2, wa);
+        else hipLaunchKernelGGL((enc_write_cabac<false, true>), cgrid, dim3(64), 0, s2, wa);
+      } else {
+        if (opt.intra) hipLaunchKernelGGL((enc_write_cabac<true, false>), cgrid, dim3(64), 0, s2, wa);
+        else hipLaunchKernelGGL((enc_write_cabac<false, false>), cgrid, dim3(64), 0, s2, wa);
+      }
+    } else if (opt.deblock) {
       if (opt.intra) hipLaunchKernelGGL((enc_write<true, true>), wgrid, dim3(64), 0, s2, wa);
       else hipLaunchKernelGGL((enc_write<false, true>), wgrid, dim3(64), 0, s2, wa);
     } else {
@@ -2387,7 +2517,7 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   t0 = clk::now();
   std::vector<uint8_t> sps, pps;
   const double fps = static_cast<double>(c->info.track_timescale) / static_cast<double>(delta);
-  make_sps_pps(mbw, mbh, S.cw - S.w, S.ch - S.h, h264_pick_level(nmb, nmb * fps), &sps, &pps);
+  make_sps_pps(mbw, mbh, S.cw - S.w, S.ch - S.h, h264_pick_level(nmb, nmb * fps), &sps, &pps, 0, opt.cabac != 0);
   std::vector<uint8_t> is_idr(static_cast<size_t>(n), 0);
   for (int64_t f : plan.gop_start) is_idr[f] = 1;
   for (int64_t f = 0; f < n && e.empty(); ++f) {

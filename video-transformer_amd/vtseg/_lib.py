@@ -154,6 +154,12 @@ class TranscodeExt3(C.Structure):
                 ("cmd_out", C.POINTER(C.c_uint32)), ("cmd_cap", C.c_int64)]
 
 
+class TranscodeExt4(C.Structure):
+    """vts_transcode_ext4: begins with TranscodeExt3; passed to
+    vts_transcode_ex by pointer cast with base.base.base.struct_size = sizeof(TranscodeExt4)."""
+    _fields_ = [("base", TranscodeExt3), ("cabac", C.c_int32), ("_pad2", C.c_int32)]
+
+
 class TranscodeExtInfo3(C.Structure):
     """vts_transcode_ext_info3: begins with TranscodeExtInfo2; as TranscodeExt3."""
     _fields_ = [("base", TranscodeExtInfo2), ("early_skip_mbs", C.c_int64), ("cmd_words", C.c_int64)]

@@ -264,7 +264,8 @@ class VideoScorer:
                   cut_threshold: float = 0.0, qp: int = 28, intra: bool = False,
                   subpel: int = 0, deblock: bool = False,
                   deblock_offsets: tuple[int, int] = (0, 0), mvcost: bool = False,
-                  early_skip: bool = False, mv_lambda16: int = 0, want_commands: bool = False) -> dict:
+                  early_skip: bool = False, mv_lambda16: int = 0, want_commands: bool = False,
+                  cabac: bool = False) -> dict:
         """360p upload transcode of this video into `out_path`
         (vts_transcode_ex): decode + score + area downscale +
         device H.264 encode with a quantised residual at `qp` (<= 0: none, the
@@ -285,7 +286,11 @@ class VideoScorer:
         search; both need `qp` > 0 and off, every byte is as before.
         `want_commands`: the result also holds `commands`, the encoder's
         final word per macroblock (vtseg.h) as a uint32 array (n_frames, mbh,
-        mbw).  Returns the facts (with `intra`, `subpel`, `deblock`, `mvcost`
+        mbw).  `cabac`: the slices are entropy coded with CABAC in a Main
+        profile stream instead of CAVLC in a Constrained Baseline one; the
+        coding is lossless, so every decision, count, command word and
+        `recon_hash` is that of the same call without it; needs `qp` > 0; off,
+        every byte is as before.  Returns the facts (with `intra`, `subpel`, `deblock`, `mvcost`
         or `early_skip` also the encoder's `recon_hash`) and per-stage
         milliseconds; with one of the last four keywords also
         `early_skip_mbs`."""
@@ -299,10 +304,11 @@ class VideoScorer:
         prm.qp = qp if qp > 0 else -1
         prm.intra = 1 if intra else 0
         info = _lib.TranscodeInfo()
-        ext = _lib.TranscodeExt3(
-            _lib.TranscodeExt2(_lib.TranscodeExt(C.sizeof(_lib.TranscodeExt3), subpel),
+        ext4 = _lib.TranscodeExt4(_lib.TranscodeExt3(
+            _lib.TranscodeExt2(_lib.TranscodeExt(C.sizeof(_lib.TranscodeExt4), subpel),
                                1 if deblock else 0, int(deblock_offsets[0]), int(deblock_offsets[1])),
-            1 if mvcost else 0, int(mv_lambda16), 1 if early_skip else 0)
+            1 if mvcost else 0, int(mv_lambda16), 1 if early_skip else 0), 1 if cabac else 0)
+        ext = ext4.base
         xinfo3 = _lib.TranscodeExtInfo3(_lib.TranscodeExtInfo2(
             _lib.TranscodeExtInfo(C.sizeof(_lib.TranscodeExtInfo3))))
         xinfo2 = xinfo3.base
@@ -317,7 +323,7 @@ class VideoScorer:
             ext.cmd_out = commands.ctypes.data_as(C.POINTER(C.c_uint32))
             ext.cmd_cap = commands.size
         _lib.check(self._lib.vts_transcode_ex(self._ctx, str(out_path).encode(), C.byref(prm),
-                                              C.cast(C.pointer(ext), C.POINTER(_lib.TranscodeExt)),
+                                              C.cast(C.pointer(ext4), C.POINTER(_lib.TranscodeExt)),
                                               C.byref(info),
                                               C.cast(C.pointer(xinfo3), C.POINTER(_lib.TranscodeExtInfo))))
         extra = {}
