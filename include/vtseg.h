@@ -203,7 +203,11 @@ int vts_add_tracks(const char *video_path, const char *src_path, const char *out
  * Frame i's Y plane starts at nv12 + i*frame_stride, its interleaved UV plane
  * at + pitch*uv_row_offset.  Outputs are device pointers; any may be NULL
  * except sad/score.  prev_luma (w*h bytes, device) seeds frame 0's SAD and
- * last_luma (w*h bytes, device, may be NULL) receives the last frame's Y'. */
+ * last_luma (w*h bytes, device, may be NULL) receives the last frame's Y'.
+ * Any width that k divides is scored; widths that are multiples of 16 (k = 6:
+ * of 48) take the fast kernels, others (cropped pictures such as 202 x 360)
+ * per-pixel kernels with the same results and a workspace of one thumbnail per
+ * frame (vts_score_workspace_bytes accounts for it). */
 typedef struct vts_score_desc {
   const uint8_t *nv12;       /* device                                      */
   int64_t frame_stride;      /* bytes between frames                        */
@@ -342,7 +346,12 @@ int vts_open_timings(const vts_ctx *ctx, double *ms, int32_t cap);
  * streams on the process's shared hardware queues, 1 streams with hardware
  * queues of their own: sessions opened beside others, at most 3 such sets
  * per device), 13 CABAC slices parsed in the windows' long-slice launches
- * (0: every window one parse launch); < 0 on error. */
+ * (0: every window one parse launch), 14 the intra kernel the general
+ * decoder's level launches run (2 h264_intra_v2, lane-parallel; 1
+ * h264_intra_full, by block: VTS_INTRA=1, or pictures whose level table does
+ * not fit the former's LDS; 0: subset decoder); < 0 on error.  Fields are
+ * only ever appended: a new index is no ABI break, and a library that does
+ * not know an index answers VTS_E_INVALID. */
 int64_t vts_schedule_info(const vts_ctx *ctx, int32_t what);  /* 8: general decoder in use (1/0) */
 int vts_close(vts_ctx *ctx);
 

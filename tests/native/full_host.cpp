@@ -132,6 +132,14 @@ extern "C" int fh_scale(const char *path, int32_t *ls4, int32_t *ls8, int *flags
   return 0;
 }
 
+// the session's shape guard (h264_sched.cpp general_shape_error): 0 when the
+// general decoder takes mbw x mbh macroblocks, else 1 and the reason in err
+extern "C" int fh_shape_error(int mbw, int mbh, char *err, int err_cap) {
+  const std::string e = general_shape_error(mbw, mbh);
+  std::snprintf(err, static_cast<size_t>(err_cap), "%s", e.c_str());
+  return e.empty() ? 0 : 1;
+}
+
 extern "C" int fh_decode(const char *path, int flags, uint8_t *out, int64_t out_cap, int64_t *n_out,
                          int *w_out, int *h_out, char *err, int err_cap) {
   auto bad = [&](const std::string &m) {

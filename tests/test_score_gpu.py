@@ -48,6 +48,14 @@ CASES = [
     (320, 240, 384, 256, 2, 7),
     (320, 240, 320, 240, 8, 6),
     (160, 96, 160, 96, 4, 1100),  # > 512 frames: multi-frame runs + seam kernel
+    # display widths that are no whole chunks of 16 (k = 6: 48) row bytes, as every cropped-width
+    # picture has: the per-pixel kernels (thumb_any, sad_any)
+    (72, 128, 80, 128, 4, 21),    # the device encoder's portrait output; thumbnail rows of 18
+    (88, 72, 96, 80, 2, 9),       # both crops; 44 x 36
+    (88, 72, 96, 80, 8, 5),       # 11 x 9: odd thumbnail size
+    (202, 360, 208, 368, 2, 7),   # scale=-2:360 of 1080x1920
+    (100, 64, 128, 64, 4, 3),
+    (120, 96, 128, 96, 6, 1100),  # k = 6 off its 48-byte chunks; more frames than grid rows of one run each
 ]
 
 
@@ -74,13 +82,22 @@ def test_score_kernel_bit_exact_vs_oracle(width, height, pitch, coded, k, n):
 def test_score_kernel_prev_luma_continuity():
     """Scoring a batch in two halves with prev_luma = first half's last_luma
     equals scoring it whole (the streaming window contract)."""
+    _prev_luma_continuity(640, 640)
+
+
+def test_score_kernel_prev_luma_continuity_any_width():
+    """The same contract through the per-pixel kernels (200 is no multiple of 16)."""
+    _prev_luma_continuity(200, 208)
+
+
+def _prev_luma_continuity(width, pitch):
     torch = _torch()
     from vtseg import scene
     rng = np.random.default_rng(7)
-    width, height, k, n = 640, 360, 4, 600
-    host, stride = smooth_nv12(rng, n, width, height, width, height + height // 2, height)
+    height, k, n = 360, 4, 600
+    host, stride = smooth_nv12(rng, n, width, height, pitch, height + height // 2, height)
     dev = torch.from_numpy(host).cuda()
-    kw = dict(width=width, height=height, pitch=width, uv_row_offset=height,
+    kw = dict(width=width, height=height, pitch=pitch, uv_row_offset=height,
               frame_stride=stride, k=k, want_rgb=False)
     whole = scene.score_nv12(dev, n_frames=n, **kw)
     a = scene.score_nv12(dev[: 250 * stride], n_frames=250, **kw)
@@ -97,8 +114,8 @@ def test_score_kernel_rejects_bad_geometry():
     from vtseg import VtsegError, scene
     dev = torch.zeros(1 << 20, dtype=torch.uint8, device="cuda")
     with pytest.raises(VtsegError):
-        scene.score_nv12(dev, width=100, height=64, pitch=128, uv_row_offset=64,
-                         frame_stride=128 * 96, n_frames=1, k=4)  # width % 16 != 0
+        scene.score_nv12(dev, width=102, height=64, pitch=128, uv_row_offset=64,
+                         frame_stride=128 * 96, n_frames=1, k=4)  # width % k != 0
     with pytest.raises(VtsegError):
         scene.score_nv12(dev, width=128, height=64, pitch=128, uv_row_offset=64,
                          frame_stride=128 * 96, n_frames=1, k=3)

@@ -39,6 +39,10 @@ SOURCES.update({
     # kind; a constant picture, where every decision is a tie
     "crafted": crafted_frames,
     "flat": lambda: np.full((6, 96, 96), 128, np.uint8),
+    # display widths that are no multiple of 16 (crop_r != 0), what every portrait upload
+    # gives: 144x256 -> 72x128 coded 80x128; 176x144 -> 88x72 coded 96x80 (both crops)
+    "portrait": dict(width=144, height=256, n_frames=20),
+    "qcif": dict(width=176, height=144, n_frames=20),
 })
 ALL_ON = dict(intra=True, subpel=2, deblock=True)
 S70 = dict(height=96)
@@ -84,6 +88,16 @@ for _i in (False, True):
         f"qp51{_s}": ("s40", dict(S70, qp=51, deblock=True, deblock_offsets=(6, 6), intra=_i)),   # index clipping at 51
         f"soft{_s}": ("s70", dict(S70, deblock=True, deblock_offsets=(-6, -6), intra=_i)),        # indexA exactly 16
         f"lowqp_on{_s}": ("s40", dict(S70, qp=12, deblock=True, deblock_offsets=(2, 2), intra=_i)),  # 16 from below
+    })
+# a right edge that is coded but not displayed: downscale padding, search-window
+# clamping, Intra16x16 and deblocking there
+CROPPED_WIDTH = {"portrait": (128, (72, 128, 80, 128)), "qcif": (72, (88, 72, 96, 80))}
+for _s, (_h, _) in CROPPED_WIDTH.items():
+    CASES.update({
+        f"{_s}_off": (_s, dict(height=_h)),
+        f"{_s}_all": (_s, dict(height=_h, **ALL_ON)),
+        f"{_s}_r16_all": (_s, dict(height=_h, search_range=16, **ALL_ON)),
+        f"{_s}_qp40_all": (_s, dict(height=_h, qp=40, **ALL_ON)),
     })
 COLUMN = dict(height=48, search_range=4, **ALL_ON)
 
@@ -196,6 +210,19 @@ def test_optin_paths_write_the_oracles_bytes(work, tmp_path, case):
     _require_gpu()
     sname, tk = CASES[case]
     _check(work, sname, tk, tmp_path / "out.mp4")
+
+
+@pytest.mark.parametrize("sname", list(CROPPED_WIDTH))
+def test_cropped_width_pictures(work, tmp_path, sname):
+    """The display width is no multiple of 16: the coded picture has columns
+    past the display's right edge, and with all paths on every macroblock kind
+    and the filter occur (the bytes themselves: the *_off / *_all cases)."""
+    _require_gpu()
+    h, geometry = CROPPED_WIDTH[sname]
+    facts, ref = _check(work, sname, dict(height=h, **ALL_ON), tmp_path / "out.mp4")
+    assert (ref["width"], ref["height"], ref["coded_width"], ref["coded_height"]) == geometry
+    assert ref["coded_width"] > ref["width"]
+    assert facts["intra_mbs"] > 0 and facts["inter_mbs"] > 0 and facts["deblock_mbs"] > 0
 
 
 def test_one_macroblock_wide_picture(work, tmp_path):

@@ -64,6 +64,9 @@ CASES = {
     "crafted_qp12_every": ("crafted", dict(height=64, qp=12, **EVERY)),
     "crafted_off": ("crafted", dict(height=64)),
     "flat_every": ("flat", dict(height=64, **EVERY)),
+    # display widths that are no multiple of 16: 72x128 coded 80x128, 88x72 coded 96x80
+    "portrait_every": ("portrait", dict(height=128, **EVERY)),
+    "qcif_every": ("qcif", dict(height=72, **EVERY)),
 }
 SAME = ("width", "height", "n_frames", "n_idr", "pcm_mbs", "inter_mbs", "skip_mbs", "intra_mbs", "subpel_mbs",
         "qpel_mbs", "deblock_mbs", "early_skip_mbs", "recon_hash")

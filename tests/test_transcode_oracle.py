@@ -246,6 +246,25 @@ def test_oracle_two_by_two_macroblocks(tmp_path):
     assert r["deblock_mbs"] > 0
 
 
+@pytest.mark.parametrize("on", [0, 1], ids=["off", "all_on"])
+@pytest.mark.parametrize("name,W,H,h,geometry", [("portrait", 144, 256, 128, (72, 128, 80, 128)),
+                                                 ("qcif", 176, 144, 72, (88, 72, 96, 80))])
+def test_oracle_cropped_width(tmp_path, name, W, H, h, geometry, on):
+    """A display width that is no multiple of 16 (what every portrait upload
+    gives): the coded picture has columns right of the display edge, filled by
+    the downscale's padding, searched, predicted and filtered like the rest
+    and cropped by the SPS.  The sources of the byte tests
+    (tests/test_transcode_bytes_gpu.py `portrait`, `qcif`)."""
+    p = tmp_path / f"{name}.mp4"
+    scene.synth_write(p, width=W, height=H, n_frames=20, cut_min_s=0.7, cut_max_s=1.5, gop_max_s=0.5)
+    frames, _ = oracle.decode_file(p)
+    sc = oracle.score_frames(frames.reshape(-1), frames[0].size, 20, W, H, W, H, 4, want_rgb=False)["score"]
+    r = _closed_loop(tmp_path, frames, W, H, sc, out_height=h, intra=on, subpel=2 * on, deblock=on)
+    assert (r["width"], r["height"], r["coded_width"], r["coded_height"]) == geometry
+    if on:
+        assert r["deblock_mbs"] > 0
+
+
 def crafted_frames(F=12, W=96, H=64, seed=11):
     """Display-size NV12 frames (samples >= 1) whose P pictures need every
     decision: per macroblock and frame a ramp (the motion search predicts it),

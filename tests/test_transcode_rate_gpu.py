@@ -72,6 +72,9 @@ LOOP.update({
     "column_both_all": ("column", dict(height=48, search_range=4, **ALL_ON, **MODES["both"])),  # mx = 0 everywhere
     "real_both_all": ("real", dict(height=240, **ALL_ON, **MODES["both"])),
     "content_both_all": ("content", dict(**ALL_ON, **MODES["both"])),
+    # display widths that are no multiple of 16: 72x128 coded 80x128, 88x72 coded 96x80
+    "portrait_both_all": ("portrait", dict(height=128, **ALL_ON, **MODES["both"])),
+    "qcif_both_all": ("qcif", dict(height=72, **ALL_ON, **MODES["both"])),
 })
 
 

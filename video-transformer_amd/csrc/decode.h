@@ -111,5 +111,9 @@ int clear_accum_launch(uint32_t *hist, uint64_t *sad, int64_t n_frames, hipStrea
 int score_launch(const vts_score_desc *d, hipStream_t stream);
 int thumb_pics_launch(const PicThumbArgs &a, int k, hipStream_t s);
 int64_t score_workspace_bytes(int32_t width, int32_t height, int32_t k, int64_t n_frames);
+// the display width is whole chunks of the chunked scoring kernels (score_runs,
+// thumb_pics: 16 row bytes, k = 6: 48); other widths are scored by
+// score_launch's per-pixel kernels only
+bool score_chunked_width(int width, int k);
 
 }  // namespace vts

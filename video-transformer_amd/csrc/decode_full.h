@@ -107,5 +107,9 @@ int bs_full_launch(const FullReconArgs &a, int n_frames, hipStream_t s);
 // reconstruction (+ deblocking from bs_full_launch's descriptors when
 // a.deblock) of n_frames pictures of one level
 int recon_full_launch(const FullReconArgs &a, int n_frames, hipStream_t s, hipEvent_t after_inter = nullptr);
+// the intra kernel recon_full_launch runs for FullReconArgs.intra_kernel on a
+// picture of mbw x mbh macroblocks: 2 h264_intra_v2 (lane-parallel) while its
+// LDS fits, else 1 h264_intra_full (by block)
+int intra_kernel_for(int intra_kernel, int mbw, int mbh);
 
 }  // namespace vts

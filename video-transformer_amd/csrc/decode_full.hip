@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dbk_sched.h"
 #include "decode_full.h"
 #if !defined(__HIP_DEVICE_COMPILE__)
 #endif
@@ -47,18 +48,17 @@ constexpr int kInterThreads = 256;   // 16 macroblocks x 16 blocks
 #ifndef VTS_INTRA_THREADS
 #define VTS_INTRA_THREADS 512
 #endif
-#ifndef VTS_DBK_THREADS
-#define VTS_DBK_THREADS 1024
-#endif
 constexpr int kIntraThreads = VTS_INTRA_THREADS;  // 512: 32 macroblocks in flight (2 waves per SIMD, <= 256 VGPRs)
 constexpr int kIntraSlots = kIntraThreads / 16;
 constexpr int kIntraLevels = 512;  // intra dependency levels bucketed in LDS (more: one scan per level)
-constexpr int kDbkThreads = VTS_DBK_THREADS;      // 1024: 16 waves = 16 row pairs in flight
-constexpr int kDbkWaves = kDbkThreads / 64;
-// (a 256-thread build, 16 rows in flight, hung on the noise stream: its ring
-// hand-off between waves needs more rows in flight than one pass of 4 waves;
-// 512 ran, no faster: profiles/r06ar_*)
-static_assert(kDbkThreads >= 512 && kDbkThreads <= 1024 && kDbkThreads % 64 == 0, "deblocking workgroup size");
+constexpr int kDbkThreads = dbk::kThreads;        // VTS_DBK_THREADS, 1024: 16 waves of 4 macroblock rows in flight
+constexpr int kDbkWaves = dbk::kWaves;
+// (a 256-thread build, 16 rows in flight, hung on the 720p noise stream:
+// the pass-start wait closes a cycle with the ring hand-off once the picture
+// is wide enough for its wave count, dbk_sched.h; 512 ran, no faster:
+// profiles/r06ar_*.  dbk_sched.h refuses a wave count that would deadlock at
+// 3840x2160 at compile time, general_shape_error() the shapes the shipped
+// one would deadlock on at open.)
 // experiment hook: per-workgroup start / end of the one-workgroup-per-picture
 // kernels (tools/exp/wg_trace.h); nothing in the product build
 #ifndef VTS_WG_TRACE
@@ -1721,8 +1721,8 @@ int derive_launch(const DeriveArgs &a, int n_pictures, hipStream_t s) {
 // finishes excepted), ring lines for the row below; the four rows of a wave
 // run in lockstep two macroblocks apart, a wave's first row waits for the
 // previous wave's last through prog[].
-constexpr int kDpGroups = kDbkThreads / 16;
-constexpr int kDpRingCols = 16;
+constexpr int kDpGroups = dbk::dp_rows_in_flight(kDbkWaves);
+constexpr int kDpRingCols = dbk::dp_ring_cols(kDbkWaves);
 struct DpTileY {
   uint8_t s[20][20];  // rows -4..15 x cols -4..15
 };
@@ -1771,8 +1771,13 @@ __device__ __forceinline__ void dp_plane(const FullReconArgs &a, int slot, int d
                                 : uvo + static_cast<uint32_t>((ya * 8 + row) * pitch);
     const DbkInfo *const drow = fdbk + ya * mbw;
     // this row's ring slot was the row kDpGroups above's: its consumer must be done
+    // (dbk::dp_waits_at_start(y), spelled with the constant: the call inside
+    // the && compiles to other, equivalent, scalar code)
+    static_assert(dbk::dp_waits_at_start(kDpGroups, kDbkWaves) && !dbk::dp_waits_at_start(kDpGroups - 1, kDbkWaves),
+                  "pass-start wait");
     if (row_ok && y - kDpGroups >= 0) {
-      while (__hip_atomic_load(&prog[y - kDpGroups + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < mbw + 1)
+      while (__hip_atomic_load(&prog[dbk::dp_start_row(y, kDbkWaves)], __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_WORKGROUP) < dbk::dp_done(mbw))
         __builtin_amdgcn_s_sleep(1);
     }
     uint32_t left = 0;   // carried cols 12..15 of the previous macroblock (this lane's row)
@@ -1780,7 +1785,7 @@ __device__ __forceinline__ void dp_plane(const FullReconArgs &a, int slot, int d
     const uint4 *dq = reinterpret_cast<const uint4 *>(drow);
     uint4 nbs = dq[0], nv = dq[vq], nh = dq[hq];
     uint4 npx = *reinterpret_cast<const uint4 *>(at(rowo));
-    constexpr int kLag = 2;
+    constexpr int kLag = dbk::dp_lag(kDbkWaves);
     for (int it = 0; it < mbw + 3 * kLag; ++it) {
       const int x = it - kLag * grp;
       const bool act = row_ok && x >= 0 && x < mbw;
@@ -1797,8 +1802,8 @@ __device__ __forceinline__ void dp_plane(const FullReconArgs &a, int slot, int d
       // row waits until it may overwrite ring column x (the next wave's first
       // row read column x - kDpRingCols)
       if (act) {
-        const int need_up = (grp == 0 && y > 0) ? (x + 1 < mbw ? x + 2 : mbw + 1) : -(1 << 30);
-        const int need_dn = (grp == 3 && y + 1 < mbh) ? x - kDpRingCols + 1 : -(1 << 30);
+        const int need_up = dbk::dp_need_up(grp, y, x, mbw);
+        const int need_dn = dbk::dp_need_dn(grp, y, x, mbh, kDbkWaves);
         const int *pu = &prog[y > 0 ? y - 1 : 0], *pd = &prog[y + 1 < mbh ? y + 1 : y];
         while (__hip_atomic_load(pu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < need_up ||
                __hip_atomic_load(pd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < need_dn)
@@ -1946,7 +1951,7 @@ __device__ __forceinline__ void dp_plane(const FullReconArgs &a, int slot, int d
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       __builtin_amdgcn_wave_barrier();
       if (act && l == 0) {
-        __hip_atomic_store(&prog[y], x + 1 < mbw ? x + 1 : mbw + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_store(&prog[y], dbk::dp_publish(x, mbw), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
     }
   }
@@ -1974,6 +1979,10 @@ int bs_full_launch(const FullReconArgs &a, int n_frames, hipStream_t s) {
   return VTS_OK;
 }
 
+int intra_kernel_for(int intra_kernel, int mbw, int mbh) {
+  return (intra_kernel != 1 && i2_lds_bytes(mbw, mbh) <= 160 * 1024) ? 2 : 1;
+}
+
 int recon_full_launch(const FullReconArgs &a, int n_frames, hipStream_t s, hipEvent_t after_inter) {
   if (n_frames <= 0) return VTS_OK;
   const int nmb = a.P.mb_width * a.P.mb_height;
@@ -1985,7 +1994,7 @@ int recon_full_launch(const FullReconArgs &a, int n_frames, hipStream_t s, hipEv
   if (after_inter && hipEventRecord(after_inter, s) != hipSuccess) return fail(VTS_E_HIP, "hipEventRecord after h264_inter_full");
   // lane-parallel intra (default) while its LDS fits, else the by-block kernel
   const size_t i2_lds = i2_lds_bytes(a.P.mb_width, a.P.mb_height);
-  if (a.intra_kernel != 1 && i2_lds <= 160 * 1024) {
+  if (intra_kernel_for(a.intra_kernel, a.P.mb_width, a.P.mb_height) == 2) {
     hipLaunchKernelGGL(h264_intra_v2, dim3(n_frames), dim3(kI2Threads), i2_lds, s, a);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(VTS_E_HIP, "h264_intra_v2 launch: %s", hipGetErrorString(e));

@@ -6,6 +6,7 @@
 // modification), 8.2.5 (IDR, sliding window, MMCO 1-6).
 #include "h264_sched.h"
 
+#include "dbk_sched.h"
 #include "h264_cabac_tables.h"
 #include "h264_tables.h"
 
@@ -162,6 +163,23 @@ void scale_tab_build(const uint8_t (*w4)[16], const uint8_t (*w8)[64], ScaleTab 
       for (int k = 0; k < 64; ++k) {
         t->ls8[l][m][k] = w8[l][k] * n8[m][vts_norm8_class(k >> 3, k & 7)];
       }
+}
+
+std::string general_shape_error(int mbw, int mbh) {
+  char b[200];
+  if (mbh > dbk::kMaxMbHeight) {
+    std::snprintf(b, sizeof b, "picture of %d macroblock rows: the general decoder takes at most %d (h264_derive)", mbh,
+                  dbk::kMaxMbHeight);
+    return b;
+  }
+  if (!dbk::dp_shape_ok(mbw, mbh, dbk::kWaves)) {
+    std::snprintf(b, sizeof b,
+                  "picture of %d x %d macroblocks: with more than %d macroblock rows the general decoder's "
+                  "deblocking hand-off takes at most %d macroblocks per row (dbk_sched.h)",
+                  mbw, mbh, dbk::dp_rows_in_flight(dbk::kWaves), dbk::dp_first_bad_width(mbh, dbk::kWaves) - 1);
+    return b;
+  }
+  return {};
 }
 
 std::string sched_stream_facts(const std::vector<uint8_t> &sps_nal, const std::vector<uint8_t> &pps_nal,

@@ -66,6 +66,13 @@ void scale_tab_build(const uint8_t (*w4)[16], const uint8_t (*w8)[64], ScaleTab 
 std::string sched_stream_facts(const std::vector<uint8_t> &sps_nal, const std::vector<uint8_t> &pps_nal,
                                const Sps &sps, const Pps &pps, SchedStream *out);
 
+// "" or why the general decoder's kernels cannot take a picture of mbw x mbh
+// macroblocks: more rows than h264_derive has lanes for, or a shape on which
+// the deblocking wavefront's hand-off never finishes (dbk_sched.h
+// dp_shape_ok at the built wave count).  Host only; checked at open before
+// anything is launched.
+std::string general_shape_error(int mbw, int mbh);
+
 // frames: per sample (access unit) the byte range [off, off + size) of its
 // AVCC NAL units (nal_length_size prefix) inside `es`.  "" or the reason.
 std::string sched_build(const Sps &sps, const Pps &pps, const uint8_t *es, const std::vector<int64_t> &off,

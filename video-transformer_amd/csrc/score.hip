@@ -24,6 +24,8 @@
 //   * the first frame of each run (other than run 0) gets its SAD from a tiny
 //     seam kernel that compares the run's head thumbnail with the previous
 //     run's tail thumbnail.
+// Display widths that are not whole chunks (no multiple of 16 bytes, k = 6:
+// 48) take thumb_any + sad_any instead: one thread per thumbnail pixel.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -436,11 +438,134 @@ __global__ void __launch_bounds__(kThumbThreads) thumb_pics(PicThumbArgs a) {
 
 int row_bytes_for(int k) { return k == 6 ? 48 : 16; }
 
+// ---- any width.  The kernels above work in chunks of 16 (k = 6: 48) row
+// bytes, so they take display widths that are multiples of that.  Other
+// widths (a portrait upload scaled to 202 x 360, say) take these two: one
+// thread per thumbnail pixel, the thumbnails' luma kept in the workspace, then
+// one workgroup per frame for the SAD against the thumbnail before.  Same
+// arithmetic, same outputs; plain byte loads, not the hot path.
+struct AnyArgs {
+  const uint8_t *nv12;
+  int64_t frame_stride;
+  int64_t n_frames;
+  int32_t w, h;            // thumbnail size
+  int32_t pitch, uv_row_offset;
+  uint8_t *rgb;
+  uint32_t *hist;          // zeroed before thumb_any
+  uint64_t *sad;
+  float *score;
+  const uint8_t *prev_luma;
+  uint8_t *last_luma;
+  uint8_t *thumbs;         // n_frames * w*h
+};
+
+template <int K>
+__global__ void __launch_bounds__(256) thumb_any(AnyArgs a) {
+  using G = Geo<K>;
+  const int64_t npx = static_cast<int64_t>(a.w) * a.h;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= npx) return;
+  const int ty = static_cast<int>(i / a.w), tx = static_cast<int>(i - static_cast<int64_t>(ty) * a.w);
+  for (int64_t f = blockIdx.y; f < a.n_frames; f += gridDim.y) {
+    const uint8_t *yplane = a.nv12 + f * a.frame_stride;
+    const uint8_t *uvplane = yplane + static_cast<int64_t>(a.pitch) * a.uv_row_offset;
+    uint32_t ys = 0, us = 0, vs = 0;
+    for (int r = 0; r < K; ++r) {
+      const uint8_t *p = yplane + static_cast<int64_t>(ty * K + r) * a.pitch + tx * K;
+      for (int c = 0; c < K; ++c) ys += p[c];
+    }
+    for (int r = 0; r < G::kH; ++r) {
+      const uint8_t *p = uvplane + static_cast<int64_t>(ty * G::kH + r) * a.pitch + tx * K;
+      for (int c = 0; c < G::kH; ++c) {
+        us += p[2 * c];
+        vs += p[2 * c + 1];
+      }
+    }
+    const uint32_t y = (ys + G::kYDiv / 2) / G::kYDiv;
+    const uint32_t u = (us + G::kCDiv / 2) / G::kCDiv;
+    const uint32_t v = (vs + G::kCDiv / 2) / G::kCDiv;
+    a.thumbs[f * npx + i] = static_cast<uint8_t>(y);
+    if (a.rgb) {
+      const uint32_t c = bt709_rgb24(y, u, v);
+      uint8_t *dst = a.rgb + (f * npx + i) * 3;
+      dst[0] = static_cast<uint8_t>(c);
+      dst[1] = static_cast<uint8_t>(c >> 8);
+      dst[2] = static_cast<uint8_t>(c >> 16);
+    }
+    if (a.hist) atomicAdd(&a.hist[f * 256 + y], 1u);
+  }
+}
+
+__global__ void __launch_bounds__(256) sad_any(AnyArgs a) {
+  __shared__ uint64_t red[4];
+  const int64_t npx = static_cast<int64_t>(a.w) * a.h;
+  for (int64_t f = blockIdx.x; f < a.n_frames; f += gridDim.x) {
+    const uint8_t *cur = a.thumbs + f * npx;
+    const uint8_t *prev = f > 0 ? cur - npx : a.prev_luma;
+    uint64_t s = 0;
+    if (prev)
+      for (int64_t i = threadIdx.x; i < npx; i += 256) {
+        const int d = static_cast<int>(cur[i]) - static_cast<int>(prev[i]);
+        s += static_cast<uint64_t>(d < 0 ? -d : d);
+      }
+    if (f == a.n_frames - 1 && a.last_luma)
+      for (int64_t i = threadIdx.x; i < npx; i += 256) a.last_luma[i] = cur[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const uint64_t total = red[0] + red[1] + red[2] + red[3];
+      a.sad[f] = prev ? total : 0;
+      a.score[f] = prev ? static_cast<float>(static_cast<double>(total) / (static_cast<double>(npx) * 255.0)) : 0.0f;
+    }
+    __syncthreads();
+  }
+}
+
+int score_any_launch(const vts_score_desc *d, hipStream_t stream) {
+  AnyArgs a{};
+  a.nv12 = d->nv12;
+  a.frame_stride = d->frame_stride;
+  a.n_frames = d->n_frames;
+  a.w = d->width / d->k;
+  a.h = d->height / d->k;
+  a.pitch = d->pitch;
+  a.uv_row_offset = d->uv_row_offset;
+  a.rgb = d->rgb;
+  a.hist = d->hist;
+  a.sad = d->sad;
+  a.score = d->score;
+  a.prev_luma = d->prev_luma;
+  a.last_luma = d->last_luma;
+  a.thumbs = d->workspace;
+  if (d->hist && hipMemsetAsync(d->hist, 0, static_cast<size_t>(d->n_frames) * 256 * sizeof(uint32_t), stream) != hipSuccess)
+    return fail(VTS_E_HIP, "hipMemsetAsync of the histograms");
+  const int64_t npx = static_cast<int64_t>(a.w) * a.h;
+  const unsigned fy = static_cast<unsigned>(std::min<int64_t>(d->n_frames, 65535));
+  const dim3 grid(static_cast<unsigned>((npx + 255) / 256), fy);
+  switch (d->k) {
+    case 2: hipLaunchKernelGGL(thumb_any<2>, grid, dim3(256), 0, stream, a); break;
+    case 4: hipLaunchKernelGGL(thumb_any<4>, grid, dim3(256), 0, stream, a); break;
+    case 6: hipLaunchKernelGGL(thumb_any<6>, grid, dim3(256), 0, stream, a); break;
+    default: hipLaunchKernelGGL(thumb_any<8>, grid, dim3(256), 0, stream, a); break;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(VTS_E_HIP, "thumb_any launch: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(sad_any, dim3(fy), dim3(256), 0, stream, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail(VTS_E_HIP, "sad_any launch: %s", hipGetErrorString(e));
+  return VTS_OK;
+}
+
 }  // namespace
+
+bool score_chunked_width(int width, int k) { return width % row_bytes_for(k) == 0; }
 
 int64_t score_workspace_bytes(int32_t width, int32_t height, int32_t k, int64_t n_frames) {
   if (k <= 0) return 0;
   const int64_t npx = static_cast<int64_t>(width / k) * (height / k);
+  if (!score_chunked_width(width, k)) return (n_frames > 0 ? n_frames : 1) * npx + 256;  // every frame's thumbnail
   const int64_t runs = n_frames < kMaxRuns ? (n_frames > 0 ? n_frames : 1) : kMaxRuns;
   return 2 * runs * npx + 256;
 }
@@ -453,8 +578,6 @@ int score_launch(const vts_score_desc *d, hipStream_t stream) {
     return fail(VTS_E_INVALID, "width/height (%d x %d) must be positive multiples of k=%d",
                 d->width, d->height, k);
   const int rb = row_bytes_for(k);
-  if (d->width % rb)
-    return fail(VTS_E_INVALID, "width %d must be a multiple of %d for k=%d", d->width, rb, k);
   if (d->pitch < d->width || d->pitch % 16)
     return fail(VTS_E_INVALID, "pitch must be >= width and a multiple of 16");
   if (d->uv_row_offset < d->height) return fail(VTS_E_INVALID, "uv_row_offset < height");
@@ -471,6 +594,12 @@ int score_launch(const vts_score_desc *d, hipStream_t stream) {
   if (d->n_frames == 0) return VTS_OK;
   const int w = d->width / k, h = d->height / k;
   const int64_t npx = static_cast<int64_t>(w) * h;
+  if (d->width % rb) {  // no whole chunks: the per-pixel kernels
+    const int64_t need_any = score_workspace_bytes(d->width, d->height, k, d->n_frames);
+    if (d->workspace_bytes < need_any)
+      return fail(VTS_E_INVALID, "workspace needs %lld bytes", static_cast<long long>(need_any));
+    return score_any_launch(d, stream);
+  }
   const size_t lds = 1024 + 64 + static_cast<size_t>((npx + 15) & ~int64_t(15));
   if (lds > 160 * 1024)
     return fail(VTS_E_INVALID, "thumbnail %dx%d too large for LDS; use a larger k", w, h);

@@ -42,6 +42,7 @@
 #include "common.h"
 #include "decode.h"
 #include "h264.h"
+#include "h264_sched.h"
 #include "mp4.h"
 #include "session.h"
 
@@ -737,6 +738,13 @@ int build(vts_ctx *c, const Mp4Info &mp4, const uint8_t *mem, int64_t mem_size, 
   // (subset only, or auto unless reordering or the parameter sets already
   // send the stream to the general decoder: wants_general's first checks)
   const bool may_subset = c->params.decoder == 1 || (c->params.decoder == 0 && !reorder && !general_by_headers(c));
+  // a stream bound for the general decoder whose picture shape its kernels
+  // cannot take is refused here, before the first HIP call (build_general
+  // checks again for the streams auto mode sends there later)
+  if (!may_subset) {
+    const std::string se = general_shape_error(c->sps.mb_width, c->sps.mb_height);
+    if (!se.empty()) return fail(VTS_E_UNSUPPORTED, "%s", se.c_str());
+  }
   // the ES's device buffer first: each piece goes up as soon as it is read
   {
     int64_t total = 0;
@@ -1662,6 +1670,8 @@ extern "C" int64_t vts_schedule_info(const vts_ctx *c, int32_t what) {
       for (const Window &w : c->windows) n += w.plong;
       return n;
     }
+    case 14:  // general decoder: the intra kernel its level launches run (0: subset decoder)
+      return c->general ? intra_kernel_for(c->intra_kernel, c->fprm.mb_width, c->fprm.mb_height) : 0;
     default: return fail(VTS_E_INVALID, "unknown schedule field %d", what);
   }
 }

@@ -97,6 +97,9 @@ int build_general(vts_ctx *c, const uint8_t *es, const std::vector<int64_t> &es_
   SchedStream facts;
   std::string e = sched_stream_facts(sps_nal, pps_nal, c->sps, c->pps, &facts);
   if (!e.empty()) return fail(VTS_E_UNSUPPORTED, "%s", e.c_str());
+  // shapes the kernels must never be launched on (the deblocking hand-off would spin for ever)
+  e = general_shape_error(c->sps.mb_width, c->sps.mb_height);
+  if (!e.empty()) return fail(VTS_E_UNSUPPORTED, "%s", e.c_str());
   if (c->sps.crop_left || c->sps.crop_top) return fail(VTS_E_UNSUPPORTED, "left/top cropping is not supported");
   std::vector<SchedFrame> frames;
   std::vector<SchedSlice> slices;
@@ -233,10 +236,13 @@ int build_general(vts_ctx *c, const uint8_t *es, const std::vector<int64_t> &es_
   c->arena_bound = 0;
   c->arena_reruns = 0;
   // recycled surfaces: only where no caller reads a decoded frame back (no
-  // keep_frames, no transcode yet); VTS_SURF_POOL=0 keeps one surface per slot
+  // keep_frames, no transcode yet); VTS_SURF_POOL=0 keeps one surface per slot.
+  // thumb_pics works in whole chunks of row bytes: a display width that is
+  // not (a cropped width) keeps its surfaces and is scored at the window's end
   {
     const char *sp = std::getenv("VTS_SURF_POOL");
-    c->surf_pool = c->params.keep_frames == 0 && !c->small.on && !(sp && std::atoi(sp) == 0);
+    c->surf_pool = c->params.keep_frames == 0 && !c->small.on && !(sp && std::atoi(sp) == 0) &&
+                   score_chunked_width(c->width, c->k);
   }
   c->surf_of.assign(static_cast<size_t>(c->surf_pool ? n : 0), 0);
   c->surf_count = 0;
