@@ -414,7 +414,8 @@ void vts_batch_free(vts_batch *b);
  * an area filter downscales it to (w, height) with w = ffmpeg's scale=-2
  * width, and a device encoder writes H.264 Constrained Baseline (CAVLC; Main
  * with CABAC when vts_transcode_ext4.cabac = 1): IDR (all
- * I_PCM, or Intra16x16 with intra = 1) every keyint frames (and at scene cuts
+ * I_PCM, or Intra16x16 with intra = 1, or Intra16x16 / Intra_4x4 with
+ * vts_transcode_ext5.intra4x4 = 1 as well) every keyint frames (and at scene cuts
  * if asked), P pictures of full-search
  * integer motion (P_L0_16x16 / P_Skip; refined to half or quarter samples
  * with vts_transcode_ext.subpel; vector cost and early P_Skip with
@@ -459,8 +460,10 @@ typedef struct vts_transcode_info {
   double ms[4];            /* decode+score+downscale (host clock), motion
                               search span (stream 1), slice writing span
                               (stream 2, overlaps the searches), MP4 mux      */
-  int64_t intra_mbs;       /* Intra16x16 macroblocks (intra = 1); pcm_mbs counts
-                              only the macroblocks that stayed I_PCM           */
+  int64_t intra_mbs;       /* Intra16x16 macroblocks (intra = 1), and with
+                              vts_transcode_ext5.intra4x4 the I_NxN ones too;
+                              pcm_mbs counts only the macroblocks that stayed
+                              I_PCM                                            */
   uint64_t recon_hash;     /* intra = 1, subpel != 0 or deblock = 1: the encoder's own
                               reconstruction, hashed as
                               vts_synth_info.recon_hash (display-size NV12, f =
@@ -584,6 +587,45 @@ typedef struct vts_transcode_ext4 {
   int32_t cabac;           /* 0 CAVLC (every output byte as before), 1 CABAC    */
   int32_t _pad2;
 } vts_transcode_ext4;
+
+/* Intra_4x4 coding of intra macroblocks, DESIGN.md §11 "Intra4x4".  As the
+ * structs above: begun with them, passed by pointer cast, struct_size = their
+ * own sizeof.  Read: intra4x4 when struct_size >= 68, i4_out at >= 80, i4_cap
+ * at >= 88 (a 64-byte vts_transcode_ext4 or anything smaller: off / NULL);
+ * written: intra4x4_mbs at >= 56, i4_words at >= 64.
+ * intra4x4 = 1 (needs intra = 1 and residual coding): every macroblock that
+ * intra = 1 would code as Intra16x16 or leave I_PCM is also tried as I_NxN
+ * with sixteen Intra_4x4 blocks and becomes that when its CAVLC bits are
+ * strictly fewer than the Intra16x16 candidate's (chroma is the same for
+ * both); the winner is coded when it takes no more bits than I_PCM.  A slice
+ * is one macroblock row, so a block has samples above it only inside its own
+ * macroblock: the top four blocks choose among Horizontal, DC and
+ * Horizontal_Up (DC alone at mx = 0), the other twelve among all nine modes
+ * (column 0 at mx = 0: Vertical, DC, Diagonal_Down_Left, Vertical_Left), by
+ * 16 SAD + lambda16(qp) * bits of the mode's code, ties to the lower mode.
+ * vts_transcode_info.intra_mbs counts Intra16x16 and I_NxN macroblocks
+ * together; intra4x4_mbs is the I_NxN share.
+ * Command word of an I_NxN macroblock: 0x80004000 | intra_chroma_pred_mode
+ * << 2 | coded_block_pattern << 4 (bits 0..1 zero).  i4_out[frame][my][mx]:
+ * nibble k of an I_NxN macroblock's word is the Intra4x4PredMode of
+ * luma4x4BlkIdx k; every other macroblock's word is ~0.
+ * VTS_E_INVALID, the field named: intra4x4 not 0 or 1, intra4x4 = 1 with
+ * intra = 0 or qp < 0.  VTS_E_CAPACITY before any encoding: i4_out with
+ * i4_cap < i4_words.  recon_hash is filled (intra = 1 does that). */
+typedef struct vts_transcode_ext5 {
+  vts_transcode_ext4 base;
+  int32_t intra4x4;        /* 0 off (every output byte as before), 1 on         */
+  int32_t _pad3;
+  uint64_t *i4_out;        /* NULL, or i4_cap words, one per macroblock         */
+  int64_t i4_cap;          /* words i4_out holds                                */
+} vts_transcode_ext5;
+
+typedef struct vts_transcode_ext_info4 {
+  vts_transcode_ext_info3 base;
+  int64_t intra4x4_mbs;    /* macroblocks coded I_NxN (Intra_4x4); 0 when
+                              intra4x4 is off                                  */
+  int64_t i4_words;        /* n_frames * macroblocks per picture               */
+} vts_transcode_ext_info4;
 
 /* vts_transcode with the settings of `ext` (NULL: none) and the further facts
  * in `ext_info` (NULL: not wanted).  vts_transcode(c, o, p, i) is

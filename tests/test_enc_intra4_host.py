@@ -1,0 +1,347 @@
+"""The device encoder's Intra_4x4 path on the CPU (no GPU).
+
+`csrc/enc_intra4.h` holds what `enc_intra<true>` decides with and what both
+slice writers read the modes by; `csrc/enc_cabac.h` holds the I_NxN syntax of
+the CABAC writer.  The harness (tests/native/enc_intra4_host.cpp) exposes them.
+
+  blocks:   the availability rules and the nine predictions against the
+            restatement of 6.4.x and 8.3.1.2.1 .. 8.3.1.2.9 below, for every
+            block with and without a left macroblock;
+  modes:    predIntra4x4PredMode over every kind of neighbour, and the key
+            that orders a block's modes;
+  rows:     seeded macroblock rows mixing I_NxN with Intra16x16, I_PCM, P_Skip
+            and coded inter neighbours are coded by the harness, written as
+            CAVLC and as CABAC (directly and through BinRing, the same bytes),
+            and the CPU oracle decodes both to the harness's reconstruction.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import re
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+ROOT = Path(__file__).resolve().parents[1]
+CSRC = ROOT / "video-transformer_amd" / "csrc"
+NATIVE = ROOT / "tests" / "native"
+sys.path.insert(0, str(ROOT / "oracle"))
+
+PCM = 0x80008000
+NONE = 0xFFFFFFFFFFFFFFFF
+PITCH = 20
+SRCS = [CSRC / f for f in ("synth.cpp", "synth_full.cpp", "mp4.cpp", "plan.cpp")]
+FLAGS = ["-std=c++20", "-Wno-unknown-pragmas", "-pthread", f"-I{CSRC}", f"-I{ROOT / 'include'}", f"-I{NATIVE}"]
+# luma4x4BlkIdx -> (column, row) of the block in the macroblock (6.4.3)
+BLK_XY = [(2 * ((k >> 2) & 1) + (k & 1), 2 * (k >> 3) + ((k >> 1) & 1)) for k in range(16)]
+BLK_AT = {xy: k for k, xy in enumerate(BLK_XY)}
+LAMBDA16 = [4, 4, 5, 5, 6, 7, 7, 8, 9, 10, 12, 13, 15, 17, 19, 21, 23, 26, 30, 33, 37, 42, 47, 53, 59, 66, 74, 83, 94,
+            105, 118, 132, 149, 167, 187, 210, 236, 265, 297, 334, 375, 421, 472, 530, 595, 668, 749, 841, 944, 1060,
+            1189, 1335]
+
+
+@pytest.fixture(scope="module")
+def lib(tmp_path_factory):
+    so = tmp_path_factory.mktemp("ei4h") / "libencintra4host.so"
+    subprocess.run(["g++", "-Og", "-fPIC", "-shared", *FLAGS, str(NATIVE / "enc_intra4_host.cpp"),
+                    *map(str, SRCS), "-o", str(so)], check=True)
+    L = C.CDLL(str(so))
+    L.ei4h_block.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ei4h_block.restype = C.c_uint32
+    L.ei4h_pred_mode.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_uint64]
+    L.ei4h_key.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int]
+    L.ei4h_key.restype = C.c_uint64
+    L.ei4h_lambda16.argtypes = [C.c_int]
+    L.ei4h_encode.argtypes = [C.c_int] * 4 + [C.c_void_p] * 8
+    L.ei4h_encode.restype = None
+    L.ei4h_write.argtypes = [C.c_int] * 5 + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p]
+    L.ei4h_write.restype = C.c_int64
+    L.ei4h_sps_pps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    return L
+
+
+# ------------------------------------- 6.4.x and 8.3.1.2, restated
+def _avail(k, mb_left):
+    """(left, top, top-left, top-right) of block k; the row above the macroblock is another slice."""
+    bx, by = BLK_XY[k]
+    left, top = bx > 0 or mb_left, by > 0
+    # the block above and to the right: inside the macroblock and earlier in decoding order
+    tr = top and bx < 3 and BLK_AT[(bx + 1, by - 1)] < k
+    return left, top, left and top, tr
+
+
+def _allowed(k, mb_left):
+    left, top, tl, _ = _avail(k, mb_left)
+    ok = {2}
+    if top:
+        ok |= {0, 3, 7}
+    if left:
+        ok |= {1, 8}
+    if top and left and tl:
+        ok |= {4, 5, 6}
+    return ok
+
+
+def _predict(mode, p, left, top):
+    """pred4x4L[x, y] of 8.3.1.2.1 .. 8.3.1.2.9; p(x, y) the neighbouring samples, x = -1..7 at y = -1 and
+    y = -1..3 at x = -1."""
+    out = np.zeros((4, 4), np.int64)           # [y, x]
+    for y in range(4):
+        for x in range(4):
+            if mode == 0:                      # Vertical
+                v = p(x, -1)
+            elif mode == 1:                    # Horizontal
+                v = p(-1, y)
+            elif mode == 2:                    # DC
+                if top and left:
+                    v = (sum(p(i, -1) for i in range(4)) + sum(p(-1, i) for i in range(4)) + 4) >> 3
+                elif left:
+                    v = (sum(p(-1, i) for i in range(4)) + 2) >> 2
+                elif top:
+                    v = (sum(p(i, -1) for i in range(4)) + 2) >> 2
+                else:
+                    v = 128
+            elif mode == 3:                    # Diagonal_Down_Left
+                v = (p(6, -1) + 3 * p(7, -1) + 2) >> 2 if x == 3 and y == 3 else \
+                    (p(x + y, -1) + 2 * p(x + y + 1, -1) + p(x + y + 2, -1) + 2) >> 2
+            elif mode == 4:                    # Diagonal_Down_Right
+                if x > y:
+                    v = (p(x - y - 2, -1) + 2 * p(x - y - 1, -1) + p(x - y, -1) + 2) >> 2
+                elif x < y:
+                    v = (p(-1, y - x - 2) + 2 * p(-1, y - x - 1) + p(-1, y - x) + 2) >> 2
+                else:
+                    v = (p(0, -1) + 2 * p(-1, -1) + p(-1, 0) + 2) >> 2
+            elif mode == 5:                    # Vertical_Right
+                z = 2 * x - y
+                if z in (0, 2, 4, 6):
+                    v = (p(x - (y >> 1) - 1, -1) + p(x - (y >> 1), -1) + 1) >> 1
+                elif z in (1, 3, 5):
+                    v = (p(x - (y >> 1) - 2, -1) + 2 * p(x - (y >> 1) - 1, -1) + p(x - (y >> 1), -1) + 2) >> 2
+                elif z == -1:
+                    v = (p(-1, 0) + 2 * p(-1, -1) + p(0, -1) + 2) >> 2
+                else:
+                    v = (p(-1, y - 1) + 2 * p(-1, y - 2) + p(-1, y - 3) + 2) >> 2
+            elif mode == 6:                    # Horizontal_Down
+                z = 2 * y - x
+                if z in (0, 2, 4, 6):
+                    v = (p(-1, y - (x >> 1) - 1) + p(-1, y - (x >> 1)) + 1) >> 1
+                elif z in (1, 3, 5):
+                    v = (p(-1, y - (x >> 1) - 2) + 2 * p(-1, y - (x >> 1) - 1) + p(-1, y - (x >> 1)) + 2) >> 2
+                elif z == -1:
+                    v = (p(-1, 0) + 2 * p(-1, -1) + p(0, -1) + 2) >> 2
+                else:
+                    v = (p(x - 1, -1) + 2 * p(x - 2, -1) + p(x - 3, -1) + 2) >> 2
+            elif mode == 7:                    # Vertical_Left
+                if y in (0, 2):
+                    v = (p(x + (y >> 1), -1) + p(x + (y >> 1) + 1, -1) + 1) >> 1
+                else:
+                    v = (p(x + (y >> 1), -1) + 2 * p(x + (y >> 1) + 1, -1) + p(x + (y >> 1) + 2, -1) + 2) >> 2
+            else:                              # Horizontal_Up
+                z = x + 2 * y
+                if z in (0, 2, 4):
+                    v = (p(-1, y + (x >> 1)) + p(-1, y + (x >> 1) + 1) + 1) >> 1
+                elif z in (1, 3):
+                    v = (p(-1, y + (x >> 1)) + 2 * p(-1, y + (x >> 1) + 1) + p(-1, y + (x >> 1) + 2) + 2) >> 2
+                elif z == 5:
+                    v = (p(-1, 2) + 3 * p(-1, 3) + 2) >> 2
+                else:
+                    v = p(-1, 3)
+            out[y, x] = v
+    return out
+
+
+@pytest.mark.parametrize("mb_left", [0, 1])
+@pytest.mark.parametrize("k", range(16))
+def test_availability_and_the_nine_predictions(lib, k, mb_left):
+    rng = np.random.default_rng(100 * k + mb_left)
+    bx, by = BLK_XY[k]
+    left, top, tl, tr = _avail(k, mb_left)
+    for trial in range(24):
+        tile = rng.integers(0, 256, (16, PITCH)).astype(np.uint8)
+        tile[rng.random(tile.shape) < 0.2] = 0           # the extremes: sums and clips at both ends
+        tile[rng.random(tile.shape) < 0.2] = 255
+        if trial == 0:
+            tile[:] = 255
+        if trial == 1:
+            tile[:] = 0
+        avail, pred = np.zeros(4, np.uint8), np.zeros((9, 4, 4), np.uint8)
+        allowed = lib.ei4h_block(k, mb_left, tile.ctypes.data, avail.ctypes.data, pred.ctypes.data)
+        assert avail.tolist() == [left, top, tl, tr]
+        assert {m for m in range(9) if (allowed >> m) & 1} == _allowed(k, mb_left)
+
+        def p(x, y):
+            """The sample at (x, y) relative to the block; the tile's byte 4 + 4 bx of row 4 by is (0, 0)."""
+            if x > 3 and not tr:
+                x = 3                                    # p[3, -1] substitutes for p[4..7, -1]
+            yy, xx = 4 * by + y, 4 + 4 * bx + x
+            assert yy >= 0, "a sample above the macroblock was read"
+            assert xx >= 4 or mb_left, "a sample left of the picture was read"
+            return int(tile[yy, xx])
+
+        for m in _allowed(k, mb_left):
+            want = _predict(m, p, left, top)
+            assert np.array_equal(pred[m], want), f"block {k} mode {m}:\n{pred[m]}\n{want}"
+
+
+def test_top_right_blocks_are_the_seven_of_the_text():
+    assert [k for k in range(16) if _avail(k, 1)[3]] == [2, 6, 8, 9, 10, 12, 14]
+    assert [sorted(_allowed(k, 0)) for k in (0, 1, 4, 5)] == [[2], [1, 2, 8], [1, 2, 8], [1, 2, 8]]
+    assert [sorted(_allowed(k, 0)) for k in (2, 8, 10)] == [[0, 2, 3, 7]] * 3
+    assert all(_allowed(k, 1) == set(range(9)) for k in range(16) if BLK_XY[k][1] > 0)
+
+
+def _word(modes):
+    return sum(int(m) << (4 * k) for k, m in enumerate(modes))
+
+
+def test_predicted_mode_over_every_neighbour_kind(lib):
+    rng = np.random.default_rng(7)
+    for _ in range(400):
+        cur, lm = rng.integers(0, 9, 16), rng.integers(0, 9, 16)
+        for mb_left in (0, 1):
+            # the left macroblock: absent, not I_NxN (Intra16x16, I_PCM, inter, P_Skip: all ~0), or I_NxN
+            for left in ([NONE] if not mb_left else [NONE, _word(lm)]):
+                for k in range(16):
+                    bx, by = BLK_XY[k]
+                    if by == 0 or (bx == 0 and not mb_left):
+                        want = 2                         # B (or A) lies outside the slice
+                    else:
+                        a = cur[BLK_AT[(bx - 1, by)]] if bx else (2 if left == NONE else lm[BLK_AT[(3, by)]])
+                        want = min(int(a), int(cur[BLK_AT[(bx, by - 1)]]))
+                    # only the earlier blocks' nibbles may matter: the later ones are garbage here
+                    garbage = _word([cur[j] if j < k else 15 for j in range(16)])
+                    assert lib.ei4h_pred_mode(k, garbage, mb_left, left) == want, (k, mb_left, left)
+
+
+def test_key_orders_by_cost_then_mode(lib):
+    for qp in (1, 28, 51):
+        lam = lib.ei4h_lambda16(qp)
+        assert lam == LAMBDA16[qp]
+        key = lambda sad, m, pm: lib.ei4h_key(sad, qp, m, pm)
+        for m in range(9):
+            for pm in range(9):
+                k = key(100, m, pm)
+                assert k >> 32 == 16 * 100 + lam * (1 if m == pm else 4) and k & 15 == m
+        assert key(50, 3, 2) < key(50, 5, 2)             # a tie in cost goes to the lower mode number
+        assert key(50, 0, 2) < key(50, 1, 2)
+        # the predicted mode's discount: 3 lambda of cost, so it wins up to that much more SAD (16 per unit)
+        extra = (3 * lam) // 16
+        assert key(50 + extra, 7, 7) <= key(50, 0, 7) or (3 * lam) % 16 == 0
+        assert key(50 + extra + 1, 7, 7) > key(50, 0, 7)
+        if (3 * lam) % 16 == 0:                          # equal cost: the lower mode number, not the predicted one
+            assert key(50 + extra, 7, 7) > key(50, 0, 7)
+    assert lib.ei4h_key(4080, 51, 8, 0) >> 32 == 16 * 4080 + 4 * 1335
+
+
+# ------------------------------------------------------------ whole rows
+def _pictures(rng, mbw, mbh, npic):
+    """Smooth textures with edges (so that directional modes win somewhere), each picture the previous one plus
+    noise (so that coded inter macroblocks have something to code); samples in 1..255."""
+    W, H = 16 * mbw, 16 * mbh
+    yy, xx = np.mgrid[0:H * 3 // 2, 0:W]
+    base = 128 + 70 * np.sin((xx + 2 * yy) / 5.0) + 40 * ((xx // 6 + yy // 5) % 2) + rng.integers(-6, 7, xx.shape)
+    pics = [np.clip(base, 1, 255)]
+    for _ in range(npic - 1):
+        pics.append(np.clip(pics[-1] + rng.integers(-25, 26, xx.shape) * (rng.random(xx.shape) < 0.5), 1, 255))
+    return np.stack(pics).astype(np.uint8)
+
+
+def _kinds(rng, mbw, mbh, npic):
+    kind = np.zeros((npic, mbh, mbw), np.uint8)
+    kind[0] = rng.choice([0, 1, 2, 2, 5], (mbh, mbw))                 # an IDR picture holds intra kinds only
+    kind[1:] = rng.choice([0, 1, 2, 2, 3, 4, 5], (npic - 1, mbh, mbw))
+    if mbw == 10:                                    # an I_NxN macroblock right of every kind, in a P slice
+        kind[1, 0] = [3, 2, 4, 2, 0, 2, 1, 2, 2, 5]
+    return kind
+
+
+def _encode(lib, mbw, mbh, npic, qp, src, kind):
+    n = npic * mbh * mbw
+    r = dict(cmd=np.zeros(n, np.uint32), cbp=np.zeros(n, np.uint8), coef=np.zeros((n, 384), np.int16),
+             modes=np.zeros(n, np.uint64), bits=np.zeros((n, 2), np.int32), rec=np.zeros_like(src))
+    lib.ei4h_encode(mbw, mbh, npic, qp, src.ctypes.data, kind.ctypes.data, r["cmd"].ctypes.data, r["cbp"].ctypes.data,
+                    r["coef"].ctypes.data, r["modes"].ctypes.data, r["bits"].ctypes.data, r["rec"].ctypes.data)
+    return r
+
+
+def _write(lib, mbw, mbh, npic, qp, cabac, src, r):
+    out = np.zeros(npic * mbh * mbw * 9024 + 1024, np.uint8)
+    sizes = np.zeros(npic, np.int64)
+    n = lib.ei4h_write(mbw, mbh, npic, qp, cabac, src.ctypes.data, r["cmd"].ctypes.data, r["cbp"].ctypes.data,
+                       r["coef"].ctypes.data, r["modes"].ctypes.data, out.ctypes.data, out.size, sizes.ctypes.data)
+    assert n > 0
+    at, samples = 0, []
+    for s in sizes:
+        samples.append(out[at:at + s].tobytes())
+        at += int(s)
+    return samples
+
+
+def _parameter_sets(lib, mbw, mbh, cabac):
+    sps, pps, k = np.zeros(64, np.uint8), np.zeros(64, np.uint8), np.zeros(2, np.int32)
+    lib.ei4h_sps_pps(mbw, mbh, int(cabac != 0), sps.ctypes.data, pps.ctypes.data, k.ctypes.data)
+    return sps[:k[0]].tobytes(), pps[:k[1]].tobytes()
+
+
+@pytest.mark.parametrize("qp", [1, 28, 51])
+@pytest.mark.parametrize("mbw", [1, 2, 10])
+def test_rows_decode_to_the_harness_reconstruction(lib, tmp_path, mbw, qp):
+    import oracle
+    rng = np.random.default_rng(1000 * mbw + qp)
+    mbh, npic = 2, 4
+    src = _pictures(rng, mbw, mbh, npic)
+    kind = _kinds(rng, mbw, mbh, npic)
+    r = _encode(lib, mbw, mbh, npic, qp, src, kind)
+    cmd = r["cmd"]
+    i4 = (cmd & 0xffffc000) == 0x80004000
+    i16 = ((cmd & 0xffff8000) == 0x80000000) & ~i4
+    inter = (cmd == 0)
+    assert np.array_equal(r["modes"] != NONE, i4)
+    # the forced kinds are what was asked; the free ones follow the rule on the two candidates' bits
+    flat = kind.reshape(-1)
+    assert i4[flat == 2].all() and i16[flat == 1].all() and (cmd[flat == 0] == PCM).all() and inter[flat >= 3][flat[flat >= 3] < 5].all()
+    for a in np.nonzero(flat == 5)[0]:
+        b16, b4 = (int(x) for x in r["bits"][a])
+        want = PCM if min(b16, b4) > 3072 else (0x80004000 if b4 < b16 else 0x80000000)
+        got = PCM if cmd[a] == PCM else int(cmd[a]) & 0xffffc000
+        assert got == want, f"macroblock {a}: Intra16x16 {b16} bits, I_NxN {b4} bits"
+    if mbw > 1:
+        rows = cmd.reshape(-1, mbw)
+        left_kinds = {("pcm" if c == PCM else "i4" if (c & 0xffffc000) == 0x80004000 else "i16" if c >> 31 else
+                       "skip" if r["cbp"].reshape(-1, mbw)[y, x - 1] == 0 else "inter")
+                      for y in range(rows.shape[0]) for x in range(1, mbw)
+                      for c in [int(rows[y, x - 1])] if (int(rows[y, x]) & 0xffffc000) == 0x80004000}
+        if mbw == 10:                                    # at qp 51 the noise quantises away: inter becomes P_Skip
+            assert left_kinds | {"inter"} == {"pcm", "i4", "i16", "skip", "inter"}, left_kinds
+            assert "inter" in left_kinds or qp == 51
+    files = {}
+    for cabac in (0, 1, 2):
+        samples = _write(lib, mbw, mbh, npic, qp, cabac, src, r)
+        sps, pps = _parameter_sets(lib, mbw, mbh, cabac)
+        # the oracle's general decoder (oracle.decode_samples is the subset decoder: no I_NxN, no CABAC)
+        path = tmp_path / f"c{cabac}.mp4"
+        oracle.write_mp4(path, sps, pps, samples, list(range(npic)), [0] * npic, 30, 16 * mbw, 16 * mbh)
+        frames, _ = oracle.decode_full(path)
+        assert frames.shape == r["rec"].shape
+        bad = [i for i in range(npic) if not np.array_equal(frames[i], r["rec"][i])]
+        assert bad == [], f"cabac {cabac}: the oracle's pictures differ from the harness's at {bad}"
+        files[cabac] = b"".join(samples)
+    assert files[1] == files[2]                          # BinRing and drain(): the bytes of the direct coder
+    print(f"mbw {mbw} qp {qp}: CAVLC {len(files[0])} bytes, CABAC {len(files[1])} bytes; "
+          f"I_NxN {int(i4.sum())}, Intra16x16 {int(i16.sum())}, I_PCM {int((cmd == PCM).sum())}, inter {int(inter.sum())}")
+
+
+def test_sanitizer_run_of_the_stand_alone_driver(tmp_path):
+    """enc_intra4_main.cpp under AddressSanitizer + UndefinedBehaviorSanitizer, run as a program."""
+    exe = tmp_path / "enc_intra4_main"
+    r = subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", *FLAGS,
+                        str(NATIVE / "enc_intra4_main.cpp"), "-o", str(exe)],
+                       capture_output=True, text=True)
+    if r.returncode != 0 and re.search(r"cannot find.*(asan|ubsan)|libasan|libubsan", r.stderr):
+        pytest.skip("the compiler has no sanitizer runtimes")
+    assert r.returncode == 0, r.stderr[-2000:]
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0 and "enc_intra4_main: ok" in run.stdout, run.stdout[-1000:] + run.stderr[-3000:]

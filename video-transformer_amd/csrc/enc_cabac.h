@@ -32,6 +32,7 @@
 #include <cstdint>
 
 #include "enc_deblock.h"
+#include "enc_intra4.h"
 #include "h264_cabac_tables.h"
 
 namespace vts {
@@ -58,6 +59,15 @@ constexpr int kNumCtx = 277;  // ctxIdx 0 .. 276: the frame-coded 4x4 syntax and
 //   mb_type, the flush, 7 alignment bits, 384 samples, end_of_slice_flag)
 //   stays under 400 as before.  The slice header and the final flush fit the
 //   slot's 64 spare bytes.
+//   An I_NxN macroblock (mb_intra4) has no mvd but 16 x 4 mode bins: its header
+//   is mb_skip_flag 1, mb_type 2, the modes 64, intra_chroma_pred_mode 3,
+//   coded_block_pattern 6, mb_qp_delta 1, end_of_slice_flag 1: 78 bins, 546 bits
+//   taken at 7, which is 223 more than the 323 counted above, with 26 flags for
+//   27 and the same 384 levels: 48318 bits, 9060 bytes by the arithmetic above.
+//   That arithmetic allows |level| < 2^13; the quantiser clamps at 2047
+//   (eres::quant1), so a level's UEG0 suffix and sign take at most 10 + 1 + 10
+//   + 1 bits and a level 16 x 6 + 22 = 118, not 124: 384 x 118 + 546 + 156 =
+//   46014 bits = 5752 bytes, 8628 with emulation prevention.  9024 bounds it.
 constexpr int kMbBytes = 9024;
 
 #if defined(__HIPCC__)
@@ -308,7 +318,7 @@ VTS_HD inline void exp_golomb(E &e, uint32_t v, int k) {
 }
 
 // ------------------------------------------------------- neighbour facts
-enum : int { kNone = 0, kPcm = 1, kSkip = 2, kI16 = 3, kInter = 4 };
+enum : int { kNone = 0, kPcm = 1, kSkip = 2, kI16 = 3, kInter = 4, kI4 = 5 };
 // coded_block_flag bits of a macroblock: bit 0 Intra16x16DCLevel, 1 + raster
 // luma 4x4 block, 17 + plane chroma DC, 19 + 4 plane + raster chroma AC.  A
 // block whose flag is not sent has 0, which is what 9.3.3.1.1.9 assigns to an
@@ -317,11 +327,12 @@ constexpr uint32_t kCbfAll = 0x07ffffffu;
 struct Left {        // the macroblock to the left in the slice (mx = 0: kNone)
   int kind;
   int cbp;           // coded_block_pattern (Intra16x16: the one mb_type says; P_Skip 0)
-  int cmode;         // intra_chroma_pred_mode (Intra16x16)
+  int cmode;         // intra_chroma_pred_mode (Intra16x16, I_NxN)
   int amvd[2];       // |mvd_l0| (inter that is not skipped; else 0)
   uint32_t cbf;
+  uint64_t i4 = ei4::kNoModes;  // I_NxN: its Intra4x4PredModes (enc_intra4.h), else ~0
 };
-VTS_HD VTS_INLINE Left left_none() { return Left{kNone, 0, 0, {0, 0}, 0}; }
+VTS_HD VTS_INLINE Left left_none() { return Left{kNone, 0, 0, {0, 0}, 0, ei4::kNoModes}; }
 
 // ------------------------------------------------------- syntax elements
 // mb_skip_flag (P): ctxIdx 11 + condTermFlagA; a skipped or absent A counts 0
@@ -330,7 +341,7 @@ VTS_HD VTS_INLINE void mb_skip_flag(E &e, const Left &l, int skip) {
   e.decision(11 + (l.kind != kNone && l.kind != kSkip ? 1 : 0), skip);
 }
 // mb_type of an intra macroblock (Table 9-36): in an I slice ctxIdx 3.., bin 0
-// by A (never I_NxN here: 1 when available); in a P slice the prefix 1 at
+// by A (1 when available and not I_NxN); in a P slice the prefix 1 at
 // ctxIdx 14 and the suffix at 17...  t = 25: I_PCM (the terminate bin 1 and
 // the flush; the caller aligns, leaves the samples and calls start()), else
 // Intra16x16 with prediction mode pm, chroma cc = cbp / 16, luma15 = cbp & 15 != 0
@@ -338,7 +349,7 @@ template <class E>
 VTS_HD inline void mb_type_intra(E &e, bool islice, const Left &l, bool pcm, int pm, int cc, bool luma15) {
   int b;  // ctxIdx of bin 2 (luma); chroma and the mode bits follow by Table 9-39
   if (islice) {
-    e.decision(3 + (l.kind != kNone ? 1 : 0), 1);
+    e.decision(3 + (l.kind != kNone && l.kind != kI4 ? 1 : 0), 1);
     b = 3 + 3;
   } else {
     e.decision(14, 1);
@@ -359,6 +370,28 @@ VTS_HD inline void mb_type_intra(E &e, bool islice, const Left &l, bool pcm, int
     e.decision(b + 2, pm & 1);
   }
 }
+// mb_type I_NxN: in an I slice the one bin 0 at ctxIdx 3 + condTermFlagA; in a
+// P slice the prefix 1 at ctxIdx 14, then 0 at 17
+template <class E>
+VTS_HD VTS_INLINE void mb_type_i4(E &e, bool islice, const Left &l) {
+  if (islice) {
+    e.decision(3 + (l.kind != kNone && l.kind != kI4 ? 1 : 0), 0);
+  } else {
+    e.decision(14, 1);
+    e.decision(17, 0);
+  }
+}
+// prev_intra4x4_pred_mode_flag at ctxIdx 68, then rem_intra4x4_pred_mode as
+// three bins at 69, least significant first
+template <class E>
+VTS_HD VTS_INLINE void intra4_pred_mode(E &e, int mode, int pred) {
+  e.decision(68, mode == pred);
+  if (mode == pred) return;
+  const int rem = ei4::rem_mode(mode, pred);
+  e.decision(69, rem & 1);
+  e.decision(69, (rem >> 1) & 1);
+  e.decision(69, (rem >> 2) & 1);
+}
 // mb_type P_L0_16x16: bins 0 0 0 at ctxIdx 14, 15, 16
 template <class E>
 VTS_HD VTS_INLINE void mb_type_p16x16(E &e) {
@@ -369,7 +402,7 @@ VTS_HD VTS_INLINE void mb_type_p16x16(E &e) {
 // intra_chroma_pred_mode: TU cMax 3, ctxIdx 64 + condTermFlagA, then 67
 template <class E>
 VTS_HD VTS_INLINE void intra_chroma_pred_mode(E &e, const Left &l, int mode) {
-  e.decision(64 + (l.kind == kI16 && l.cmode != 0 ? 1 : 0), mode > 0);
+  e.decision(64 + ((l.kind == kI16 || l.kind == kI4) && l.cmode != 0 ? 1 : 0), mode > 0);
   if (mode > 0) {
     e.decision(67, mode > 1);
     if (mode > 1) e.decision(67, mode > 2);
@@ -401,7 +434,7 @@ VTS_HD inline void coded_block_pattern(E &e, const Left &l, int cbp) {
     cb = b8 >= 2 ? !((cbp >> (b8 - 2)) & 1) : 0;
     e.decision(73 + ca + 2 * cb, (cbp >> b8) & 1);
   }
-  const int cc = cbp >> 4, lc = l.kind == kPcm ? 2 : ((l.kind == kI16 || l.kind == kInter) ? l.cbp >> 4 : 0);
+  const int cc = cbp >> 4, lc = l.kind == kPcm ? 2 : ((l.kind == kI16 || l.kind == kI4 || l.kind == kInter) ? l.cbp >> 4 : 0);
   e.decision(77 + (lc != 0 ? 1 : 0), cc != 0);
   if (cc) e.decision(81 + (lc == 2 ? 1 : 0), cc == 2);
 }
@@ -516,6 +549,34 @@ VTS_HD inline void mb_intra16(E &e, bool islice, Left &l, uint32_t cmd, const in
   cbf = chroma_residual(e, l, cp, cbp >> 4, true, cbf);
   e.terminate(last);
   l = Left{kI16, cbp, cmode, {0, 0}, cbf};
+}
+// I_NxN (Intra_4x4) from its command word (bits 2..3 intra_chroma_pred_mode,
+// 4..9 coded_block_pattern), its Intra4x4PredModes and levels (the inter
+// layout: 16 per luma block by luma4x4BlkIdx, chroma).  There is no
+// transform_size_8x8_flag: the PPS has no 8x8 transform.  A luma block's
+// coded_block_flag takes condTermFlag 1 for a neighbour outside the slice
+// (intra: cbf_inc_luma), mb_qp_delta is sent only with a pattern.
+template <class E>
+VTS_HD inline void mb_intra4(E &e, bool islice, Left &l, uint32_t cmd, uint64_t modes, const int16_t *cp, bool last) {
+  const int cbp = static_cast<int>(cmd >> 4) & 63, cmode = static_cast<int>(cmd >> 2) & 3;
+  e.block_begin();
+  if (!islice) mb_skip_flag(e, l, 0);
+  mb_type_i4(e, islice, l);
+  for (int k = 0; k < 16; ++k)
+    intra4_pred_mode(e, ei4::mode_at(modes, k), ei4::pred_mode_of(k, modes, l.kind != kNone, l.kind == kI4 ? l.i4 : ei4::kNoModes));
+  intra_chroma_pred_mode(e, l, cmode);
+  coded_block_pattern(e, l, cbp);
+  uint32_t cbf = 0;
+  if (cbp) {
+    mb_qp_delta0(e);
+    for (int k = 0; k < 16; ++k)
+      if ((cbp >> (k >> 2)) & 1)
+        cbf |= static_cast<uint32_t>(residual_block(e, 2, cbf_inc_luma(l, cbf, k, true), cp + 16 * k, 16))
+               << (1 + edb::raster_of_blk(k));
+    cbf = chroma_residual(e, l, cp, cbp >> 4, true, cbf);
+  }
+  e.terminate(last);
+  l = Left{kI4, cbp, cmode, {0, 0}, cbf, modes};
 }
 // P_L0_16x16 with the vector difference (dx, dy), coded_block_pattern cbp and
 // levels (16 per luma block by luma4x4BlkIdx, chroma)

@@ -193,8 +193,10 @@ __device__ __constant__ static const uint8_t kCbpInterTab[48] = VTS_CBPP_DATA;
 __device__ __constant__ static const uint8_t kQpcTab[52] = VTS_QPC_DATA;
 __device__ __constant__ static const uint8_t kBlkXd[16] = {0, 1, 0, 1, 2, 3, 2, 3, 0, 1, 0, 1, 2, 3, 2, 3};
 __device__ __constant__ static const uint8_t kBlkYd[16] = {0, 0, 1, 1, 0, 0, 1, 1, 2, 2, 3, 3, 2, 2, 3, 3};
+__device__ __constant__ static const uint8_t kCbpIntraTab[48] = VTS_CBPI_DATA;  // Intra_4x4 column of Table 9-4
 namespace er = full::erate;
 namespace eres = full::eres;  // the transform, the quantiser and the reconstruction (enc_residual.h)
+namespace ei4 = full::ei4;    // the Intra_4x4 decisions (enc_intra4.h)
 
 // bits of residual_block_cavlc (7.3.5.3.2, 9.2) of levels lv[0, maxNum) in
 // scan order with nC (-1: chroma DC); nC < -1: an upper bound (coeff_token
@@ -850,6 +852,7 @@ struct WriteArgs {
   uint32_t *n_jobs;
   int32_t n_slices;
   int32_t dbk_alpha, dbk_beta, _pad;  // enc_write<., true>: slice_alpha_c0_offset_div2, slice_beta_offset_div2
+  const uint64_t *i4;   // [entry][mb] the Intra4x4PredModes of the I_NxN macroblocks (intra4x4; else unread)
 };
 
 // RBSP bits -> EBSP bytes (emulation prevention) into a staging slot, four
@@ -1018,8 +1021,30 @@ struct IntraArgs {
   int32_t qp;
   int32_t all;          // 1: every macroblock is a candidate and dst is unwritten (level 0, the IDR
                         // pictures); 0: the macroblocks enc_search left as kPcmCmd (dst holds the source)
+  uint64_t *i4;         // enc_intra<true>: [entry][mb] the Intra4x4PredModes of an I_NxN macroblock, else ~0
 };
 
+// me(v) of an I_NxN macroblock's coded_block_pattern (Table 9-4, Intra_4x4 column)
+__device__ __forceinline__ uint32_t cbp_intra_code(int cbp) {
+  uint32_t code = 0;
+  while (kCbpIntraTab[code] != cbp) ++code;
+  return code;
+}
+
+// kI4 (vts_transcode_ext5.intra4x4, DESIGN.md §11 "Intra4x4"): every
+// candidate macroblock is also tried as I_NxN with sixteen Intra_4x4 blocks,
+// and that is what it becomes when its CAVLC bits are strictly fewer than the
+// Intra16x16 candidate's; chroma is the same for both.  The sixteen blocks are
+// a serial chain (a block predicts from the reconstruction of the ones before
+// it, kept in an LDS tile), each of them spread over the wave: lanes 0..12
+// fetch the block's 13 neighbouring samples, lanes 0..35 take (mode, row) =
+// (lane / 4, lane % 4), predict that row (enc_intra4.h), v_sad_u8 it against
+// the source and the quad sums the mode's SAD; the least (cost, mode) key is a
+// 64-bit minimum over the wave; lane 0 transforms, quantises and reconstructs
+// the block into the tile.  The levels wait in LDS for the bit count, which
+// lanes 0..15 then take a block each as the Intra16x16 candidate's.
+// false: the code is the kernel's without it.
+template <bool kI4>
 __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
   __shared__ __attribute__((aligned(16))) uint32_t srcy[64], recy[64];
   __shared__ uint16_t srcc[64];
@@ -1041,9 +1066,11 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
   if (lane < 4) lnz[lane] = -1;
   if (lane < 4) lnzc[lane >> 1][lane & 1] = -1;
   bool left_mine = false;  // the left macroblock was coded by this wave: its column is in left_y / left_c
+  [[maybe_unused]] uint64_t left_modes = ei4::kNoModes;  // kI4: the left macroblock's Intra4x4PredModes when it is I_NxN
   for (int mx = 0; mx < a.mbw; ++mx) {
     if (!a.all && a.cmd[mb0 + mx] != kPcmCmd) {  // wave-uniform
       left_mine = false;
+      if constexpr (kI4) left_modes = ei4::kNoModes;
       continue;
     }
     const int64_t lo = static_cast<int64_t>(my * 16 + ly) * a.cw + mx * 16 + lx;
@@ -1187,10 +1214,123 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
       contrib = ue_bits(static_cast<uint32_t>(a.all ? mbt : 5 + mbt)) + ue_bits(static_cast<uint32_t>(cmode)) + 1 +
                 cavlc_block<false>(nullptr, dlv, 16, nc_of(lnz[0], -1));
     }
+    [[maybe_unused]] int own = 0;  // kI4: lanes 16..25 hold the chroma bits, the same for both candidates
+    if constexpr (kI4) own = contrib;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) contrib += __shfl_xor(contrib, off);
+    // ---- kI4: the I_NxN candidate
+    [[maybe_unused]] bool use4 = false;  // wave-uniform
+    [[maybe_unused]] int cbp4 = 0, lv4k[16];
+    [[maybe_unused]] uint64_t modes4 = 0;
+    if constexpr (kI4) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) lv4k[q] = 0;
+      __shared__ __attribute__((aligned(16))) uint8_t tile[16 * ei4::kTilePitch];
+      __shared__ int eT[9], eL[5];      // the block's neighbouring samples as ei4::pred_row reads them
+      __shared__ int16_t lv4[16][16];   // the blocks' levels (luma4x4BlkIdx, scan order)
+      __shared__ int tc4[16];           // their total_coeff, raster order
+      if (lane < 16) tile[lane * ei4::kTilePitch + 3] = static_cast<uint8_t>(mx > 0 ? left_y[lane] : 0);
+      __syncthreads();
+      int mbits = 0;
+      for (int k = 0; k < 16; ++k) {
+        const ei4::Avail av = ei4::avail_of(k, mx > 0);
+        const int pm = ei4::pred_mode_of(k, modes4, mx > 0, left_modes);
+        const int bx = kBlkXd[k], by = kBlkYd[k];
+        if (lane < 13) {
+          const int v = ei4::edge_sample(tile, k, av, lane);
+          if (lane < 9) eT[lane] = v;
+          else eL[lane - 8] = v;
+          if (lane == 0) eL[0] = v;
+        }
+        __syncthreads();
+        const int mode = lane >> 2, y = lane & 3;
+        uint32_t p4 = 0, s = 0;
+        if (lane < 36) {
+          p4 = ei4::pred_row(mode, y, eT, eL, av);
+          s = __builtin_amdgcn_sad_u8(p4, srcy[(by * 4 + y) * 4 + bx], 0);
+        }
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        uint64_t key = ~0ull;
+        if (lane < 36 && ((ei4::allowed_modes(av) >> mode) & 1u)) key = ei4::mode_key(s, qp, mode, pm);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+          const uint64_t o = __shfl_xor(key, off);
+          key = o < key ? o : key;
+        }
+        const int best = ei4::key_mode(key);  // wave-uniform
+        uint32_t pr[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pr[r] = static_cast<uint32_t>(__shfl(static_cast<int>(p4), best * 4 + r));
+        if (lane == 0) {
+          int x[16], z4[16], l4[16], res[16];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) eres::diff_row4(srcy[(by * 4 + r) * 4 + bx], pr[r], x + 4 * r);
+          eres::code_block<false>(x, qp, z4, l4, nullptr);
+          full::scale_idct4(z4, qp, false, res);
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            *reinterpret_cast<uint32_t *>(tile + (by * 4 + r) * ei4::kTilePitch + 4 + 4 * bx) = eres::recon_row4(pr[r], res + 4 * r);
+#pragma unroll
+          for (int q = 0; q < 16; ++q) lv4[k][q] = static_cast<int16_t>(l4[q]);
+        }
+        modes4 |= static_cast<uint64_t>(best) << (4 * k);
+        mbits += ei4::mode_bits(best, pm);
+        __syncthreads();
+      }
+      // its bits: the luma blocks of the coded 8x8s with the writer's nC, the chroma bits as above, the header
+      int tck = 0;
+      if (lane < 16) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          lv4k[q] = lv4[lane][q];
+          tck += lv4k[q] != 0;
+        }
+      }
+      const uint32_t nzm4 = static_cast<uint32_t>(__ballot(tck != 0)) & 0xffffu;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if ((nzm4 >> (4 * q)) & 15u) cbp4 |= 1 << q;
+      cbp4 |= cc << 4;
+      const bool coded8 = lane < 16 && ((cbp4 >> (lane >> 2)) & 1);
+      if (lane < 16) tc4[byl * 4 + bxl] = coded8 ? tck : 0;
+      __syncthreads();
+      int c4 = 0;
+      if (lane < 16) {
+        if (coded8) {
+          const int na = bxl ? tc4[byl * 4 + bxl - 1] : lnz[byl], nb = byl ? tc4[(byl - 1) * 4 + bxl] : -1;
+          c4 = cavlc_block<false>(nullptr, lv4k, 16, nc_of(na, nb));
+        }
+      } else if (lane < 26) {
+        c4 = own;
+      } else if (lane == 26) {  // mb_type, the sixteen modes, intra_chroma_pred_mode, coded_block_pattern, mb_qp_delta
+        c4 = ue_bits(a.all ? 0u : 5u) + mbits + ue_bits(static_cast<uint32_t>(cmode)) + ue_bits(cbp_intra_code(cbp4)) +
+             (cbp4 ? 1 : 0);
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) c4 += __shfl_xor(c4, off);
+      use4 = c4 < contrib;  // ties go to Intra16x16
+      if (use4) {
+        contrib = c4;
+        if (lane < 36 && lane >= 32) tcy[(lane - 32) * 4 + 3] = tc4[(lane - 32) * 4 + 3];  // what the right neighbour counts
+        recy[lane] = *reinterpret_cast<const uint32_t *>(tile + ly * ei4::kTilePitch + 4 + lx);
+      }
+      __syncthreads();
+    }
     const bool intra = contrib <= kPcmBits;  // wave-uniform
-    if (intra) {
+    if constexpr (kI4) {
+      if (intra && use4) {
+        // I_NxN: luma is reconstructed (recy, above); chroma as Intra16x16; luma levels in the inter layout
+        if (lane >= 16 && lane < 24) chroma_block_recon(lane, pred, dcl, z, cc == 2, qpc, recc);
+        int16_t *cp = a.coef + (mb0 + mx) * kCoefPerMb;
+        if (lane < 16) {
+#pragma unroll
+          for (int q = 0; q < 16; ++q) cp[16 * lane + q] = static_cast<int16_t>(lv4k[q]);
+        }
+        store_chroma_levels(cp, lane, lv, dcl);
+      }
+    }
+    if (intra && !(kI4 && use4)) {
       // ---- reconstruction through the decoder's inverse path
       if (lane < 16) {
         int res[16];
@@ -1215,7 +1355,17 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
       *reinterpret_cast<uint32_t *>(dst + lo) = intra ? recy[lane] : sy4;
       *reinterpret_cast<uint16_t *>(dst + co) = intra ? static_cast<uint16_t>(recc[0][lane] | (recc[1][lane] << 8)) : suv;
     }
-    if (lane == 0) {
+    if constexpr (kI4) {
+      left_modes = intra && use4 ? modes4 : ei4::kNoModes;
+      if (lane == 0) {
+        a.i4[mb0 + mx] = left_modes;
+        if (intra && use4) {
+          a.cmd[mb0 + mx] = ei4::kI4Cmd | static_cast<uint32_t>((cmode << 2) | (cbp4 << 4));
+          a.cbp[mb0 + mx] = static_cast<uint8_t>(cbp4);
+        }
+      }
+    }
+    if (lane == 0 && !(kI4 && intra && use4)) {
       a.cmd[mb0 + mx] = intra ? kIntraCmd | static_cast<uint32_t>(lmode | (cmode << 2) | (cbp << 4)) : kPcmCmd;
       a.cbp[mb0 + mx] = static_cast<uint8_t>(intra ? cbp : 0);
     }
@@ -1557,6 +1707,11 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
       a.coef + ((static_cast<int64_t>(en.y % a.ring) * a.coef_per_level + en.w) * a.mbh + row) * a.mbw * kCoefPerMb;
   // total_coeff of the left macroblock's right column for nC (9.2.1); -1 none
   int lnz[4] = {-1, -1, -1, -1}, lnzc[2][2] = {{-1, -1}, {-1, -1}}, cnz[16], cnzc[2][4];
+  // I_NxN: the row's mode words; the last I_NxN macroblock's word and column (predIntra4x4PredMode's A)
+  const uint64_t *i4r = kIntra && a.i4 ? a.i4 + static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw : nullptr;
+  uint64_t i4_left = ei4::kNoModes;
+  int i4_mx = -2;
+  unsigned long long ni4 = 0;
   // reserve this slice's I_PCM jobs
   uint32_t njob = 0;
   if (idr && !kIntra) {
@@ -1573,6 +1728,40 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
       continue;
     }
     const uint32_t c = cmd[mx];
+    if (kIntra && ei4::is_i4_cmd(c)) {  // I_NxN (7.3.5, 7.3.5.1): mb_type 0, 5 in a P slice; no transform_size_8x8_flag
+      const int cbp = static_cast<int>(c >> 4) & 63;
+      if (!idr) {
+        o.ue(skip);
+        skip = 0;
+      }
+      o.ue(idr ? 0 : 5);
+      const uint64_t modes = i4r[mx], lw = i4_mx == mx - 1 ? i4_left : ei4::kNoModes;
+      for (int k = 0; k < 16; ++k) {
+        const int m = ei4::mode_at(modes, k), pm = ei4::pred_mode_of(k, modes, mx > 0, lw);
+        if (m == pm) o.bits(1, 1);  // prev_intra4x4_pred_mode_flag
+        else o.bits(4, static_cast<uint32_t>(ei4::rem_mode(m, pm)));  // the flag 0, rem_intra4x4_pred_mode
+      }
+      o.ue((c >> 2) & 3u);  // intra_chroma_pred_mode
+      o.ue(cbp_intra_code(cbp));
+      if (cbp) {
+        o.se(0);  // mb_qp_delta
+        put_residual(o, coef_row + static_cast<int64_t>(mx) * kCoefPerMb, cbp, lnz, lnzc, cnz, cnzc);
+      } else {
+        for (int i = 0; i < 16; ++i) cnz[i] = 0;
+        for (int i = 0; i < 4; ++i) cnzc[0][i] = cnzc[1][i] = 0;
+      }
+      for (int i = 0; i < 4; ++i) lnz[i] = cnz[i * 4 + 3];
+      for (int pl = 0; pl < 2; ++pl) {
+        lnzc[pl][0] = cnzc[pl][1];
+        lnzc[pl][1] = cnzc[pl][3];
+      }
+      a_ok = false;
+      i4_left = modes;
+      i4_mx = mx;
+      ++nintra;
+      ++ni4;
+      continue;
+    }
     if (kIntra && is_intra_cmd(c)) {  // Intra16x16 (7.3.5, Table 7-11; 5 more in a P slice)
       const int cbp = static_cast<int>(c >> 4) & 63;
       const uint32_t mbt = 1 + (c & 3u) + 4 * static_cast<uint32_t>(cbp >> 4) + ((cbp & 15) ? 12 : 0);
@@ -1657,6 +1846,7 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   atomicAdd(&a.stats[1], ninter);
   atomicAdd(&a.stats[2], nskip);
   if (nintra) atomicAdd(&a.stats[3], nintra);
+  if (ni4) atomicAdd(&a.stats[9], ni4);
 }
 
 // The slices with entropy_coding_mode_flag = 1 (vts_transcode_ext4.cabac,
@@ -1692,6 +1882,8 @@ __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
   const uint8_t *cbpr = a.cbp + static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw;
   const int16_t *coef_row =
       a.coef + ((static_cast<int64_t>(en.y % a.ring) * a.coef_per_level + en.w) * a.mbh + row) * a.mbw * kCoefPerMb;
+  const uint64_t *i4r = kIntra && a.i4 ? a.i4 + static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw : nullptr;
+  unsigned long long ni4 = 0;
   const bool all_pcm = idr && !kIntra;  // level 0 without intra holds no commands
   uint32_t njob = 0;
   if (all_pcm) {
@@ -1732,6 +1924,11 @@ __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
       ec::mb_pcm_end(enc, left, last);
       a_ok = false;
       ++npcm;
+    } else if (intra && ei4::is_i4_cmd(c)) {
+      ec::mb_intra4(enc, idr, left, c, i4r[mx], lv, last);
+      a_ok = false;
+      ++nintra;
+      ++ni4;
     } else if (intra) {
       ec::mb_intra16(enc, idr, left, c, lv, last);
       a_ok = false;
@@ -1766,6 +1963,7 @@ __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
   atomicAdd(&a.stats[1], ninter);
   atomicAdd(&a.stats[2], nskip);
   if (nintra) atomicAdd(&a.stats[3], nintra);
+  if (ni4) atomicAdd(&a.stats[9], ni4);
 }
 
 // Slice offsets of one level on the device: offs[s] = running output total +
@@ -2018,8 +2216,11 @@ struct TranscodeOpts {
   int subpel = 0, deblock = 0, dbk_alpha = 0, dbk_beta = 0;
   int mvcost = 0, mv_lambda16 = 0, early_skip = 0;
   int cabac = 0;
+  int intra4x4 = 0;
   uint32_t *cmd_out = nullptr;
   int64_t cmd_cap = 0;
+  uint64_t *i4_out = nullptr;
+  int64_t i4_cap = 0;
   int rate = 0;         // SearchArgs.rate: mvcost | early_skip << 1
   int sh = 0, R = 0, T = 0, qp = 0, keyint = 0;  // output height, search range, max SAD, residual QP (0: none)
   bool intra = false, idr_at_cuts = false;
@@ -2059,6 +2260,12 @@ int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_trans
     // vts_transcode_ext4, the same way
     if (ext->struct_size >= 60) o.cabac = reinterpret_cast<const vts_transcode_ext4 *>(ext)->cabac;
     if (o.cabac != 0 && o.cabac != 1) return fail(VTS_E_INVALID, "cabac %d: 0 or 1", o.cabac);
+    // vts_transcode_ext5, the same way
+    const vts_transcode_ext5 *x5 = reinterpret_cast<const vts_transcode_ext5 *>(ext);
+    if (ext->struct_size >= 68) o.intra4x4 = x5->intra4x4;
+    if (ext->struct_size >= 80) o.i4_out = x5->i4_out;
+    if (ext->struct_size >= 88) o.i4_cap = x5->i4_cap;
+    if (o.intra4x4 != 0 && o.intra4x4 != 1) return fail(VTS_E_INVALID, "intra4x4 %d: 0 or 1", o.intra4x4);
   }
   o.rate = o.mvcost | (o.early_skip << 1);
   if (xinfo && xinfo->struct_size < 8)
@@ -2073,6 +2280,8 @@ int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_trans
   if (p.intra != 0 && p.intra != 1) return fail(VTS_E_INVALID, "intra %d: 0 or 1", p.intra);
   o.intra = p.intra == 1;
   o.hashed = o.intra || o.subpel != 0 || o.deblock || o.rate;
+  if (o.intra4x4 && o.qp < 1) return fail(VTS_E_INVALID, "intra4x4 = 1 needs residual coding (qp >= 0)");
+  if (o.intra4x4 && !o.intra) return fail(VTS_E_INVALID, "intra4x4 = 1 needs intra = 1");
   if (o.intra && o.qp < 1) return fail(VTS_E_INVALID, "intra = 1 needs residual coding (qp >= 0)");
   if (o.deblock && o.qp < 1) return fail(VTS_E_INVALID, "deblock = 1 needs residual coding (qp >= 0)");
   if (o.mvcost && o.qp < 1) return fail(VTS_E_INVALID, "mvcost = 1 needs residual coding (qp >= 0)");
@@ -2164,6 +2373,11 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   if (opt.cmd_out && opt.cmd_cap < cmd_words)
     return fail(VTS_E_CAPACITY, "cmd_cap %lld < %lld command words", static_cast<long long>(opt.cmd_cap),
                 static_cast<long long>(cmd_words));
+  // the Intra4x4PredModes word of every macroblock, the same way
+  if (xinfo && xinfo->struct_size >= 64) reinterpret_cast<vts_transcode_ext_info4 *>(xinfo)->i4_words = cmd_words;
+  if (opt.i4_out && opt.i4_cap < cmd_words)
+    return fail(VTS_E_CAPACITY, "i4_cap %lld < %lld mode words", static_cast<long long>(opt.i4_cap),
+                static_cast<long long>(cmd_words));
 
   // 1. decode + score + downscale
   auto t0 = clk::now();
@@ -2199,6 +2413,10 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   VTS_TRY(B.get(&d_cmd, static_cast<size_t>(plan.went.size()) * nmb));  // every frame: searches run ahead
   uint8_t *d_cbp;
   VTS_TRY(B.get(&d_cbp, static_cast<size_t>(plan.went.size()) * nmb));
+  // intra4x4: the mode word of every macroblock, [entry][mb] as the command words; ~0 where enc_intra<true>
+  // writes none (a macroblock that enc_search coded)
+  uint64_t *d_i4 = nullptr;
+  if (opt.intra4x4) VTS_TRY(B.get(&d_i4, static_cast<size_t>(plan.went.size()) * nmb));
   // residual levels: a ring of kRing levels (the searches run at most kRing
   // levels ahead of the slice writing that reads them)
   constexpr int64_t kRing = 32;
@@ -2217,8 +2435,8 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   VTS_TRY(B.get(&d_sizes, static_cast<size_t>(max_chunk * mbh)));
   VTS_TRY(B.get(&d_offs, static_cast<size_t>(max_chunk * mbh)));
   // pcm, inter, skip, intra macroblocks; the reconstruction hash; enc_search's two sub-sample counts;
-  // enc_deblock's filtered macroblocks; enc_search's early P_Skip macroblocks
-  VTS_TRY(B.get(&d_stats, 9));
+  // enc_deblock's filtered macroblocks; enc_search's early P_Skip macroblocks; the writers' I_NxN macroblocks
+  VTS_TRY(B.get(&d_stats, 10));
   VTS_TRY(B.get(&d_err, 1));
   uint4 *d_jobs;
   uint32_t *d_njobs;
@@ -2244,6 +2462,10 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   // enc_hash, enc_search<., SP > 0> and enc_deblock (s1) add into these
   if (opt.hashed) HIP_TRY(hipMemsetAsync(d_stats + 4, 0, (opt.rate ? 5 : 4) * sizeof(unsigned long long), s1));
   HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(uint32_t), s2));
+  if (opt.intra4x4) {
+    HIP_TRY(hipMemsetAsync(d_stats + 9, 0, sizeof(unsigned long long), s2));
+    HIP_TRY(hipMemsetAsync(d_i4, 0xff, plan.went.size() * static_cast<size_t>(nmb) * sizeof(uint64_t), s1));
+  }
   const int64_t nchunks = (plan.maxlen + kChunkLevels - 1) / kChunkLevels;
   std::vector<hipEvent_t> ev(static_cast<size_t>(plan.maxlen + 5 + nchunks), nullptr);
   struct EvGuard {
@@ -2276,7 +2498,12 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
     ia.mbh = mbh;
     ia.qp = opt.qp;
     ia.all = j == 0;
-    hipLaunchKernelGGL(enc_intra, dim3(static_cast<unsigned>(ne * mbh)), dim3(64), 0, s1, ia);
+    if (opt.intra4x4) {
+      ia.i4 = d_i4 + plan.lvl_off[j] * nmb;
+      hipLaunchKernelGGL(enc_intra<true>, dim3(static_cast<unsigned>(ne * mbh)), dim3(64), 0, s1, ia);
+    } else {
+      hipLaunchKernelGGL(enc_intra<false>, dim3(static_cast<unsigned>(ne * mbh)), dim3(64), 0, s1, ia);
+    }
   };
   // deblock: the level's reconstruction filtered in place (8.7, inside each
   // macroblock row's slice) behind its search and intra coding, before it is
@@ -2434,6 +2661,7 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
     wa.n_slices = ns;
     wa.dbk_alpha = opt.dbk_alpha;
     wa.dbk_beta = opt.dbk_beta;
+    wa.i4 = d_i4 ? d_i4 + e0 * nmb : nullptr;
     const dim3 wgrid(static_cast<unsigned>((ns + 63) / 64));
     if (opt.cabac) {  // one wave per slice
       const dim3 cgrid(static_cast<unsigned>(ns));
@@ -2499,7 +2727,7 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   }
   VTS_TRY(status);
   uint32_t err = 0;
-  unsigned long long st[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long st[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   HIP_TRY(hipMemcpy(&err, d_err, sizeof err, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost));
   if (err) return fail(VTS_E_CAPACITY, "a slice exceeded its %lld-byte staging slot", static_cast<long long>(cap));
@@ -2510,6 +2738,17 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
       uint32_t *o = opt.cmd_out + static_cast<int64_t>(plan.went[i].x) * nmb;
       if (plan.went[i].y == 0 && !opt.intra) std::fill(o, o + nmb, kPcmCmd);
       else std::memcpy(o, words.data() + i * static_cast<size_t>(nmb), static_cast<size_t>(nmb) * sizeof(uint32_t));
+    }
+  }
+
+  if (opt.i4_out) {  // as cmd_out; without intra4x4 no macroblock is I_NxN
+    std::fill(opt.i4_out, opt.i4_out + cmd_words, ei4::kNoModes);
+    if (opt.intra4x4) {
+      std::vector<uint64_t> words(plan.went.size() * static_cast<size_t>(nmb));
+      HIP_TRY(hipMemcpy(words.data(), d_i4, words.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < plan.went.size(); ++i)
+        std::memcpy(opt.i4_out + static_cast<int64_t>(plan.went[i].x) * nmb, words.data() + i * static_cast<size_t>(nmb),
+                    static_cast<size_t>(nmb) * sizeof(uint64_t));
     }
   }
 
@@ -2552,6 +2791,8 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
       reinterpret_cast<vts_transcode_ext_info2 *>(xinfo)->deblock_mbs = opt.deblock ? static_cast<int64_t>(st[7]) : 0;
     if (xinfo->struct_size >= 40)
       reinterpret_cast<vts_transcode_ext_info3 *>(xinfo)->early_skip_mbs = opt.early_skip ? static_cast<int64_t>(st[8]) : 0;
+    if (xinfo->struct_size >= 56)
+      reinterpret_cast<vts_transcode_ext_info4 *>(xinfo)->intra4x4_mbs = opt.intra4x4 ? static_cast<int64_t>(st[9]) : 0;
   }
   return VTS_OK;
 }

@@ -165,6 +165,18 @@ class TranscodeExtInfo3(C.Structure):
     _fields_ = [("base", TranscodeExtInfo2), ("early_skip_mbs", C.c_int64), ("cmd_words", C.c_int64)]
 
 
+class TranscodeExt5(C.Structure):
+    """vts_transcode_ext5: begins with TranscodeExt4; passed to vts_transcode_ex by
+    pointer cast with base.base.base.base.struct_size = sizeof(TranscodeExt5)."""
+    _fields_ = [("base", TranscodeExt4), ("intra4x4", C.c_int32), ("_pad3", C.c_int32),
+                ("i4_out", C.POINTER(C.c_uint64)), ("i4_cap", C.c_int64)]
+
+
+class TranscodeExtInfo4(C.Structure):
+    """vts_transcode_ext_info4: begins with TranscodeExtInfo3; as TranscodeExt5."""
+    _fields_ = [("base", TranscodeExtInfo3), ("intra4x4_mbs", C.c_int64), ("i4_words", C.c_int64)]
+
+
 class ManifestArgs(C.Structure):
     _fields_ = [("video_id", C.c_char_p), ("segment_dir", C.c_char_p),
                 ("created_at", C.c_char_p), ("duration", C.c_double),

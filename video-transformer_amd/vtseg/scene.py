@@ -265,7 +265,7 @@ class VideoScorer:
                   subpel: int = 0, deblock: bool = False,
                   deblock_offsets: tuple[int, int] = (0, 0), mvcost: bool = False,
                   early_skip: bool = False, mv_lambda16: int = 0, want_commands: bool = False,
-                  cabac: bool = False) -> dict:
+                  cabac: bool = False, intra4x4: bool = False, want_intra4_modes: bool = False) -> dict:
         """360p upload transcode of this video into `out_path`
         (vts_transcode_ex): decode + score + area downscale +
         device H.264 encode with a quantised residual at `qp` (<= 0: none, the
@@ -290,7 +290,15 @@ class VideoScorer:
         profile stream instead of CAVLC in a Constrained Baseline one; the
         coding is lossless, so every decision, count, command word and
         `recon_hash` is that of the same call without it; needs `qp` > 0; off,
-        every byte is as before.  Returns the facts (with `intra`, `subpel`, `deblock`, `mvcost`
+        every byte is as before.  `intra4x4`: every macroblock `intra` codes is
+        also tried as I_NxN with sixteen Intra_4x4 blocks and becomes that when
+        it takes strictly fewer bits than the Intra16x16 candidate; needs
+        `intra` and `qp` > 0; off, every byte is as before; the result then
+        holds `intra4x4_mbs`, the I_NxN share of `intra_mbs`.
+        `want_intra4_modes`: the result also holds `intra4_modes`, a uint64
+        array (n_frames, mbh, mbw): nibble k of an I_NxN macroblock's word is
+        the Intra4x4PredMode of luma4x4BlkIdx k, every other word is ~0.
+        Returns the facts (with `intra`, `subpel`, `deblock`, `mvcost`
         or `early_skip` also the encoder's `recon_hash`) and per-stage
         milliseconds; with one of the last four keywords also
         `early_skip_mbs`."""
@@ -304,29 +312,44 @@ class VideoScorer:
         prm.qp = qp if qp > 0 else -1
         prm.intra = 1 if intra else 0
         info = _lib.TranscodeInfo()
-        ext4 = _lib.TranscodeExt4(_lib.TranscodeExt3(
-            _lib.TranscodeExt2(_lib.TranscodeExt(C.sizeof(_lib.TranscodeExt4), subpel),
+        # the Intra4x4 structs only with their keywords: without them the call is the one it was
+        i4 = bool(intra4x4 or want_intra4_modes)
+        ext5 = _lib.TranscodeExt5(_lib.TranscodeExt4(_lib.TranscodeExt3(
+            _lib.TranscodeExt2(_lib.TranscodeExt(C.sizeof(_lib.TranscodeExt5 if i4 else _lib.TranscodeExt4), subpel),
                                1 if deblock else 0, int(deblock_offsets[0]), int(deblock_offsets[1])),
-            1 if mvcost else 0, int(mv_lambda16), 1 if early_skip else 0), 1 if cabac else 0)
-        ext = ext4.base
-        xinfo3 = _lib.TranscodeExtInfo3(_lib.TranscodeExtInfo2(
-            _lib.TranscodeExtInfo(C.sizeof(_lib.TranscodeExtInfo3))))
+            1 if mvcost else 0, int(mv_lambda16), 1 if early_skip else 0), 1 if cabac else 0),
+            1 if intra4x4 else 0)
+        ext = ext5.base.base
+        xinfo4 = _lib.TranscodeExtInfo4(_lib.TranscodeExtInfo3(_lib.TranscodeExtInfo2(
+            _lib.TranscodeExtInfo(C.sizeof(_lib.TranscodeExtInfo4 if i4 else _lib.TranscodeExtInfo3)))))
+        xinfo3 = xinfo4.base
         xinfo2 = xinfo3.base
         xinfo = xinfo2.base
-        commands = None
-        if want_commands:
+        commands = modes = None
+        if want_commands or want_intra4_modes:
             # the coded macroblock grid of the output: width as ffmpeg's scale=-2, both 16-aligned
             w, h = int(self.info.width), int(self.info.height)
             sw = (height * w + h) // (2 * h) * 2
             mbw, mbh = (sw + 15) // 16, (height + 15) // 16
+        if want_commands:
             commands = np.zeros((int(self.info.n_frames), mbh, mbw), np.uint32)
             ext.cmd_out = commands.ctypes.data_as(C.POINTER(C.c_uint32))
             ext.cmd_cap = commands.size
+        if want_intra4_modes:
+            modes = np.zeros((int(self.info.n_frames), mbh, mbw), np.uint64)
+            ext5.i4_out = modes.ctypes.data_as(C.POINTER(C.c_uint64))
+            ext5.i4_cap = modes.size
         _lib.check(self._lib.vts_transcode_ex(self._ctx, str(out_path).encode(), C.byref(prm),
-                                              C.cast(C.pointer(ext4), C.POINTER(_lib.TranscodeExt)),
+                                              C.cast(C.pointer(ext5), C.POINTER(_lib.TranscodeExt)),
                                               C.byref(info),
-                                              C.cast(C.pointer(xinfo3), C.POINTER(_lib.TranscodeExtInfo))))
+                                              C.cast(C.pointer(xinfo4), C.POINTER(_lib.TranscodeExtInfo))))
         extra = {}
+        if i4:
+            extra["intra4x4_mbs"] = xinfo4.intra4x4_mbs
+        if want_intra4_modes:
+            if xinfo4.i4_words != modes.size:
+                raise RuntimeError(f"{xinfo4.i4_words} mode words, expected {modes.size}")
+            extra["intra4_modes"] = modes
         if mvcost or early_skip or mv_lambda16 or want_commands:   # only with a new keyword
             extra["early_skip_mbs"] = xinfo3.early_skip_mbs
         if want_commands:
