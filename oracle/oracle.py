@@ -89,6 +89,13 @@ def lib() -> C.CDLL:
                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.or_transcode_ex2.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -374,11 +381,19 @@ def sps_pps(mbw: int, mbh: int, crop_r: int, crop_b: int, fps: float) -> tuple[b
     return bytes(sps[:sn.value]), bytes(pps[:pn.value])
 
 
+# or_transcode_ex2's decision counters, in the order of transcode_oracle.c's enum
+DECISION_COUNTERS = tuple(f"mode{m}" for m in range(9)) + (
+    "discount_blocks", "cost_tie_blocks", "i4_won_mbs", "i16_won_mbs", "equal_bits_mbs", "i4_pcm_mbs",
+    "cost_decided_vectors", "early_skip_hits", "inter_predictor_mbs")
+
+
 def transcode(frames: np.ndarray, width: int, height: int, scores: np.ndarray, *,
               threshold: float = 0.08, out_height: int = 360, search_range: int = 8,
               max_mb_sad: int = 1536, keyint: int = 250, idr_at_cuts: bool = False,
               want_recon: bool = False, qp: int = 28, intra: bool = False, subpel: int = 0,
-              deblock: bool = False, deblock_offsets: tuple[int, int] = (0, 0)) -> dict:
+              deblock: bool = False, deblock_offsets: tuple[int, int] = (0, 0), mvcost: bool = False,
+              early_skip: bool = False, mv_lambda16: int = 0, intra4x4: bool = False,
+              want_words: bool = False) -> dict:
     """The upload transcode of display-size NV12 frames [F, H*3/2, W] with
     their scene scores: output samples (bytes), per-frame sizes / sync flags,
     SPS/PPS, stats and (optionally) the encoder's reconstruction.  qp >= 1:
@@ -389,7 +404,15 @@ def transcode(frames: np.ndarray, width: int, height: int, scores: np.ndarray, *
     encoder's opt-in paths of the same names; with them the
     reconstruction is the filtered one, and the result also counts
     `intra_mbs`, `subpel_mbs`, `qpel_mbs` and `deblock_mbs` as the device's
-    facts do.  All off: or_transcode's bytes."""
+    facts do.  All off: or_transcode's bytes.  `mvcost`, `early_skip`,
+    `mv_lambda16` and `intra4x4` are the rules of the same names
+    (or_transcode_ex2); with one of them, or with `want_words`, the result also
+    holds `early_skip_mbs`, `intra4x4_mbs`, `counters` (DECISION_COUNTERS: what
+    the input made the rules decide) and, with `want_words`, `commands`
+    (uint32 [F, mbh, mbw]), `intra4_modes` (uint64, ~0 where not I_NxN) and
+    `candidate_bits` (int32 [F, mbh, mbw, 2]: Intra16x16, I_NxN; 0 where
+    `intra4x4` did not try both), in the device's encodings (include/vtseg.h).
+    All five at their defaults: or_transcode_ex's bytes, by that entry."""
     F = frames.shape[0]
     sw = small_width(width, height, out_height)
     cw, ch = (sw + 15) & ~15, (out_height + 15) & ~15
@@ -406,7 +429,26 @@ def transcode(frames: np.ndarray, width: int, height: int, scores: np.ndarray, *
     n = C.c_int64(0)
     tail = (out.ctypes.data, cap, off.ctypes.data, size.ctypes.data, sync.ctypes.data,
             recon.ctypes.data if recon is not None else None, stats.ctypes.data, C.byref(n))
-    if intra or subpel or deblock or tuple(deblock_offsets) != (0, 0):
+    extra = {}
+    if mvcost or early_skip or mv_lambda16 or intra4x4 or want_words:
+        stats = np.zeros(10, np.int64)
+        counters = np.zeros(len(DECISION_COUNTERS), np.int64)
+        words = np.zeros((F, mbh, mbw), np.uint32) if want_words else None
+        modes = np.zeros((F, mbh, mbw), np.uint64) if want_words else None
+        cbits = np.zeros((F, mbh, mbw, 2), np.int32) if want_words else None
+        rc = lib().or_transcode_ex2(fr.ctypes.data, F, width, height, sc.ctypes.data, threshold,
+                                    int(idr_at_cuts), out_height, search_range, max_mb_sad, keyint, int(qp),
+                                    int(bool(intra)), int(subpel), int(bool(deblock)),
+                                    int(deblock_offsets[0]), int(deblock_offsets[1]), int(bool(mvcost)),
+                                    int(bool(early_skip)), int(mv_lambda16), int(bool(intra4x4)),
+                                    *tail[:6], stats.ctypes.data,
+                                    *(a.ctypes.data if a is not None else None for a in (words, modes, cbits)),
+                                    counters.ctypes.data, C.byref(n))
+        extra = {"early_skip_mbs": int(stats[8]), "intra4x4_mbs": int(stats[9]),
+                 "counters": dict(zip(DECISION_COUNTERS, map(int, counters)))}
+        if want_words:
+            extra.update(commands=words, intra4_modes=modes, candidate_bits=cbits)
+    elif intra or subpel or deblock or tuple(deblock_offsets) != (0, 0):
         rc = lib().or_transcode_ex(fr.ctypes.data, F, width, height, sc.ctypes.data, threshold,
                                    int(idr_at_cuts), out_height, search_range, max_mb_sad, keyint, int(qp),
                                    int(bool(intra)), int(subpel), int(bool(deblock)),
@@ -421,7 +463,7 @@ def transcode(frames: np.ndarray, width: int, height: int, scores: np.ndarray, *
             "samples": samples, "sync": sync.astype(bool), "recon": recon,
             "pcm_mbs": int(stats[0]), "inter_mbs": int(stats[1]), "skip_mbs": int(stats[2]),
             "n_idr": int(stats[3]), "intra_mbs": int(stats[4]), "subpel_mbs": int(stats[5]),
-            "qpel_mbs": int(stats[6]), "deblock_mbs": int(stats[7])}
+            "qpel_mbs": int(stats[6]), "deblock_mbs": int(stats[7]), **extra}
 
 
 def decode_samples(sps: bytes, pps: bytes, samples: list[bytes], nal_length_size: int = 4):

@@ -64,7 +64,36 @@
  * tests/test_transcode_oracle.py closes each of them through the general
  * oracle decoder (h264_full_oracle.c, which has its own 8.3.3, 8.4.2.2.1 and
  * 8.7); tests/test_transcode_bytes_gpu.py holds the device to these bytes.
+ *
+ * The rules merged since (or_transcode_ex2; DESIGN.md §11, "Rate-aware motion
+ * cost and early P_Skip", "Intra4x4" and "The byte oracle restates the rate
+ * rules and Intra4x4"), again off by default and then absent from every byte.
+ * They are written from that text and the standard, not from the product's
+ * headers or kernels (none is included), and reuse only this file's own fwd4 /
+ * quant1 / idct4 / block_bits / put_residual / Intra16x16:
+ *   - early_skip: before the search, the residual of the prediction at vector
+ *     (0, 0) through residual_mb; no level left: P_Skip, the prediction is the
+ *     reconstruction (encode_p);
+ *   - mvcost: the integer pass and both refinement steps order their
+ *     candidates by (16 SAD + lambda16 (selen(dx) + selen(dy)), index) against
+ *     the predictor guess: the left macroblock's final word in the previous
+ *     picture of the GOP (word_vector); lambda16 by the formula
+ *     (lambda16_formula), selen by 9.1 with a loop;
+ *   - intra4x4: every macroblock of the intra pass also as I_NxN
+ *     (intra4_candidate): availability by 6.4.x with one slice per row, the
+ *     nine predictions of 8.3.1.2.1 .. 9 one sample at a time (pred4_sample)
+ *     over reconstructed neighbours, predIntra4x4PredMode by 8.3.1.1
+ *     (pred_mode4), key (16 SAD + lambda16 (1 or 4), mode), exact bits by the
+ *     writer itself (put_i4_mb: 7.3.5, 7.3.5.1, Table 9-4's Intra column);
+ *     I_NxN when its bits < Intra16x16's, the winner coded when <= 3072 bits.
+ * It also returns the command and mode words in include/vtseg.h's encodings
+ * and counters of what the input made the rules decide.
+ * tests/test_transcode_oracle.py closes these through the general decoder
+ * (its own 8.3.1.2) and compares the Intra4x4 rule with the product's CPU
+ * harness; tests/test_transcode_bytes_rate_intra4_gpu.py holds the device's
+ * words, bytes, counts and hash to them.
  */
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -267,6 +296,8 @@ typedef struct {
   int cbp;            /* coded_block_pattern of an inter or Intra16x16 macroblock */
   int i16;            /* Intra16x16 (pcm = 0, no motion) */
   int lmode, cmode;   /* Intra16x16PredMode, intra_chroma_pred_mode */
+  int i4;             /* I_NxN, sixteen Intra_4x4 blocks (pcm = i16 = 0, no motion); levels in the inter layout */
+  uint64_t modes;     /* I_NxN: nibble k = Intra4x4PredMode of luma4x4BlkIdx k */
   int16_t lv[384];    /* levels in scan order: luma by luma4x4BlkIdx (16 x 16), Cb / Cr DC (2 x 4),
                          Cb / Cr AC by chroma4x4BlkIdx (8 x 15); Intra16x16: Intra16x16DCLevel in
                          [0, 16), Intra16x16ACLevel of block k in [16 + 15 k, 31 + 15 k) */
@@ -587,21 +618,117 @@ static void predict_mb(const uint8_t *ref, int cw, int ch, int mx, int my, int m
     }
 }
 
-/* encode one P picture's decisions and reconstruction (qp >= 1: residual coding) */
+/* ---- the opt-in rules of or_transcode_ex2 ("Rate-aware motion
+ * cost and early P_Skip", "Intra4x4") */
+
+/* the decision counters of or_transcode_ex2 (what the inputs of a test made
+ * the rules decide) */
+enum {
+  OC_MODE0 = 0,      /* [0, 9): blocks that chose Intra4x4PredMode 0 .. 8 */
+  OC_DISCOUNT = 9,   /* blocks whose winner is not the mode of least (SAD, mode): the rate term decided */
+  OC_COST_TIE = 10,  /* blocks whose least cost two or more modes share: the lower mode number decided */
+  OC_I4_WON = 11,    /* macroblocks whose I_NxN bits < their Intra16x16 bits */
+  OC_I16_WON = 12,   /* macroblocks whose I_NxN bits >= their Intra16x16 bits */
+  OC_EQUAL_BITS = 13,/* of those, equal bits (the tie that Intra16x16 wins) */
+  OC_I4_PCM = 14,    /* macroblocks left I_PCM by the 3072 bound although I_NxN was the cheaper */
+  OC_COST_MV = 15,   /* vector decisions (a pass of one macroblock) whose winner is not that of (SAD, index) */
+  OC_EARLY = 16,     /* early P_Skip hits */
+  OC_PHAT = 17,      /* searched macroblocks whose predictor guess is a non-zero vector of an inter word */
+  OC_N = 18
+};
+
+typedef struct {
+  int mvcost, early_skip, intra4x4;
+  int lambda_mv;  /* 16 lambda of the vector cost */
+  int lambda_i4;  /* 16 lambda of the Intra4x4 mode cost: always the formula's */
+} or_opts;
+
+/* 16 lambda of a SAD-domain Lagrangian: the square root of 0.85 2^((qp - 12) / 3), rounded */
+static int lambda16_formula(int qp) { return (int)(16.0 * sqrt(0.85 * pow(2.0, (qp - 12) / 3.0)) + 0.5); }
+
+/* the length of se(v) for the value k (9.1, 9.1.1): codeNum = 2|k| - (k > 0),
+ * leadingZeroBits = floor(log2(codeNum + 1)), 2 leadingZeroBits + 1 bits */
+static int selen(int k) {
+  uint32_t x = (k > 0 ? (uint32_t)(2 * k - 1) : (uint32_t)(-2 * k)) + 1;
+  int lz = 0;
+  while ((x >> lz) > 1) lz++;
+  return 2 * lz + 1;
+}
+
+/* the command word of a macroblock as include/vtseg.h documents it */
+static uint32_t mb_word(const or_mb *m) {
+  if (m->pcm) return 0x80008000u;
+  if (m->i16) return 0x80000000u | (uint32_t)(m->lmode | (m->cmode << 2) | (m->cbp << 4));
+  if (m->i4) return 0x80004000u | (uint32_t)((m->cmode << 2) | (m->cbp << 4));
+  return ((uint32_t)m->mvx & 0xffffu) | (((uint32_t)m->mvy & 0xffffu) << 16);
+}
+
+/* the vector an inter word holds, in quarter samples; (0, 0) for every intra kind */
+static void word_vector(uint32_t w, int *vx, int *vy) {
+  *vx = *vy = 0;
+  if ((w & 0xffff8000u) == 0x80000000u || w == 0x80008000u) return;  /* Intra16x16, I_NxN; I_PCM */
+  *vx = (int16_t)(w & 0xffffu);
+  *vy = (int16_t)(w >> 16);
+}
+
+/* encode one P picture's decisions and reconstruction (qp >= 1: residual coding).
+ * o: the opt-in rules (all zero: none); pw: the final command words of the
+ * previous picture, j: this picture's position in its GOP (for the predictor
+ * guess of the vector cost); cnt: the decision counters */
 static void encode_p(const uint8_t *src, const uint8_t *ref, uint8_t *rec, int cw, int ch, int R,
-                     int T, int qp, int subpel, or_mb *mbs, int64_t *stats) {
+                     int T, int qp, int subpel, const or_opts *o, const uint32_t *pw, int gop_j, or_mb *mbs,
+                     int64_t *stats, int64_t *cnt) {
   int mbw = cw / 16, mbh = ch / 16;
   const uint8_t *suv = src + (int64_t)cw * ch;
   uint8_t *ruv = rec + (int64_t)cw * ch;
   int side = 2 * R + 1, ncand = side * side, center = R * side + R;
-  int64_t n_frac = 0, n_quarter = 0;
+  int64_t n_frac = 0, n_quarter = 0, n_early = 0, n_costmv = 0, n_phat = 0;
+  int rate_ok = qp >= 1 && T >= 0;  /* both rules need residual coding and inter macroblocks */
+  int lam = (o->mvcost && rate_ok) ? o->lambda_mv : 0;
   /* the macroblocks of a P picture are independent of each other (each reads
    * the previous picture): threads only shorten the checker's run */
-#pragma omp parallel for collapse(2) schedule(dynamic, 4) reduction(+ : n_frac, n_quarter)
+#pragma omp parallel for collapse(2) schedule(dynamic, 4) reduction(+ : n_frac, n_quarter, n_early, n_costmv, n_phat)
   for (int my = 0; my < mbh; my++)
     for (int mx = 0; mx < mbw; mx++) {
-      int64_t best = -1;
-      int bdx = 0, bdy = 0;
+      uint8_t py[256], pu[64], pv[64];
+      or_mb *m = &mbs[my * mbw + mx];
+      if (o->early_skip && rate_ok) {
+        /* (a) early P_Skip: the residual at vector (0, 0) quantises to nothing */
+        uint8_t sy[256], su[64], sv[64], ry[256], ru[64], rv[64];
+        for (int j = 0; j < 16; j++)
+          for (int i = 0; i < 16; i++) sy[j * 16 + i] = src[(int64_t)(my * 16 + j) * cw + mx * 16 + i];
+        for (int j = 0; j < 8; j++)
+          for (int i = 0; i < 8; i++) {
+            int64_t q = (int64_t)(my * 8 + j) * cw + 2 * (mx * 8 + i);
+            su[j * 8 + i] = suv[q];
+            sv[j * 8 + i] = suv[q + 1];
+          }
+        predict_mb(ref, cw, ch, mx, my, 0, 0, py, pu, pv);
+        residual_mb(sy, su, sv, py, pu, pv, qp, m, ry, ru, rv);
+        if (m->cbp == 0) {  /* decided: vector (0, 0), word 0, the prediction is the reconstruction */
+          m->pcm = m->i16 = m->i4 = m->mvx = m->mvy = 0;
+          for (int j = 0; j < 16; j++)
+            for (int i = 0; i < 16; i++) rec[(int64_t)(my * 16 + j) * cw + mx * 16 + i] = py[j * 16 + i];
+          for (int j = 0; j < 8; j++)
+            for (int i = 0; i < 8; i++) {
+              int64_t q = (int64_t)(my * 8 + j) * cw + 2 * (mx * 8 + i);
+              ruv[q] = pu[j * 8 + i];
+              ruv[q + 1] = pv[j * 8 + i];
+            }
+          n_early++;
+          continue;
+        }
+      }
+      /* (b) the predictor guess of the vector cost: (0, 0) in column 0 and in
+       * the first P picture of a GOP, else what the final word of the left
+       * macroblock in the previous picture holds */
+      int phx = 0, phy = 0;
+      if (lam && mx > 0 && gop_j > 1) word_vector(pw[my * mbw + mx - 1], &phx, &phy);
+      if (phx || phy) n_phat++;
+      /* the integer pass: key (16 SAD + lambda16 bits(v - guess), index), index
+       * 0 the centre, then raster order; the least key wins (lam = 0: the SAD's order) */
+      int64_t best = -1, best_sad = 0, least_sad = -1;
+      int bdx = 0, bdy = 0, least_c = 0, best_c = 0;
       for (int c = 0; c < ncand; c++) {
         int r = c == 0 ? center : (c - 1 < center ? c - 1 : c);
         int dy = r / side - R, dx = r % side - R;
@@ -611,24 +738,34 @@ static void encode_p(const uint8_t *src, const uint8_t *ref, uint8_t *rec, int c
           for (int i = 0; i < 16; i++)
             s += abs((int)ref[(int64_t)clampi(y0 + j, 0, ch - 1) * cw + clampi(x0 + i, 0, cw - 1)] -
                      (int)src[(int64_t)(my * 16 + j) * cw + mx * 16 + i]);
-        if (best < 0 || s < best) { best = s; bdx = dx; bdy = dy; }
+        int64_t cost = 16 * s + (int64_t)lam * (selen(4 * dx - phx) + selen(4 * dy - phy));
+        if (least_sad < 0 || s < least_sad) { least_sad = s; least_c = c; }
+        if (best < 0 || cost < best) { best = cost; best_sad = s; best_c = c; bdx = dx; bdy = dy; }
       }
-      uint8_t py[256], pu[64], pv[64];
+      if (best_c != least_c) n_costmv++;
       /* sub-sample refinement: around the
        * integer winner in steps of 2, then (subpel == 2) around that winner in
-       * steps of 1; key (SAD, index), the centre index 0, the other eight 1..8
-       * in raster order of (j, i); the least key wins */
+       * steps of 1; key (cost, index), the centre index 0 with its bits counted
+       * anew, the other eight 1..8 in raster order of (j, i); the least key wins */
       int wmvx = 4 * bdx, wmvy = 4 * bdy;
-      int64_t wsad = best;
+      int64_t wsad = best_sad;
       for (int step = 2; subpel >= 1 && step >= (subpel == 2 ? 1 : 2); step >>= 1) {
         int cx = wmvx, cy = wmvy;  /* the centre keeps its SAD and wins ties; then raster order */
+        int64_t wcost = 16 * wsad + (int64_t)lam * (selen(cx - phx) + selen(cy - phy));
+        int64_t lsad = wsad;
+        int idx = 0, widx = 0, lidx = 0;
         for (int j = -1; j <= 1; j++)
           for (int i = -1; i <= 1; i++) {
             if (!i && !j) continue;
-            predict_luma(ref, cw, ch, mx, my, cx + step * i, cy + step * j, py);
+            idx++;
+            int vx = cx + step * i, vy = cy + step * j;
+            predict_luma(ref, cw, ch, mx, my, vx, vy, py);
             int64_t s = luma_sad(src, cw, mx, my, py);
-            if (s < wsad) { wsad = s; wmvx = cx + step * i; wmvy = cy + step * j; }
+            int64_t cost = 16 * s + (int64_t)lam * (selen(vx - phx) + selen(vy - phy));
+            if (s < lsad) { lsad = s; lidx = idx; }
+            if (cost < wcost) { wcost = cost; wsad = s; widx = idx; wmvx = vx; wmvy = vy; }
           }
+        if (widx != lidx) n_costmv++;
       }
       predict_mb(ref, cw, ch, mx, my, wmvx, wmvy, py, pu, pv);
       int64_t cost = 0;
@@ -640,7 +777,6 @@ static void encode_p(const uint8_t *src, const uint8_t *ref, uint8_t *rec, int c
           int64_t o = (int64_t)(my * 8 + j) * cw + 2 * (mx * 8 + i);
           cost += abs((int)pu[j * 8 + i] - (int)suv[o]) + abs((int)pv[j * 8 + i] - (int)suv[o + 1]);
         }
-      or_mb *m = &mbs[my * mbw + mx];
       m->cbp = 0;
       int inter;
       if (qp >= 1) {  /* residual coding: inter unless the residual costs more than I_PCM */
@@ -667,7 +803,7 @@ static void encode_p(const uint8_t *src, const uint8_t *ref, uint8_t *rec, int c
         inter = T >= 0 && cost <= T;
       }
       m->pcm = !inter;
-      m->i16 = 0;
+      m->i16 = m->i4 = 0;
       m->mvx = inter ? wmvx : 0;
       m->mvy = inter ? wmvy : 0;
       if (inter && ((wmvx | wmvy) & 3)) {  /* a fractional vector; one with an odd component */
@@ -688,6 +824,10 @@ static void encode_p(const uint8_t *src, const uint8_t *ref, uint8_t *rec, int c
     }
   stats[5] += n_frac;
   stats[6] += n_quarter;
+  stats[8] += n_early;
+  cnt[OC_EARLY] += n_early;
+  cnt[OC_COST_MV] += n_costmv;
+  cnt[OC_PHAT] += n_phat;
 }
 
 /* residual() of an inter macroblock (7.3.5.3) with nC from the left
@@ -830,15 +970,22 @@ static void i16_dc_scale(const int *c, int qp, int *dcy) {
     dcy[k] = qp >= 36 ? (f[k] * ls) << (qp / 6 - 6) : (f[k] * ls + (1 << (5 - qp / 6))) >> (6 - qp / 6);
 }
 
-/* Try macroblock (mx, my) as Intra16x16 (the Intra16x16 rules):
+/* a candidate coding of one macroblock: its reconstruction and what is coded */
+typedef struct {
+  uint8_t y[256], c[2][64];
+  or_mb m;
+  int bits;  /* macroblock_layer() without mb_skip_run, exact */
+} or_cand;
+
+/* Macroblock (mx, my) as Intra16x16 (the Intra16x16 rules):
  * prediction from the left macroblock's right column of this picture's
- * unfiltered reconstruction rec (the row above is another slice); returns 1 and
- * writes the reconstruction and m when its exact bits are <= 3072, else 0 (the
- * macroblock is I_PCM: rec holds the source).  lnz / lnzc as put_intra_mb's. */
-static int encode_intra_mb(const uint8_t *src, uint8_t *rec, int cw, int ch, int mx, int my, int qp, int p_slice,
-                           const int *lnz, const int (*lnzc)[2], or_mb *m) {
+ * unfiltered reconstruction rec (the row above is another slice).  Fills the
+ * candidate: reconstruction, levels, modes, pattern and exact bits; rec is only
+ * read.  lnz / lnzc as put_intra_mb's. */
+static void intra16_candidate(const uint8_t *src, const uint8_t *rec, int cw, int ch, int mx, int my, int qp,
+                              int p_slice, const int *lnz, const int (*lnzc)[2], or_cand *cd) {
   const uint8_t *suv = src + (int64_t)cw * ch;
-  uint8_t *ruv = rec + (int64_t)cw * ch;
+  const uint8_t *ruv = rec + (int64_t)cw * ch;
   int py[16], pc[2][8];  /* both modes are constant along a row: the prediction of each row */
   int lmode = 2, cmode = 0;  /* no neighbour: DC (128) for luma and chroma */
   for (int j = 0; j < 16; j++) py[j] = 128;
@@ -954,7 +1101,7 @@ static int encode_intra_mb(const uint8_t *src, uint8_t *rec, int cw, int ch, int
   int cc = cacnz ? 2 : (cdcnz ? 1 : 0);
   t.cbp = (acnz ? 15 : 0) | (cc << 4);
   int cnz[16], cnzc[2][4];
-  if (put_intra_mb(NULL, &t, p_slice, lnz, lnzc, cnz, cnzc) > 3072) return 0;
+  cd->bits = put_intra_mb(NULL, &t, p_slice, lnz, lnzc, cnz, cnzc);
   /* reconstruction: the decoder's (8.5.10 DC, 8.5.12; uncoded AC reads as zero) */
   for (int k = 0; k < 16; k++) {
     int bx = BLK_X[k] * 4, by = BLK_Y[k] * 4, co[16], r[16];
@@ -963,7 +1110,7 @@ static int encode_intra_mb(const uint8_t *src, uint8_t *rec, int cw, int ch, int
     idct4(co, qp, 1, r);
     for (int i = 0; i < 4; i++)
       for (int j = 0; j < 4; j++)
-        rec[(int64_t)(my * 16 + by + i) * cw + mx * 16 + bx + j] = (uint8_t)clip255(py[by + i] + r[i * 4 + j]);
+        cd->y[(by + i) * 16 + bx + j] = (uint8_t)clip255(py[by + i] + r[i * 4 + j]);
   }
   for (int pl = 0; pl < 2; pl++) {
     const int *c = cdl[pl];
@@ -976,18 +1123,224 @@ static int encode_intra_mb(const uint8_t *src, uint8_t *rec, int cw, int ch, int
       idct4(co, qpc, 1, r);
       for (int i = 0; i < 4; i++)
         for (int j = 0; j < 4; j++)
-          ruv[(int64_t)(my * 8 + by + i) * cw + 2 * (mx * 8 + bx + j) + pl] = (uint8_t)clip255(pc[pl][by + i] + r[i * 4 + j]);
+          cd->c[pl][(by + i) * 8 + bx + j] = (uint8_t)clip255(pc[pl][by + i] + r[i * 4 + j]);
     }
   }
-  *m = t;
-  return 1;
+  cd->m = t;
+}
+
+/* ---------------------------------------------------- Intra4x4 (intra4x4 = 1) */
+
+/* Table 9-4 (chroma_format_idc 1), Intra_4x4 column: codeNum -> coded_block_pattern */
+static const int CBP_I[48] = {47, 31, 15, 0,  23, 27, 29, 30, 7,  11, 13, 14, 39, 43, 45, 46,
+                              16, 3,  5,  10, 12, 19, 21, 26, 28, 35, 37, 42, 44, 1,  2,  4,
+                              8,  17, 18, 20, 24, 6,  9,  22, 25, 32, 33, 34, 36, 40, 38, 41};
+
+/* luma4x4BlkIdx of the block at raster column bx, row by (6.4.3 inverted) */
+static int blk_at(int bx, int by) {
+  int k = 0;
+  while (BLK_X[k] != bx || BLK_Y[k] != by) k++;
+  return k;
+}
+
+/* the neighbouring samples p[x, -1], x = -1 .. 7, and p[-1, y], y = 0 .. 3 of a 4x4 block (8.3.1.2) */
+typedef struct {
+  int top[9];  /* top[x + 1] = p[x, -1] */
+  int left[4]; /* left[y] = p[-1, y] */
+  int has_left, has_top;
+} or_nb4;
+static int nbp(const or_nb4 *n, int x, int y) { return y < 0 ? n->top[x + 1] : n->left[y]; }
+
+/* pred4x4L[x, y] of Intra4x4PredMode mode, 8.3.1.2.1 .. 8.3.1.2.9, one sample */
+static int pred4_sample(const or_nb4 *n, int mode, int x, int y) {
+  switch (mode) {
+    case 0: return nbp(n, x, -1);                                                       /* Vertical */
+    case 1: return nbp(n, -1, y);                                                       /* Horizontal */
+    case 2: {                                                                           /* DC */
+      int st = 0, sl = 0;
+      for (int i = 0; i < 4; i++) { st += nbp(n, i, -1); sl += nbp(n, -1, i); }
+      if (n->has_top && n->has_left) return (st + sl + 4) >> 3;
+      if (n->has_left) return (sl + 2) >> 2;
+      if (n->has_top) return (st + 2) >> 2;
+      return 128;
+    }
+    case 3:                                                                             /* Diagonal_Down_Left */
+      if (x == 3 && y == 3) return (nbp(n, 6, -1) + 3 * nbp(n, 7, -1) + 2) >> 2;
+      return (nbp(n, x + y, -1) + 2 * nbp(n, x + y + 1, -1) + nbp(n, x + y + 2, -1) + 2) >> 2;
+    case 4:                                                                             /* Diagonal_Down_Right */
+      if (x > y) return (nbp(n, x - y - 2, -1) + 2 * nbp(n, x - y - 1, -1) + nbp(n, x - y, -1) + 2) >> 2;
+      if (x < y) return (nbp(n, -1, y - x - 2) + 2 * nbp(n, -1, y - x - 1) + nbp(n, -1, y - x) + 2) >> 2;
+      return (nbp(n, 0, -1) + 2 * nbp(n, -1, -1) + nbp(n, -1, 0) + 2) >> 2;
+    case 5: {                                                                           /* Vertical_Right */
+      int z = 2 * x - y, h = y >> 1;
+      if (z >= 0 && !(z & 1)) return (nbp(n, x - h - 1, -1) + nbp(n, x - h, -1) + 1) >> 1;
+      if (z >= 0) return (nbp(n, x - h - 2, -1) + 2 * nbp(n, x - h - 1, -1) + nbp(n, x - h, -1) + 2) >> 2;
+      if (z == -1) return (nbp(n, -1, 0) + 2 * nbp(n, -1, -1) + nbp(n, 0, -1) + 2) >> 2;
+      return (nbp(n, -1, y - 1) + 2 * nbp(n, -1, y - 2) + nbp(n, -1, y - 3) + 2) >> 2;
+    }
+    case 6: {                                                                           /* Horizontal_Down */
+      int z = 2 * y - x, h = x >> 1;
+      if (z >= 0 && !(z & 1)) return (nbp(n, -1, y - h - 1) + nbp(n, -1, y - h) + 1) >> 1;
+      if (z >= 0) return (nbp(n, -1, y - h - 2) + 2 * nbp(n, -1, y - h - 1) + nbp(n, -1, y - h) + 2) >> 2;
+      if (z == -1) return (nbp(n, -1, 0) + 2 * nbp(n, -1, -1) + nbp(n, 0, -1) + 2) >> 2;
+      return (nbp(n, x - 1, -1) + 2 * nbp(n, x - 2, -1) + nbp(n, x - 3, -1) + 2) >> 2;
+    }
+    case 7: {                                                                           /* Vertical_Left */
+      int h = y >> 1;
+      if (!(y & 1)) return (nbp(n, x + h, -1) + nbp(n, x + h + 1, -1) + 1) >> 1;
+      return (nbp(n, x + h, -1) + 2 * nbp(n, x + h + 1, -1) + nbp(n, x + h + 2, -1) + 2) >> 2;
+    }
+    default: {                                                                          /* Horizontal_Up */
+      int z = x + 2 * y, h = x >> 1;
+      if (z > 5) return nbp(n, -1, 3);
+      if (z == 5) return (nbp(n, -1, 2) + 3 * nbp(n, -1, 3) + 2) >> 2;
+      if (!(z & 1)) return (nbp(n, -1, y + h) + nbp(n, -1, y + h + 1) + 1) >> 1;
+      return (nbp(n, -1, y + h) + 2 * nbp(n, -1, y + h + 1) + nbp(n, -1, y + h + 2) + 2) >> 2;
+    }
+  }
+}
+
+/* predIntra4x4PredMode of block k (8.3.1.1) with one slice per macroblock row:
+ * the macroblock above is never available and the one to the left only for mx >
+ * 0, so dcPredModePredictedFlag holds for the top row and for column 0 at mx = 0
+ * (2); a left macroblock that is not I_NxN counts as 2 (no constrained intra
+ * prediction); else Min(A, B).  cur: the modes of this macroblock so far */
+static int pred_mode4(int k, uint64_t cur, int mx, const or_mb *left) {
+  int bx = BLK_X[k], by = BLK_Y[k];
+  if (by == 0 || (bx == 0 && mx == 0)) return 2;
+  int a = bx ? (int)((cur >> (4 * blk_at(bx - 1, by))) & 15)
+             : (left->i4 ? (int)((left->modes >> (4 * blk_at(3, by))) & 15) : 2);
+  int b = (int)((cur >> (4 * blk_at(bx, by - 1))) & 15);
+  return a < b ? a : b;
+}
+
+/* macroblock_layer() of an I_NxN macroblock (7.3.5, 7.3.5.1) without its
+ * mb_skip_run: mb_type 0 (5 in a P slice), the sixteen prev_intra4x4_pred_mode_flag
+ * / rem_intra4x4_pred_mode, intra_chroma_pred_mode, coded_block_pattern me(v)
+ * by the Intra_4x4 column, mb_qp_delta 0 with a pattern, residual() in the shape
+ * of an inter macroblock's.  left: the macroblock to the left (NULL at mx = 0).
+ * b == NULL only counts.  Returns the bits; cnz / cnzc as put_intra_mb's. */
+static int put_i4_mb(or_bw *b, const or_mb *m, int p_slice, int mx, const or_mb *left, const int *lnz,
+                     const int (*lnzc)[2], int *cnz, int (*cnzc)[4]) {
+  or_bw cnt = {NULL, 0, 0, 0, 0};
+  if (!b) b = &cnt;
+  int64_t before = b->n * 8 + b->nb;
+  bw_ue(b, p_slice ? 5 : 0);
+  uint64_t cur = 0;
+  for (int k = 0; k < 16; k++) {
+    int mode = (int)((m->modes >> (4 * k)) & 15), pm = pred_mode4(k, cur, mx, left);
+    if (mode == pm) {
+      bw_bit(b, 1);  /* prev_intra4x4_pred_mode_flag */
+    } else {
+      bw_bit(b, 0);
+      bw_u(b, 3, (uint32_t)(mode < pm ? mode : mode - 1));  /* rem_intra4x4_pred_mode */
+    }
+    cur |= (uint64_t)mode << (4 * k);
+  }
+  bw_ue(b, (uint32_t)m->cmode);
+  int code = 0;
+  while (CBP_I[code] != m->cbp) code++;
+  bw_ue(b, (uint32_t)code);
+  if (m->cbp) {
+    bw_se(b, 0);
+    put_residual(b, m, lnz, lnzc, cnz, cnzc);
+  } else {
+    for (int i = 0; i < 16; i++) cnz[i] = 0;
+    for (int pl = 0; pl < 2; pl++)
+      for (int i = 0; i < 4; i++) cnzc[pl][i] = 0;
+  }
+  return (int)(b->n * 8 + b->nb - before);
+}
+
+/* Macroblock (mx, my) as I_NxN ("Intra4x4", the rules).  The
+ * blocks in luma4x4BlkIdx order, each predicted from the reconstruction of the
+ * blocks before it and of the left macroblock's right column in rec; chroma
+ * (mode, levels, reconstruction, pattern class) is the Intra16x16 candidate's.
+ * Fills the candidate as intra16_candidate does. */
+static void intra4_candidate(const uint8_t *src, const uint8_t *rec, int cw, int mx, int my, int qp, int p_slice,
+                             int lambda16, const or_mb *left, const int *lnz, const int (*lnzc)[2],
+                             const or_cand *c16, or_cand *cd, int64_t *cnt) {
+  int qbits = 15 + qp / 6;
+  int64_t f = ((int64_t)1 << qbits) / 6;
+  or_mb t;
+  memset(&t, 0, sizeof t);
+  t.i4 = 1;
+  t.cmode = c16->m.cmode;
+  memcpy(t.lv + 256, c16->m.lv + 256, 128 * sizeof(int16_t));
+  memcpy(cd->c, c16->c, sizeof cd->c);
+  int cbp = c16->m.cbp & 0x30;
+  for (int k = 0; k < 16; k++) {
+    int bx = BLK_X[k], by = BLK_Y[k];
+    /* availability (6.4.x; the row above the macroblock is another slice) */
+    or_nb4 n;
+    memset(&n, 0, sizeof n);
+    n.has_left = bx > 0 || mx > 0;
+    n.has_top = by > 0;
+    int has_tl = n.has_left && n.has_top;
+    int has_tr = n.has_top && bx < 3 && blk_at(bx + 1, by - 1) < k;  /* inside the macroblock and earlier */
+    for (int y = 0; y < 4 && n.has_left; y++)
+      n.left[y] = bx ? cd->y[(by * 4 + y) * 16 + bx * 4 - 1] : rec[(int64_t)(my * 16 + by * 4 + y) * cw + mx * 16 - 1];
+    if (has_tl) n.top[0] = bx ? cd->y[(by * 4 - 1) * 16 + bx * 4 - 1] : rec[(int64_t)(my * 16 + by * 4 - 1) * cw + mx * 16 - 1];
+    for (int x = 0; x < 8 && n.has_top; x++)  /* p[4 .. 7, -1] not available: p[3, -1] in their place */
+      n.top[x + 1] = cd->y[(by * 4 - 1) * 16 + bx * 4 + ((x < 4 || has_tr) ? x : 3)];
+    int pm = pred_mode4(k, t.modes, mx, left);
+    int64_t best = -1, least_sad = -1;
+    int bmode = 2, lmode = 2, nbest = 0, s4[16];
+    for (int i = 0; i < 4; i++)
+      for (int j = 0; j < 4; j++) s4[i * 4 + j] = src[(int64_t)(my * 16 + by * 4 + i) * cw + mx * 16 + bx * 4 + j];
+    for (int mode = 0; mode < 9; mode++) {
+      int ok = mode == 2 ? 1
+               : (mode == 0 || mode == 3 || mode == 7) ? n.has_top
+               : (mode == 1 || mode == 8) ? n.has_left
+                                          : has_tl;
+      if (!ok) continue;
+      int64_t sad = 0;
+      for (int y = 0; y < 4; y++)
+        for (int x = 0; x < 4; x++) sad += abs(s4[y * 4 + x] - pred4_sample(&n, mode, x, y));
+      int64_t cost = 16 * sad + (int64_t)lambda16 * (mode == pm ? 1 : 4);
+      if (least_sad < 0 || sad < least_sad) { least_sad = sad; lmode = mode; }
+      if (best < 0 || cost < best) { best = cost; bmode = mode; nbest = 1; }
+      else if (cost == best) nbest++;
+    }
+    cnt[OC_MODE0 + bmode]++;
+    if (bmode != lmode) cnt[OC_DISCOUNT]++;
+    if (nbest > 1) cnt[OC_COST_TIE]++;
+    t.modes |= (uint64_t)bmode << (4 * k);
+    /* residual, levels (the inter layout) and reconstruction before the next block predicts */
+    int x[16], w[16], z[16], r[16], nz = 0;
+    for (int i = 0; i < 4; i++)
+      for (int j = 0; j < 4; j++) x[i * 4 + j] = s4[i * 4 + j] - pred4_sample(&n, bmode, j, i);
+    fwd4(x, w);
+    for (int i = 0; i < 4; i++)
+      for (int j = 0; j < 4; j++) {
+        z[i * 4 + j] = quant1(w[i * 4 + j], MF[qp % 6][pos_class(i, j)], qbits, f);
+        nz |= z[i * 4 + j] != 0;
+      }
+    for (int s = 0; s < 16; s++) t.lv[16 * k + s] = (int16_t)z[ZZ[s]];
+    idct4(z, qp, 0, r);
+    for (int i = 0; i < 4; i++)
+      for (int j = 0; j < 4; j++)
+        cd->y[(by * 4 + i) * 16 + bx * 4 + j] = (uint8_t)clip255(pred4_sample(&n, bmode, j, i) + r[i * 4 + j]);
+    if (nz) cbp |= 1 << (k >> 2);
+  }
+  /* an 8x8 whose bit is clear has no non-zero level: its reconstruction is
+   * already the prediction, which is what the decoder makes of it */
+  t.cbp = cbp;
+  int cnz[16], cnzc[2][4];
+  cd->bits = put_i4_mb(NULL, &t, p_slice, mx, left, lnz, lnzc, cnz, cnzc);
+  cd->m = t;
 }
 
 /* The intra pass over one picture: all = 1 (an IDR picture) tries every
  * macroblock, all = 0 (a P picture) those the search left as I_PCM.  A row is
  * a chain: a macroblock predicts from, and takes its nC from, the macroblock
- * to its left as it is finally coded. */
-static void encode_intra(const uint8_t *src, uint8_t *rec, int cw, int ch, int qp, int all, or_mb *mbs) {
+ * to its left as it is finally coded.  i4: also try I_NxN, which the macroblock
+ * becomes when its bits are fewer than the Intra16x16 candidate's; the winner
+ * is coded when its bits are <= 3072, else the macroblock stays I_PCM (rec
+ * holds the source).  cbits (may be NULL): [my][mx][2], the bits of the
+ * Intra16x16 and the I_NxN candidate of every macroblock tried. */
+static void encode_intra(const uint8_t *src, uint8_t *rec, int cw, int ch, int qp, int all, int i4, int lambda16,
+                         or_mb *mbs, int32_t *cbits, int64_t *cnt) {
   int mbw = cw / 16, mbh = ch / 16;
   for (int my = 0; my < mbh; my++) {
     int lnz[4] = {-1, -1, -1, -1}, lnzc[2][2] = {{-1, -1}, {-1, -1}};
@@ -1002,7 +1355,31 @@ static void encode_intra(const uint8_t *src, uint8_t *rec, int cw, int ch, int q
           memcpy(rec + (int64_t)cw * ch + (int64_t)(my * 8 + j) * cw + mx * 16,
                  src + (int64_t)cw * ch + (int64_t)(my * 8 + j) * cw + mx * 16, 16);
       }
-      if (m->pcm && encode_intra_mb(src, rec, cw, ch, mx, my, qp, !all, lnz, (const int(*)[2])lnzc, m)) m->pcm = 0;
+      if (m->pcm) {
+        or_cand c16, c4;
+        const or_cand *win = &c16;
+        intra16_candidate(src, rec, cw, ch, mx, my, qp, !all, lnz, (const int(*)[2])lnzc, &c16);
+        if (i4) {
+          intra4_candidate(src, rec, cw, mx, my, qp, !all, lambda16, mx ? m - 1 : NULL, lnz, (const int(*)[2])lnzc,
+                           &c16, &c4, cnt);
+          if (c4.bits < c16.bits) win = &c4;  /* a tie stays Intra16x16 */
+          cnt[win == &c4 ? OC_I4_WON : OC_I16_WON]++;
+          if (c4.bits == c16.bits) cnt[OC_EQUAL_BITS]++;
+          if (win == &c4 && c4.bits > 3072) cnt[OC_I4_PCM]++;
+          if (cbits) {
+            cbits[2 * (my * mbw + mx)] = c16.bits;
+            cbits[2 * (my * mbw + mx) + 1] = c4.bits;
+          }
+        }
+        if (win->bits <= 3072) {
+          *m = win->m;
+          for (int j = 0; j < 16; j++) memcpy(rec + (int64_t)(my * 16 + j) * cw + mx * 16, win->y + j * 16, 16);
+          for (int j = 0; j < 8; j++)
+            for (int i = 0; i < 8; i++)
+              for (int pl = 0; pl < 2; pl++)
+                rec[(int64_t)cw * ch + (int64_t)(my * 8 + j) * cw + 2 * (mx * 8 + i) + pl] = win->c[pl][j * 8 + i];
+        }
+      }
       right_column_nz(m, lnz, lnzc);
     }
   }
@@ -1061,7 +1438,7 @@ static int blk_coded(const or_mb *m, int bx, int by) {
 /* bS (8.7.2.1) of a line between block (pbx, pby) of macroblock p and block
  * (qbx, qby) of macroblock q; one reference picture, frame macroblocks */
 static int edge_bs(const or_mb *p, int pbx, int pby, const or_mb *q, int qbx, int qby, int mb_edge) {
-  if (p->pcm || p->i16 || q->pcm || q->i16) return mb_edge ? 4 : 3;
+  if (p->pcm || p->i16 || p->i4 || q->pcm || q->i16 || q->i4) return mb_edge ? 4 : 3;
   if (blk_coded(p, pbx, pby) || blk_coded(q, qbx, qby)) return 2;
   return (abs(p->mvx - q->mvx) >= 4 || abs(p->mvy - q->mvy) >= 4) ? 1 : 0;
 }
@@ -1156,12 +1533,17 @@ static int write_picture(const uint8_t *src, int cw, int ch, const or_mb *mbs, i
         stats[0]++;
         continue;
       }
-      if (m->i16) {  /* Intra16x16 in an I or a P slice */
+      if (m->i16 || m->i4) {  /* Intra16x16 or I_NxN in an I or a P slice */
         if (!idr) {
           bw_ue(&b, skip);
           skip = 0;
         }
-        put_intra_mb(&b, m, !idr, lnz, (const int(*)[2])lnzc, cnz, cnzc);
+        if (m->i4) {
+          put_i4_mb(&b, m, !idr, mx, mx ? m - 1 : NULL, lnz, (const int(*)[2])lnzc, cnz, cnzc);
+          stats[9]++;
+        } else {
+          put_intra_mb(&b, m, !idr, lnz, (const int(*)[2])lnzc, cnz, cnzc);
+        }
         for (int i = 0; i < 4; i++) lnz[i] = cnz[i * 4 + 3];
         for (int pl = 0; pl < 2; pl++) {
           lnzc[pl][0] = cnzc[pl][1];
@@ -1246,12 +1628,15 @@ static int write_picture(const uint8_t *src, int cw, int ch, const or_mb *mbs, i
  * filter inside each macroblock row's slice.  stats has 8 entries: the four
  * above, then [Intra16x16 MBs, inter MBs with a fractional vector, of those
  * with a quarter-sample component, MBs with a filtered line]; recon is the
- * filtered reconstruction (what a decoder outputs).  All zero: or_transcode. */
-int or_transcode_ex(const uint8_t *frames, int64_t n, int W, int H, const float *scores, float thr,
-                    int idr_at_cuts, int sh, int R, int T, int keyint, int qp, int intra, int subpel, int deblock,
-                    int dalpha, int dbeta, uint8_t *out, int64_t cap, int64_t *sample_off,
-                    int64_t *sample_size, uint8_t *sync, uint8_t *recon, int64_t *stats,
-                    int64_t *out_len) {
+ * filtered reconstruction (what a decoder outputs).  All zero: or_transcode.
+ * transcode_core is the one body of all three entries: o holds the rules of
+ * or_transcode_ex2 (described there; all zero: none), stats has 10 entries,
+ * words / modes / cbits may be NULL, cnt receives the OC_N decision counters. */
+static int transcode_core(const uint8_t *frames, int64_t n, int W, int H, const float *scores, float thr,
+                          int idr_at_cuts, int sh, int R, int T, int keyint, int qp, int intra, int subpel, int deblock,
+                          int dalpha, int dbeta, const or_opts *o, uint8_t *out, int64_t cap, int64_t *sample_off,
+                          int64_t *sample_size, uint8_t *sync, uint8_t *recon, int64_t *stats, uint32_t *words,
+                          uint64_t *modes, int32_t *cbits, int64_t *cnt, int64_t *out_len) {
   if (n <= 0 || sh < 2 || (sh & 1) || R < 0 || R > 16 || keyint < 1 || qp > 51) return -1;
   if ((intra != 0 && intra != 1) || subpel < 0 || subpel > 2 || (deblock != 0 && deblock != 1)) return -1;
   if (dalpha < -6 || dalpha > 6 || dbeta < -6 || dbeta > 6 || (!deblock && (dalpha || dbeta))) return -1;
@@ -1263,12 +1648,14 @@ int or_transcode_ex(const uint8_t *frames, int64_t n, int W, int H, const float 
   rec[0] = (uint8_t *)malloc((size_t)fsz);
   rec[1] = (uint8_t *)malloc((size_t)fsz);
   or_mb *mbs = (or_mb *)calloc((size_t)mbw * mbh, sizeof(or_mb));
+  uint32_t *pw = (uint32_t *)calloc((size_t)mbw * mbh, sizeof(uint32_t));  /* the previous picture's final words */
   int64_t rcap = 64 + (int64_t)mbw * 420;
   uint8_t *rbsp = (uint8_t *)malloc((size_t)rcap);
-  int rc = (src && rec[0] && rec[1] && mbs && rbsp) ? 0 : -3;
+  int rc = (src && rec[0] && rec[1] && mbs && pw && rbsp) ? 0 : -3;
   int64_t pos = 0, last_idr = 0, n_idr = 0;
   int cur = 0;
-  for (int k = 0; k < 8; k++) stats[k] = 0;
+  for (int k = 0; k < 10; k++) stats[k] = 0;
+  for (int k = 0; k < OC_N; k++) cnt[k] = 0;
   for (int64_t f = 0; f < n && !rc; f++) {
     or_downscale_nv12(frames + f * dsz, W, H, src, sw, sh);
     int idr = f == 0 || (idr_at_cuts && scores[f] > thr) || f - last_idr >= keyint;
@@ -1278,20 +1665,23 @@ int or_transcode_ex(const uint8_t *frames, int64_t n, int W, int H, const float 
     sync[f] = (uint8_t)idr;
     if (idr) {
       if (intra) {
-        encode_intra(src, rec[cur], cw, ch, qp, 1, mbs);
+        encode_intra(src, rec[cur], cw, ch, qp, 1, o->intra4x4, o->lambda_i4, mbs,
+                     cbits ? cbits + 2 * f * mbw * mbh : NULL, cnt);
       } else {  /* every macroblock I_PCM: the source */
         memcpy(rec[cur], src, (size_t)fsz);
         for (int k = 0; k < mbw * mbh; k++) {
           mbs[k].pcm = 1;
-          mbs[k].i16 = mbs[k].cbp = mbs[k].mvx = mbs[k].mvy = 0;
+          mbs[k].i16 = mbs[k].i4 = mbs[k].cbp = mbs[k].mvx = mbs[k].mvy = 0;
         }
       }
       rc = write_picture(src, cw, ch, mbs, 1, (int)(n_idr & 1), 0, qp, intra, deblock, dalpha, dbeta, out, cap,
                          &pos, rbsp, rcap, stats);
       n_idr++;
     } else {
-      encode_p(src, rec[cur ^ 1], rec[cur], cw, ch, R, T, qp, subpel, mbs, stats);
-      if (intra) encode_intra(src, rec[cur], cw, ch, qp, 0, mbs);
+      encode_p(src, rec[cur ^ 1], rec[cur], cw, ch, R, T, qp, subpel, o, pw, j, mbs, stats, cnt);
+      if (intra)
+        encode_intra(src, rec[cur], cw, ch, qp, 0, o->intra4x4, o->lambda_i4, mbs,
+                     cbits ? cbits + 2 * f * mbw * mbh : NULL, cnt);
       rc = write_picture(src, cw, ch, mbs, 0, 0, j & 0xffff, qp, intra, deblock, dalpha, dbeta, out, cap, &pos,
                          rbsp, rcap, stats);
     }
@@ -1300,13 +1690,67 @@ int or_transcode_ex(const uint8_t *frames, int64_t n, int W, int H, const float 
      * edge (alpha' = 0): nothing passes, and the filter leaves it as it is */
     if (deblock && !rc) stats[7] += deblock_picture(rec[cur], cw, ch, mbs, qp, 2 * dalpha, 2 * dbeta);
     sample_size[f] = pos - sample_off[f];
+    for (int k = 0; k < mbw * mbh; k++) {  /* the final decisions, as the device reports them */
+      pw[k] = mb_word(&mbs[k]);
+      if (words) words[f * mbw * mbh + k] = pw[k];
+      if (modes) modes[f * mbw * mbh + k] = mbs[k].i4 ? mbs[k].modes : ~(uint64_t)0;
+    }
     if (recon) memcpy(recon + f * fsz, rec[cur], (size_t)fsz);
     cur ^= 1;
   }
   stats[3] = n_idr;
   *out_len = pos;
-  free(src); free(rec[0]); free(rec[1]); free(mbs); free(rbsp);
+  free(src); free(rec[0]); free(rec[1]); free(mbs); free(pw); free(rbsp);
   return rc;
+}
+
+int or_transcode_ex(const uint8_t *frames, int64_t n, int W, int H, const float *scores, float thr,
+                    int idr_at_cuts, int sh, int R, int T, int keyint, int qp, int intra, int subpel, int deblock,
+                    int dalpha, int dbeta, uint8_t *out, int64_t cap, int64_t *sample_off,
+                    int64_t *sample_size, uint8_t *sync, uint8_t *recon, int64_t *stats,
+                    int64_t *out_len) {
+  or_opts o = {0, 0, 0, 0, 0};
+  int64_t st[10], cnt[OC_N];
+  int rc = transcode_core(frames, n, W, H, scores, thr, idr_at_cuts, sh, R, T, keyint, qp, intra, subpel, deblock,
+                          dalpha, dbeta, &o, out, cap, sample_off, sample_size, sync, recon, st, NULL, NULL, NULL, cnt,
+                          out_len);
+  for (int k = 0; k < 8 && rc != -1; k++) stats[k] = st[k];
+  return rc;
+}
+
+/* or_transcode_ex2: or_transcode_ex with the rules merged since (DESIGN.md §11,
+ * "Rate-aware motion cost and early P_Skip" and "Intra4x4"): mvcost, early_skip
+ * (0 / 1; both need qp >= 1), mv_lambda16 (0: the formula's value for qp; 1 ..
+ * 4096 only with mvcost), intra4x4 (0 / 1; needs intra and qp >= 1).  stats has
+ * 10 entries: or_transcode_ex's eight (Intra16x16 MBs now counts I_NxN too),
+ * early_skip_mbs, intra4x4_mbs.  words / modes (may be NULL): the command word
+ * and the 64-bit mode word of every macroblock, [frame][my][mx], in the
+ * encodings of include/vtseg.h; cbits (may be NULL): [frame][my][mx][2], the
+ * bits of the Intra16x16 and the I_NxN candidate where intra4x4 tried both, else
+ * 0; counters: OC_N decision counters (the enum above).  All four zero:
+ * or_transcode_ex's bytes. */
+int or_transcode_ex2(const uint8_t *frames, int64_t n, int W, int H, const float *scores, float thr,
+                     int idr_at_cuts, int sh, int R, int T, int keyint, int qp, int intra, int subpel, int deblock,
+                     int dalpha, int dbeta, int mvcost, int early_skip, int mv_lambda16, int intra4x4, uint8_t *out,
+                     int64_t cap, int64_t *sample_off, int64_t *sample_size, uint8_t *sync, uint8_t *recon,
+                     int64_t *stats, uint32_t *words, uint64_t *modes, int32_t *cbits, int64_t *counters,
+                     int64_t *out_len) {
+  if ((mvcost != 0 && mvcost != 1) || (early_skip != 0 && early_skip != 1) || (intra4x4 != 0 && intra4x4 != 1)) return -1;
+  if (mv_lambda16 < 0 || mv_lambda16 > 4096 || (mv_lambda16 && !mvcost)) return -1;
+  if ((mvcost || early_skip || intra4x4) && (qp < 1 || qp > 51)) return -1;
+  if (intra4x4 && !intra) return -1;
+  or_opts o = {mvcost, early_skip, intra4x4, 0, 0};
+  if (qp >= 1 && qp <= 51) {
+    o.lambda_mv = mv_lambda16 > 0 ? mv_lambda16 : lambda16_formula(qp);
+    o.lambda_i4 = lambda16_formula(qp);
+  }
+  if (n > 0 && cbits) {
+    int sw = or_small_width(W, H, sh), mbw = (sw + 15) / 16, mbh = (sh + 15) / 16;
+    memset(cbits, 0, (size_t)n * mbw * mbh * 2 * sizeof(int32_t));
+  }
+  return transcode_core(frames, n, W, H, scores, thr, idr_at_cuts, sh, R, T, keyint, qp, intra, subpel, deblock,
+                        dalpha, dbeta, &o, out, cap, sample_off, sample_size, sync, recon, stats, words, modes, cbits,
+                        counters, out_len);
 }
 
 int or_transcode(const uint8_t *frames, int64_t n, int W, int H, const float *scores, float thr,

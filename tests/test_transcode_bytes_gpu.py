@@ -23,7 +23,7 @@ import numpy as np
 import pytest
 
 import oracle
-from test_transcode_oracle import crafted_frames
+from test_transcode_oracle import crafted_frames, diagonal_frames, noisy_frames
 from test_transcode_subpel_gpu import REAL, SOURCES as SUBPEL_SOURCES, SYNTH, _require_gpu
 from vtseg import scene
 
@@ -39,6 +39,10 @@ SOURCES.update({
     # kind; a constant picture, where every decision is a tie
     "crafted": crafted_frames,
     "flat": lambda: np.full((6, 96, 96), 128, np.uint8),
+    # sources of tests/test_transcode_bytes_rate_intra4_gpu.py and test_transcode_rate_gpu.py: noise inside
+    # the quantiser's dead zone (early P_Skip); edges at many angles, ramps, constants and noise (Intra_4x4)
+    "noisy": noisy_frames,
+    "diag": diagonal_frames,
     # display widths that are no multiple of 16 (crop_r != 0), what every portrait upload
     # gives: 144x256 -> 72x128 coded 80x128; 176x144 -> 88x72 coded 96x80 (both crops)
     "portrait": dict(width=144, height=256, n_frames=20),

@@ -290,6 +290,61 @@ def crafted_frames(F=12, W=96, H=64, seed=11):
     return np.maximum(fr, 1)
 
 
+def noisy_frames(F=8, W=96, H=64, seed=5):
+    """One textured picture plus seeded noise in {-1, 0, +1}, luma and chroma,
+    samples kept in 1..254 (display-size NV12)."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H * 3 // 2, 0:W]
+    # smooth enough that a quarter-sample vector, whose prediction averages the reference's noise
+    # away, beats the centre by a few units of SAD in some macroblocks (the CPU oracle: 134 of 168
+    # P macroblocks stay P_Skip with subpel = 2, all 168 with subpel = 0)
+    base = np.clip(128 + 60 * np.sin(xx / 11.0) * np.cos(yy / 9.0), 2, 253).astype(np.int16)
+    fr = np.stack([base + rng.integers(-1, 2, base.shape) for _ in range(F)])
+    assert fr.min() >= 1 and fr.max() <= 254
+    return fr.astype(np.uint8)
+
+
+def diagonal_frames(F=6, W=96, H=64, seed=3):
+    """Display-size NV12 frames (samples >= 1) for the Intra_4x4 decisions:
+    per macroblock a seeded kind: hard edges at one of eight angles (the
+    directional modes 3 .. 8 predict them), a smooth ramp (DC and the predicted
+    mode's discount), a constant (every mode predicts the same samples: cost
+    ties, and I_NxN against Intra16x16 on few bits) or noise (nothing predicts
+    it: at qp 1 both candidates pass 3072 bits).  The whole pattern moves by
+    (3, 1) samples a frame, so the P pictures search, and every third frame has
+    two macroblocks of fresh noise that the search misses (intra in a P slice)."""
+    rng = np.random.default_rng(seed)
+    mbw, mbh, pad = W // 16, H // 16, 32
+    kinds = rng.integers(0, 12, (mbh + 4, mbw + 4))
+    ang = rng.uniform(0, np.pi, kinds.shape)
+    lo, hi = rng.integers(20, 110, kinds.shape), rng.integers(140, 250, kinds.shape)
+    yy, xx = np.mgrid[0:H + 2 * pad, 0:W + 2 * pad]
+    big = np.zeros(yy.shape, np.int64)
+    for my in range(kinds.shape[0]):
+        for mx in range(kinds.shape[1]):
+            ys, xs = slice(my * 16, my * 16 + 16), slice(mx * 16, mx * 16 + 16)
+            y, x, k = yy[ys, xs], xx[ys, xs], kinds[my, mx]
+            if k < 7:      # stripes 5 samples wide across the direction ang
+                t = np.floor((x * np.cos(ang[my, mx]) + y * np.sin(ang[my, mx])) / 5.0).astype(np.int64)
+                big[ys, xs] = np.where(t & 1, hi[my, mx], lo[my, mx])
+            elif k < 9:
+                big[ys, xs] = lo[my, mx] + (x % 16) * 3 + (y % 16) * 2
+            elif k < 11:
+                big[ys, xs] = lo[my, mx]
+            else:
+                big[ys, xs] = rng.integers(1, 256, (16, 16))
+    fr = np.zeros((F, H * 3 // 2, W), np.uint8)
+    for f in range(F):
+        oy, ox = pad // 2 + f, pad // 2 + 3 * f
+        fr[f, :H] = big[oy:oy + H, ox:ox + W]
+        c = big[oy:oy + H:2, ox:ox + W:2]
+        fr[f, H:, 0::2], fr[f, H:, 1::2] = 128 + (c - 128) // 4, 128 - (c - 128) // 8
+        if f % 3 == 2:
+            for mx in (1, 4):
+                fr[f, 16:32, mx * 16:mx * 16 + 16] = rng.integers(1, 256, (16, 16))
+    return np.maximum(fr, 1)
+
+
 @pytest.mark.parametrize("qp,kw", [(4, dict(subpel=0, deblock=0)),
                                    (12, dict(subpel=2, deblock=1, deblock_offsets=(6, 6))),
                                    (4, dict(subpel=2, deblock=1, deblock_offsets=(6, 6)))])
@@ -388,6 +443,213 @@ def test_oracle_idr_at_keyint_and_optionally_cuts(clip, at_cuts):
         last = f if is_idr else last
         assert bool(r["sync"][f]) == is_idr
     assert len(idr) == r["n_idr"]
+
+
+# ------- the rules of or_transcode_ex2: mvcost, early_skip, intra4x4
+# As above, the oracle is checked before it judges the device
+# (tests/test_transcode_bytes_rate_intra4_gpu.py): (a) its output decodes, through
+# h264_full_oracle.c's own 8.3.1.2 and CAVLC, to its own reconstruction; (b) the
+# GPU cases make every rule decide; (c) it agrees with the product's CPU harness,
+# a restatement by another hand; (d) with the new keywords at their defaults it
+# writes or_transcode_ex's bytes.
+
+PCM_WORD, I4_NONE = 0x80008000, np.uint64(0xFFFFFFFFFFFFFFFF)
+NEW_RULES = {"mv": dict(mvcost=True), "es": dict(early_skip=True), "both": dict(mvcost=True, early_skip=True),
+             "i4": dict(intra=True, intra4x4=True),
+             "every": dict(intra=True, intra4x4=True, mvcost=True, early_skip=True)}
+
+
+def _closed_loop_ex2(tmp_path, frames, W, H, sc, **kw):
+    r = oracle.transcode(frames, W, H, sc, want_recon=True, want_words=True, **kw)
+    cw, ch, sw, sh = r["coded_width"], r["coded_height"], r["width"], r["height"]
+    rec = r["recon"]
+    dec = _decode_full_samples(tmp_path, r)
+    want = np.concatenate([rec[:, :sh, :sw], rec[:, ch:ch + sh // 2, :sw]], 1)
+    bad = [i for i in range(len(want)) if not np.array_equal(dec[i], want[i])]
+    assert bad == [], f"the oracle decoder differs from the encoder's reconstruction at frames {bad[:8]}"
+    # the words say what the counts say
+    cmd, modes = r["commands"], r["intra4_modes"]
+    assert cmd.shape == modes.shape == (len(frames), ch // 16, cw // 16)
+    intra = (cmd & 0xffff8000) == 0x80000000
+    i4 = (cmd & 0xffffc000) == 0x80004000
+    assert int((cmd == PCM_WORD).sum()) == r["pcm_mbs"] and int(intra.sum()) == r["intra_mbs"]
+    assert int(i4.sum()) == r["intra4x4_mbs"] and np.array_equal(modes != I4_NONE, i4)
+    assert int((cmd == 0).sum()) >= r["skip_mbs"] >= r["early_skip_mbs"] == r["counters"]["early_skip_hits"]
+    assert r["pcm_mbs"] + r["inter_mbs"] + r["skip_mbs"] + r["intra_mbs"] == cmd.size
+    assert r["counters"]["i4_won_mbs"] - r["counters"]["i4_pcm_mbs"] == r["intra4x4_mbs"]
+    assert sum(r["counters"][f"mode{m}"] for m in range(9)) == \
+        16 * (r["counters"]["i4_won_mbs"] + r["counters"]["i16_won_mbs"])
+    return r
+
+
+@pytest.mark.parametrize("qp", [1, 28, 51])
+@pytest.mark.parametrize("deblock", [0, 1])
+@pytest.mark.parametrize("subpel", [0, 2])
+@pytest.mark.parametrize("rules", list(NEW_RULES))
+def test_oracle_rate_and_intra4_closed_loop(tmp_path, clip, rules, subpel, deblock, qp):
+    frames, sc, _ = clip
+    kw = NEW_RULES[rules]
+    r = _closed_loop_ex2(tmp_path, frames[:24], 320, 192, sc[:24], out_height=96, subpel=subpel, deblock=bool(deblock),
+                         qp=qp, **kw)
+    assert (r["early_skip_mbs"] > 0) == bool(kw.get("early_skip"))
+    if kw.get("intra4x4") and qp < 51:     # at qp 51 almost nothing is coded and Intra16x16's shorter header wins
+        assert r["intra4x4_mbs"] > 0
+    if not kw.get("intra4x4"):
+        assert r["intra4x4_mbs"] == 0 and sum(r["counters"][f"mode{m}"] for m in range(9)) == 0
+    if not kw.get("mvcost"):
+        assert r["counters"]["cost_decided_vectors"] == 0 and r["counters"]["inter_predictor_mbs"] == 0
+
+
+@pytest.mark.parametrize("qp", [1, 28, 51])
+@pytest.mark.parametrize("name,W,H,h,R,coded", [("tiny", 64, 48, 24, 4, (32, 32)), ("column", 48, 144, 48, 4, (16, 48)),
+                                                ("qcif", 176, 144, 72, 8, (96, 80))])
+def test_oracle_rate_and_intra4_edge_shapes(tmp_path, name, W, H, h, R, coded, qp):
+    """Everything on over 2 x 2 macroblocks, a one-macroblock-wide column
+    (never a left macroblock: block column 0 has the modes 0, 2, 3, 7 only)
+    and a width that is cropped."""
+    p = tmp_path / f"{name}.mp4"
+    scene.synth_write(p, width=W, height=H, n_frames=20, cut_min_s=0.7, cut_max_s=1.5, gop_max_s=0.5, max_motion=6)
+    frames, _ = oracle.decode_full(p)
+    sc = oracle.score_frames(frames.reshape(-1), frames[0].size, 20, W, H, W, H, 4, want_rgb=False)["score"]
+    r = _closed_loop_ex2(tmp_path, frames, W, H, sc, out_height=h, search_range=R, subpel=2, deblock=True, qp=qp,
+                         **NEW_RULES["every"])
+    assert (r["coded_width"], r["coded_height"]) == coded
+    if name == "column":
+        for w in r["intra4_modes"][r["intra4_modes"] != I4_NONE]:
+            assert {(int(w) >> (4 * k)) & 15 for k in (0, 2, 8, 10)} <= {0, 2, 3, 7}
+
+
+@pytest.mark.parametrize("qp", [1, 28, 51])
+def test_oracle_i_nxn_in_p_slices(tmp_path, clip, qp):
+    """max_mb_sad < 0 leaves every P macroblock to the intra pass: I_NxN with
+    mb_type 5 beside Intra16x16 in P slices."""
+    frames, sc, _ = clip
+    r = _closed_loop_ex2(tmp_path, frames[:12], 320, 192, sc[:12], out_height=96, max_mb_sad=-1, qp=qp, intra=True,
+                         intra4x4=True)
+    assert r["intra_mbs"] + r["pcm_mbs"] == 12 * 60
+    if qp < 51:     # at qp 51 almost nothing is coded and Intra16x16's shorter header wins
+        assert ((r["commands"][1:] & 0xffffc000) == 0x80004000).any()
+
+
+def test_oracle_ex2_defaults_are_or_transcode_ex(clip):
+    """Every new keyword at its default: or_transcode_ex's bytes, counts and
+    reconstruction, also when the call goes through the new entry (want_words)."""
+    frames, sc, _ = clip
+    for kw in (dict(), dict(intra=True, subpel=2, deblock=True, deblock_offsets=(2, -2)), dict(qp=0, subpel=1)):
+        old = oracle.transcode(frames[:30], 320, 192, sc[:30], out_height=96, want_recon=True, keyint=16, **kw)
+        new = oracle.transcode(frames[:30], 320, 192, sc[:30], out_height=96, want_recon=True, keyint=16,
+                               want_words=True, **kw)
+        assert "counters" not in old and new["early_skip_mbs"] == 0 and new["intra4x4_mbs"] == 0
+        assert new["samples"] == old["samples"] and np.array_equal(new["recon"], old["recon"])
+        assert {k: new[k] for k in old if k.endswith("_mbs") or k == "n_idr"} == \
+            {k: old[k] for k in old if k.endswith("_mbs") or k == "n_idr"}
+        assert (new["intra4_modes"] == I4_NONE).all() and not any(new["counters"].values())
+        assert (new["commands"][0] == PCM_WORD).all() or kw.get("intra")
+    with pytest.raises(RuntimeError):      # the rules need residual coding; intra4x4 needs intra
+        oracle.transcode(frames[:2], 320, 192, sc[:2], out_height=96, qp=0, early_skip=True)
+    with pytest.raises(RuntimeError):
+        oracle.transcode(frames[:2], 320, 192, sc[:2], out_height=96, intra4x4=True)
+    with pytest.raises(RuntimeError):
+        oracle.transcode(frames[:2], 320, 192, sc[:2], out_height=96, mv_lambda16=400)
+
+
+def test_oracle_vector_cost_keeps_a_true_pan():
+    """Noise that pans by (3, 1) samples a frame: only the true vector predicts
+    it (16 SAD of any other candidate is some 350 000), so even the largest
+    mv_lambda16, 4096, whose 16 bits for (-12, -4) against a zero guess cost
+    65 536, leaves the vector alone; the words hold it in quarter samples,
+    two's complement halves (include/vtseg.h)."""
+    rng = np.random.default_rng(2)
+    big = rng.integers(1, 256, (64 + 16, 96 + 32), dtype=np.uint8)
+    fr = np.zeros((4, 96, 96), np.uint8)
+    for f in range(4):
+        fr[f, :64] = big[8 - f:72 - f, 16 - 3 * f:112 - 3 * f]
+        fr[f, 64:] = 128
+    r = oracle.transcode(fr, 96, 64, np.zeros(4, np.float32), out_height=64, qp=28, mvcost=True, mv_lambda16=4096,
+                         want_words=True)
+    inner = r["commands"][1:, 1:-1, 1:-1]
+    assert (inner == ((-4 & 0xffff) << 16 | (-12 & 0xffff))).all()     # the content came from (x - 3, y - 1)
+    assert r["counters"]["inter_predictor_mbs"] > 0                    # pictures 2 and 3 guess that vector
+
+
+def _ei4h(tmp_path_factory):
+    import ctypes as C
+    import subprocess
+    from test_enc_intra4_host import FLAGS, NATIVE, SRCS
+    so = tmp_path_factory.mktemp("ei4h_oracle") / "libencintra4host.so"
+    subprocess.run(["g++", "-Og", "-fPIC", "-shared", *FLAGS, str(NATIVE / "enc_intra4_host.cpp"),
+                    *map(str, SRCS), "-o", str(so)], check=True)
+    L = C.CDLL(str(so))
+    L.ei4h_encode.argtypes = [C.c_int] * 4 + [C.c_void_p] * 8
+    L.ei4h_encode.restype = None
+    return L
+
+
+@pytest.fixture(scope="module")
+def ei4h(tmp_path_factory):
+    return _ei4h(tmp_path_factory)
+
+
+@pytest.mark.parametrize("qp", [1, 28, 51])
+@pytest.mark.parametrize("mbw", [1, 2, 10])
+def test_oracle_agrees_with_the_encoder_harness(ei4h, mbw, qp):
+    """Two restatements of the Intra4x4 rules by different hands: the product's
+    CPU harness (tests/native/enc_intra4_host.cpp over csrc/enc_intra4.h, every
+    macroblock at kind 5, the encoder's own choice) and the oracle, on one IDR
+    picture.  out_height = the source's height makes the downscale the identity
+    on samples >= 1.  Equal command words, mode words, bit counts of both
+    candidates and reconstruction."""
+    mbh = 3
+    W, H = 16 * mbw, 16 * mbh
+    fr = np.ascontiguousarray(diagonal_frames(F=1, W=max(W, 32), H=H, seed=40 + mbw)[:, :, :W])
+    assert np.array_equal(oracle.downscale_nv12(fr[0], W, H, H), fr[0])
+    r = oracle.transcode(fr, W, H, np.zeros(1, np.float32), out_height=H, qp=qp, intra=True, intra4x4=True,
+                         want_recon=True, want_words=True)
+    assert (r["coded_width"], r["coded_height"]) == (W, H)
+    n = mbw * mbh
+    kind = np.full(n, 5, np.uint8)
+    cmd, cbp, coef = np.zeros(n, np.uint32), np.zeros(n, np.uint8), np.zeros(n * 384, np.int16)
+    modes, bits, rec = np.zeros(n, np.uint64), np.zeros(2 * n, np.int32), np.zeros_like(fr[0])
+    src = np.ascontiguousarray(fr[0])
+    ei4h.ei4h_encode(mbw, mbh, 1, qp, src.ctypes.data, kind.ctypes.data, cmd.ctypes.data, cbp.ctypes.data,
+                     coef.ctypes.data, modes.ctypes.data, bits.ctypes.data, rec.ctypes.data)
+    c = r["counters"]
+    print(f"{mbw} x {mbh} macroblocks at qp {qp}: I_NxN {r['intra4x4_mbs']}, Intra16x16 "
+          f"{r['intra_mbs'] - r['intra4x4_mbs']}, I_PCM {r['pcm_mbs']}; modes {[c[f'mode{m}'] for m in range(9)]}")
+    want_cmd, want_modes = r["commands"][0].reshape(-1), r["intra4_modes"][0].reshape(-1)
+    for i in range(n):
+        where = f"macroblock (mx {i % mbw}, my {i // mbw})"
+        assert int(cmd[i]) == int(want_cmd[i]), f"{where}: harness {int(cmd[i]):#x}, oracle {int(want_cmd[i]):#x}"
+        assert int(modes[i]) == int(want_modes[i]), f"{where}: harness {int(modes[i]):#x}, oracle {int(want_modes[i]):#x}"
+    assert np.array_equal(bits.reshape(mbh, mbw, 2), r["candidate_bits"][0])
+    assert np.array_equal(rec, r["recon"][0])
+
+
+def test_gpu_cases_exercise_every_decision():
+    """A condition on the inputs of tests/test_transcode_bytes_rate_intra4_gpu.py,
+    not a measurement: over its (source, settings) pairs the oracle must have
+    chosen every Intra4x4PredMode, let the predicted mode's discount decide a
+    block, met a cost tie, decided a macroblock each way, met equal bits (won by
+    Intra16x16), sent an I_NxN winner back to I_PCM over 3072 bits, let the
+    vector cost overrule the least SAD, hit the early-skip probe, and used a
+    non-zero predictor guess taken from an inter word.  A case that a defect of
+    the device could not fail for lack of such input is no pin."""
+    import tempfile
+    from pathlib import Path
+
+    from test_transcode_bytes_gpu import _decoded
+    from test_transcode_bytes_rate_intra4_gpu import CASES, oracle_side
+    with tempfile.TemporaryDirectory() as d:
+        work = {"dir": Path(d), "src": {}, "dec": {}, "ref": {}}
+        total = dict.fromkeys(oracle.DECISION_COUNTERS, 0)
+        print("case | " + " ".join(oracle.DECISION_COUNTERS))
+        for name, (sname, tk) in CASES.items():
+            c = oracle_side(_decoded(work, sname), tk)["counters"]
+            print(f"{name} | " + " ".join(str(c[k]) for k in oracle.DECISION_COUNTERS))
+            for k in total:
+                total[k] += c[k]
+    print("all | " + " ".join(str(total[k]) for k in oracle.DECISION_COUNTERS))
+    assert [k for k, v in total.items() if v == 0] == []
 
 
 # ------------------------------------------------ drop-in decision flow

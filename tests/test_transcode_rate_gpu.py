@@ -32,22 +32,7 @@ PCM = 0x80008000
 MODES = {"mv": dict(mvcost=True), "es": dict(early_skip=True), "both": dict(mvcost=True, early_skip=True)}
 
 
-def _noisy_frames(F=8, W=96, H=64, seed=5):
-    """One textured picture plus seeded noise in {-1, 0, +1}, luma and chroma,
-    samples kept in 1..254 (display-size NV12)."""
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:H * 3 // 2, 0:W]
-    # smooth enough that a quarter-sample vector, whose prediction averages the reference's noise
-    # away, beats the centre by a few units of SAD in some macroblocks (the CPU oracle: 134 of 168
-    # P macroblocks stay P_Skip with subpel = 2, all 168 with subpel = 0)
-    base = np.clip(128 + 60 * np.sin(xx / 11.0) * np.cos(yy / 9.0), 2, 253).astype(np.int16)
-    fr = np.stack([base + rng.integers(-1, 2, base.shape) for _ in range(F)])
-    assert fr.min() >= 1 and fr.max() <= 254
-    return fr.astype(np.uint8)
-
-
-SOURCES = dict(BYTES_SOURCES)      # s70, s40, tiny, column, content, real, crafted ...
-SOURCES["noisy"] = _noisy_frames
+SOURCES = dict(BYTES_SOURCES)      # s70, s40, tiny, column, content, real, crafted, noisy ...
 
 ALL_ON = dict(intra=True, subpel=2, deblock=True)
 # name -> (source, transcode kwargs)
