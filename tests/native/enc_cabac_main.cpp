@@ -4,7 +4,9 @@
 // the runtimes).  Seeded bin sequences through the engine, the context
 // tables at every QP, and macroblock rows of every kind through both writers,
 // into exactly sized buffers; a slot one byte short must report the overflow
-// and store nothing past it.  TEST INFRASTRUCTURE.
+// and store nothing past it; CAVLC rows through the byte sink and the kernel's
+// dword sink into exactly sized buffers, generous and 1 .. 5 bytes short.
+// TEST INFRASTRUCTURE.
 #include <cstdio>
 #include <cstdlib>
 
@@ -95,6 +97,29 @@ int main() {
         const int64_t len = ech_pictures(mbw, mbh, npic, 20 + r.below(20), round & 1, cabac, cmd.data(), cbp.data(),
                                          coef.data(), pcm.data(), out.data(), static_cast<int64_t>(out.size()), sizes);
         bad += check(len > 0 && sizes[0] + sizes[1] + sizes[2] == len, "ech_pictures failed");
+      }
+      // both sinks over an I and a P row (zeros among the samples: emulation prevention), into buffers of
+      // exactly `cap` bytes and cap / 4 words: a generous cap, then 1 .. 5 bytes short of the slice
+      for (size_t i = 0; i < pcm.size(); i += 1 + static_cast<size_t>(r.below(3))) pcm[i] = 0;
+      for (int p = 0; p < 2; ++p) {
+        const size_t at = static_cast<size_t>(p) * mbh * mbw;
+        int64_t full[4] = {0, 0, 0, 0};
+        for (int shortby = 0; shortby <= 5; ++shortby) {
+          const int64_t cap = shortby ? full[0] - shortby : static_cast<int64_t>(mbw) * ecab::kMbBytes + 64;
+          std::vector<uint8_t> bytes(static_cast<size_t>(cap));
+          std::vector<uint32_t> words(static_cast<size_t>(cap / 4));
+          int64_t res[4];
+          ech_sinks(p == 0, mbw, 20 + round, round & 1, cmd.data() + at, cbp.data() + at, coef.data() + at * kCoefPerMb,
+                    pcm.data() + at * 384, cap, bytes.data(), words.data(), res);
+          if (!shortby) {
+            std::memcpy(full, res, sizeof full);
+            bad += check(!res[1] && !res[3] && res[0] == res[2] && res[0] > 0 &&
+                             !std::memcmp(bytes.data(), words.data(), static_cast<size_t>(res[0])),
+                         "the two sinks differ");
+          } else {
+            bad += check(res[1] && res[3] && res[0] == full[0] && res[2] == full[0], "a short sink did not report the overflow");
+          }
+        }
       }
     }
   if (bad) return 1;

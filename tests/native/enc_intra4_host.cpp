@@ -7,316 +7,35 @@
 //                   I_NxN, P_Skip, coded inter at vector (0, 0), or the
 //                   encoder's own choice between the intra kinds) coded
 //                   serially with the headers' arithmetic: command words,
-//                   patterns, levels, mode words, the two candidates' bits and
-//                   the reconstruction;
-//   ei4h_write:     those pictures as slices, one per macroblock row: CAVLC by
-//                   the writer below, which restates enc_write's syntax, or
-//                   CABAC through enc_cabac.h, directly or through BinRing.
+//                   patterns, levels, mode words, the two candidates' bits (on
+//                   enc_cavlc.h's counting sink) and the reconstruction;
+//   ei4h_write:     those pictures as slices, one per macroblock row: CAVLC
+//                   through enc_cavlc.h, the code enc_write calls, or CABAC
+//                   through enc_cabac.h, directly or through BinRing
+//                   (enc_rows.h walks both);
+//   ei4h_count:     a slice's macroblocks on enc_cavlc.h's counting sink
+//                   against the bits the byte sink receives.
 // TEST INFRASTRUCTURE (tests/test_enc_intra4_host.py; enc_intra4_main.cpp runs
 // the same functions under the sanitizers).
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
-#include "enc_cabac.h"
 #include "enc_intra4.h"
 #include "enc_residual.h"
+#include "enc_rows.h"
 #include "h264.h"
 #include "h264_tables.h"
 
 using namespace vts;
-namespace ecab = vts::full::ecab;
-namespace edb = vts::full::edb;
-namespace ei4 = vts::full::ei4;
 namespace eres = vts::full::eres;
 
 namespace {
-constexpr int kCoefPerMb = 384;  // transcode.hip's level layout
 constexpr int kPcmBits = 3072;
-const uint8_t kCtLen[4][17][4] = VTS_CT_LEN_DATA;
-const uint8_t kCtCode[4][17][4] = VTS_CT_CODE_DATA;
-const uint8_t kTzLen[15][16] = VTS_TZ_LEN_DATA;
-const uint8_t kTzCode[15][16] = VTS_TZ_CODE_DATA;
-const uint8_t kTzcLen[3][4] = VTS_TZC_LEN_DATA;
-const uint8_t kTzcCode[3][4] = VTS_TZC_CODE_DATA;
-const uint8_t kRbLen[7][15] = VTS_RB_LEN_DATA;
-const uint8_t kRbCode[7][15] = VTS_RB_CODE_DATA;
-const uint8_t kCbpInterTab[48] = VTS_CBPP_DATA;
-const uint8_t kCbpIntraTab[48] = VTS_CBPI_DATA;
 const uint8_t kQpc[52] = VTS_QPC_DATA;
 const uint8_t kZz[16] = VTS_ZZ_DATA;
-
-using Sink = ecab::ByteSink;
-// RBSP bits counted, nothing stored
-struct BitCount {
-  int64_t n = 0;
-  void bits(int k, uint32_t) { n += k; }
-  void ue(uint32_t v) { n += 2 * (31 - __builtin_clz(v + 1)) + 1; }
-  void se(int v) { ue(v > 0 ? static_cast<uint32_t>(2 * v - 1) : static_cast<uint32_t>(-2 * v)); }
-};
-
-// residual_block_cavlc (7.3.5.3.2, 9.2) of lv[0 .. maxNum) in scan order; returns total_coeff
-template <class S>
-int cavlc_block(S &o, const int16_t *lv, int maxNum, int nC) {
-  int tc = 0, t1 = 0, top = -1;
-  bool open = true;
-  for (int i = maxNum - 1; i >= 0; --i) {
-    const int v = lv[i];
-    if (!v) continue;
-    if (top < 0) top = i;
-    ++tc;
-    if (open && t1 < 3 && (v == 1 || v == -1)) ++t1;
-    else open = false;
-  }
-  if (nC >= 8) {
-    o.bits(6, tc == 0 ? 3u : static_cast<uint32_t>(((tc - 1) << 2) | t1));
-  } else {
-    const int col = nC == -1 ? 3 : (nC < 2 ? 0 : (nC < 4 ? 1 : 2));
-    o.bits(kCtLen[col][tc][t1], kCtCode[col][tc][t1]);
-  }
-  if (!tc) return 0;
-  int k = 0, sl = (tc > 10 && t1 < 3) ? 1 : 0;
-  for (int i = maxNum - 1; i >= 0; --i) {
-    const int v = lv[i];
-    if (!v) continue;
-    if (k < t1) {
-      o.bits(1, v < 0 ? 1u : 0u);
-    } else {
-      int code = v > 0 ? 2 * v - 2 : -2 * v - 1;
-      if (k == t1 && t1 < 3) code -= 2;
-      int prefix, suffix = 0, ssize = 0;
-      if (sl == 0) {
-        if (code < 14) prefix = code;
-        else if (code < 30) { prefix = 14; suffix = code - 14; ssize = 4; }
-        else { prefix = 15; suffix = code - 30; ssize = 12; }
-      } else if (code < (15 << sl)) {
-        prefix = code >> sl;
-        suffix = code & ((1 << sl) - 1);
-        ssize = sl;
-      } else {
-        prefix = 15;
-        suffix = code - (15 << sl);
-        ssize = 12;
-      }
-      o.bits(prefix + 1, 1u);
-      if (ssize) o.bits(ssize, static_cast<uint32_t>(suffix));
-      if (sl == 0) sl = 1;
-      if ((v < 0 ? -v : v) > (3 << (sl - 1)) && sl < 6) ++sl;
-    }
-    ++k;
-  }
-  int zl = top + 1 - tc;
-  if (tc < maxNum) o.bits(maxNum == 4 ? kTzcLen[tc - 1][zl] : kTzLen[tc - 1][zl],
-                          maxNum == 4 ? kTzcCode[tc - 1][zl] : kTzCode[tc - 1][zl]);
-  int prev = -1;
-  for (int i = maxNum - 1; i >= 0; --i) {
-    if (!lv[i]) continue;
-    if (prev >= 0 && zl > 0) {
-      const int run = prev - i - 1, row = (zl < 7 ? zl : 7) - 1;
-      o.bits(kRbLen[row][run], kRbCode[row][run]);
-      zl -= run;
-    }
-    prev = i;
-  }
-  return tc;
-}
-int nc_of(int na, int nb) { return (na >= 0 && nb >= 0) ? (na + nb + 1) >> 1 : (na >= 0 ? na : (nb >= 0 ? nb : 0)); }
-
-// What a slice's CAVLC writer carries from macroblock to macroblock: total_coeff of the left macroblock's
-// right column (-1: none), and the left macroblock's mode word when it is I_NxN
-struct Row {
-  int l[4], lc[2][2], c[16], cc[2][4];
-  uint64_t left_modes;
-  bool has_left;
-  void start() {
-    for (int i = 0; i < 4; ++i) l[i] = -1;
-    lc[0][0] = lc[0][1] = lc[1][0] = lc[1][1] = -1;
-    left_modes = ei4::kNoModes;
-    has_left = false;
-  }
-  void all(int v) {
-    for (int i = 0; i < 4; ++i) l[i] = v;
-    lc[0][0] = lc[0][1] = lc[1][0] = lc[1][1] = v;
-  }
-  void clear() {
-    std::memset(c, 0, sizeof c);
-    std::memset(cc, 0, sizeof cc);
-  }
-  void shift() {
-    for (int i = 0; i < 4; ++i) l[i] = c[i * 4 + 3];
-    for (int pl = 0; pl < 2; ++pl) {
-      lc[pl][0] = cc[pl][1];
-      lc[pl][1] = cc[pl][3];
-    }
-  }
-};
-template <class S>
-void cavlc_chroma(S &o, const int16_t *cp, int cc, Row &z) {
-  if (cc)
-    for (int pl = 0; pl < 2; ++pl) cavlc_block(o, cp + 256 + 4 * pl, 4, -1);
-  if (cc == 2)
-    for (int pl = 0; pl < 2; ++pl)
-      for (int k = 0; k < 4; ++k) {
-        const int bx = k & 1, by = k >> 1;
-        const int na = bx ? z.cc[pl][by * 2] : z.lc[pl][by], nb = by ? z.cc[pl][bx] : -1;
-        z.cc[pl][k] = cavlc_block(o, cp + 264 + 60 * pl + 15 * k, 15, nc_of(na, nb));
-      }
-}
-template <class S>
-void cavlc_luma(S &o, const int16_t *lv, int n, int k, Row &z) {
-  const int r = edb::raster_of_blk(k), bx = r & 3, by = r >> 2;
-  const int na = bx ? z.c[r - 1] : z.l[by], nb = by ? z.c[r - 4] : -1;
-  z.c[r] = cavlc_block(o, lv, n, nc_of(na, nb));
-}
-
-// macroblock_layer() (7.3.5) of an intra macroblock that is not I_PCM, from mb_type on, as enc_write writes
-// it; z is left as the macroblock to the right finds it
-template <class S>
-void cavlc_intra_mb(S &o, bool idr, uint32_t c, uint64_t modes, const int16_t *cp, Row &z) {
-  const int cbp = static_cast<int>(c >> 4) & 63;
-  z.clear();
-  if (ei4::is_i4_cmd(c)) {  // I_NxN
-    o.ue(idr ? 0 : 5);
-    for (int k = 0; k < 16; ++k) {
-      const int m = ei4::mode_at(modes, k), pm = ei4::pred_mode_of(k, modes, z.has_left, z.left_modes);
-      if (m == pm) o.bits(1, 1);
-      else o.bits(4, static_cast<uint32_t>(ei4::rem_mode(m, pm)));
-    }
-    o.ue((c >> 2) & 3u);
-    uint32_t code = 0;
-    while (kCbpIntraTab[code] != cbp) ++code;
-    o.ue(code);
-    if (cbp) {
-      o.se(0);
-      for (int k = 0; k < 16; ++k)
-        if ((cbp >> (k >> 2)) & 1) cavlc_luma(o, cp + 16 * k, 16, k, z);
-      cavlc_chroma(o, cp, cbp >> 4, z);
-    }
-    z.left_modes = modes;
-  } else {  // Intra16x16
-    const uint32_t mbt = 1 + (c & 3u) + 4 * static_cast<uint32_t>(cbp >> 4) + ((cbp & 15) ? 12 : 0);
-    o.ue(idr ? mbt : 5 + mbt);
-    o.ue((c >> 2) & 3u);
-    o.se(0);
-    cavlc_block(o, cp, 16, nc_of(z.l[0], -1));
-    if (cbp & 15)
-      for (int k = 0; k < 16; ++k) cavlc_luma(o, cp + 16 + 15 * k, 15, k, z);
-    cavlc_chroma(o, cp, cbp >> 4, z);
-    z.left_modes = ei4::kNoModes;
-  }
-  z.shift();
-  z.has_left = true;
-}
-
-// one slice (macroblock row) as CAVLC: what enc_write writes
-void cavlc_row(Sink &o, bool idr, int row, int mbw, int frame_num, int qp, const uint32_t *cmd, const uint8_t *cbp_row,
-               const int16_t *coef, const uint64_t *modes, const uint8_t *pcm) {
-  o.put(idr ? 0x65 : 0x41);
-  o.ue(static_cast<uint32_t>(row * mbw));
-  o.ue(idr ? 7 : 5);
-  o.ue(0);
-  o.bits(16, static_cast<uint32_t>(frame_num));
-  if (idr) {
-    o.ue(0);
-    o.bits(2, 0);
-  } else {
-    o.bits(3, 0);
-  }
-  o.se(qp - 26);
-  o.ue(1);
-  Row z;
-  z.start();
-  uint32_t skip = 0;
-  for (int mx = 0; mx < mbw; ++mx) {
-    const uint32_t c = cmd[mx];
-    const int16_t *cp = coef + static_cast<int64_t>(mx) * kCoefPerMb;
-    if (c == edb::kPcmCmd || edb::is_intra_cmd(c)) {
-      if (!idr) {
-        o.ue(skip);
-        skip = 0;
-      }
-      if (c == edb::kPcmCmd) {
-        o.ue(idr ? 25 : 30);
-        o.align();
-        for (int i = 0; i < 384; ++i) o.byte(pcm[384 * mx + i]);
-        z.all(16);
-        z.left_modes = ei4::kNoModes;
-        z.has_left = true;
-      } else {
-        cavlc_intra_mb(o, idr, c, modes[mx], cp, z);
-      }
-      continue;
-    }
-    const int cbp = cbp_row[mx];  // the harness codes vector (0, 0) only: mvd is 0 whatever the predictor
-    if (cbp == 0) {
-      ++skip;
-      z.all(0);
-    } else {
-      o.ue(skip);
-      skip = 0;
-      o.ue(0);
-      o.se(0);
-      o.se(0);
-      int code = 0;
-      while (kCbpInterTab[code] != cbp) ++code;
-      o.ue(static_cast<uint32_t>(code));
-      z.clear();
-      o.se(0);
-      for (int k = 0; k < 16; ++k)
-        if ((cbp >> (k >> 2)) & 1) cavlc_luma(o, cp + 16 * k, 16, k, z);
-      cavlc_chroma(o, cp, cbp >> 4, z);
-      z.shift();
-    }
-    z.left_modes = ei4::kNoModes;
-    z.has_left = true;
-  }
-  if (skip) o.ue(skip);
-  o.bits(1, 1);
-  o.align();
-}
-
-// the same slice through enc_cabac.h, in the order enc_write_cabac walks it
-template <class E>
-void cabac_mbs(E &e, Sink &o, bool idr, int mbw, const uint32_t *cmd, const uint8_t *cbp_row, const int16_t *coef,
-               const uint64_t *modes, const uint8_t *pcm) {
-  ecab::Left l = ecab::left_none();
-  for (int mx = 0; mx < mbw; ++mx) {
-    const uint32_t c = cmd[mx];
-    const int16_t *cp = coef + static_cast<int64_t>(mx) * kCoefPerMb;
-    const bool last = mx == mbw - 1;
-    if (c == edb::kPcmCmd) {
-      ecab::mb_pcm_begin(e, idr, l);
-      o.align();
-      for (int i = 0; i < 384; ++i) o.byte(pcm[384 * mx + i]);
-      ecab::mb_pcm_end(e, l, last);
-    } else if (ei4::is_i4_cmd(c)) {
-      ecab::mb_intra4(e, idr, l, c, modes[mx], cp, last);
-    } else if (edb::is_intra_cmd(c)) {
-      ecab::mb_intra16(e, idr, l, c, cp, last);
-    } else if (cbp_row[mx] == 0) {
-      ecab::mb_skip(e, l, last);
-    } else {
-      ecab::mb_inter(e, l, 0, 0, cbp_row[mx], cp, last);
-    }
-  }
-  e.sync();
-}
-void cabac_row(Sink &o, bool ring, bool idr, int row, int mbw, int frame_num, int qp, const uint32_t *cmd,
-               const uint8_t *cbp_row, const int16_t *coef, const uint64_t *modes, const uint8_t *pcm) {
-  ecab::slice_header(o, idr, row * mbw, frame_num, 0, qp, false, 0, 0);
-  uint8_t st[ecab::kNumCtx];
-  ecab::init_contexts(st, idr, qp);
-  ecab::Encoder<Sink> e{&o, st, 0, 0, 0, false};
-  e.start();
-  if (ring) {
-    std::vector<uint16_t> bins(ecab::kRingBins);
-    ecab::BinRing<Sink> r{&e, bins.data(), 0};
-    cabac_mbs(r, o, idr, mbw, cmd, cbp_row, coef, modes, pcm);
-  } else {
-    cabac_mbs(e, o, idr, mbw, cmd, cbp_row, coef, modes, pcm);
-  }
-  o.align();
-}
+using Row = ecav::Row;
+using BitCount = erbsp::BitCount;
 
 // ------------------------------------------------------------ the encoder
 // A macroblock's samples out of / into an NV12 picture [H * 3 / 2][W]
@@ -484,8 +203,8 @@ void intra_mb(const Enc &E, bool idr, int want, int mx, int64_t mbi, const MbPix
   // ---- the bits of both with the writer's own contexts, and the choice
   Row z16 = z, z4 = z;
   BitCount b16, b4;
-  cavlc_intra_mb(b16, idr, cmd16, ei4::kNoModes, c16, z16);
-  cavlc_intra_mb(b4, idr, cmd4, word, c4, z4);
+  ecav::intra16_layer(b16, idr, z16, cmd16, c16);
+  ecav::intra4_layer(b4, idr, z4, cmd4, word, c4);
   E.bits[2 * mbi] = static_cast<int32_t>(b16.n);
   E.bits[2 * mbi + 1] = static_cast<int32_t>(b4.n);
   const bool use4 = want == 2 || (want == 5 && b4.n < b16.n);
@@ -495,9 +214,8 @@ void intra_mb(const Enc &E, bool idr, int want, int mx, int64_t mbi, const MbPix
     E.cbp[mbi] = 0;
     E.modes[mbi] = ei4::kNoModes;
     rec = src;
-    z.all(16);
-    z.left_modes = ei4::kNoModes;
-    z.has_left = true;
+    BitCount b;  // the writer's bookkeeping only
+    ecav::mb_pcm_head(b, idr, z);
     return;
   }
   E.cmd[mbi] = use4 ? cmd4 : cmd16;
@@ -514,8 +232,6 @@ void inter_mb(const Enc &E, int want, int64_t mbi, const MbPix &src, const MbPix
   int16_t *cp = E.coef + mbi * kCoefPerMb;
   E.cmd[mbi] = 0;
   E.modes[mbi] = ei4::kNoModes;
-  z.left_modes = ei4::kNoModes;
-  z.has_left = true;
   int cbp = 0;
   if (want != 3) {
     for (int k = 0; k < 16; ++k) {
@@ -531,18 +247,13 @@ void inter_mb(const Enc &E, int want, int64_t mbi, const MbPix &src, const MbPix
     cbp |= code_chroma(src, ref.c, qpc, cp, rec) << 4;
   }
   E.cbp[mbi] = static_cast<uint8_t>(cbp);
+  BitCount b;  // the writer's bookkeeping, for the intra macroblocks to the right
   if (cbp == 0) {  // P_Skip
     rec = ref;
-    z.all(0);
-    return;
+    ecav::mb_skip(z);
+  } else {
+    ecav::mb_inter(b, z, 0, cbp, cp);
   }
-  // the writer's total_coeff bookkeeping, for the intra macroblocks to the right
-  BitCount b;
-  z.clear();
-  for (int k = 0; k < 16; ++k)
-    if ((cbp >> (k >> 2)) & 1) cavlc_luma(b, cp + 16 * k, 16, k, z);
-  cavlc_chroma(b, cp, cbp >> 4, z);
-  z.shift();
 }
 }  // namespace
 
@@ -595,9 +306,8 @@ extern "C" void ei4h_encode(int mbw, int mbh, int npic, int qp, const uint8_t *s
           cbp[mbi] = 0;
           modes[mbi] = ei4::kNoModes;
           r = s;
-          z.all(16);
-          z.left_modes = ei4::kNoModes;
-          z.has_left = true;
+          BitCount b;
+          ecav::mb_pcm_head(b, p == 0, z);
         } else if (want == 3 || want == 4) {
           inter_mb(E, want, mbi, s, ref, z, r);
         } else {
@@ -620,33 +330,59 @@ extern "C" int64_t ei4h_write(int mbw, int mbh, int npic, int qp, int cabac, con
                               int64_t *sizes) {
   const int W = 16 * mbw, H = 16 * mbh;
   const int64_t fsz = static_cast<int64_t>(W) * H * 3 / 2;
-  int64_t at = 0;
-  const int64_t slot = 64 + static_cast<int64_t>(mbw) * ecab::kMbBytes;
-  std::vector<uint8_t> buf(static_cast<size_t>(slot)), pcm(static_cast<size_t>(mbw) * 384);
-  for (int p = 0; p < npic; ++p) {
-    const int64_t at0 = at;
-    for (int row = 0; row < mbh; ++row) {
-      const int64_t r = (static_cast<int64_t>(p) * mbh + row) * mbw;
-      for (int mx = 0; mx < mbw; ++mx) {  // pcm_sample_luma 16 x 16, then Cb 8 x 8, Cr 8 x 8
-        MbPix s;
-        load_mb(src + p * fsz, W, H, mx, row, s);
-        std::memcpy(&pcm[384 * mx], s.y, 256);
-        std::memcpy(&pcm[384 * mx + 256], s.c, 128);
-      }
-      Sink o{buf.data(), slot, 0, 0, 0, 0, false};
-      if (cabac) cabac_row(o, cabac == 2, p == 0, row, mbw, p, qp, cmd + r, cbp + r, coef + r * kCoefPerMb, modes + r, pcm.data());
-      else cavlc_row(o, p == 0, row, mbw, p, qp, cmd + r, cbp + r, coef + r * kCoefPerMb, modes + r, pcm.data());
-      if (o.over || at + 4 + o.n > cap) return -1;
-      out[at] = static_cast<uint8_t>(o.n >> 24);
-      out[at + 1] = static_cast<uint8_t>(o.n >> 16);
-      out[at + 2] = static_cast<uint8_t>(o.n >> 8);
-      out[at + 3] = static_cast<uint8_t>(o.n);
-      std::memcpy(out + at + 4, buf.data(), static_cast<size_t>(o.n));
-      at += 4 + o.n;
+  std::vector<uint8_t> pcm(static_cast<size_t>(mbw) * 384);
+  auto row_data = [&](int p, int row) {
+    const int64_t r = (static_cast<int64_t>(p) * mbh + row) * mbw;
+    for (int mx = 0; mx < mbw; ++mx) {  // pcm_sample_luma 16 x 16, then Cb 8 x 8, Cr 8 x 8
+      MbPix s;
+      load_mb(src + p * fsz, W, H, mx, row, s);
+      std::memcpy(&pcm[384 * mx], s.y, 256);
+      std::memcpy(&pcm[384 * mx + 256], s.c, 128);
     }
-    sizes[p] = at - at0;
+    return RowData{cmd + r, cbp + r, coef + r * kCoefPerMb, modes + r, pcm.data()};
+  };
+  return write_pictures(mbw, mbh, npic, qp, false, cabac, row_data, out, cap, sizes);
+}
+
+// Counting against writing, macroblock by macroblock of one CAVLC slice: counted[mx] the bits enc_cavlc.h's
+// mb_* function adds on the counting sink, written[mx] the RBSP bits the byte sink received from the same
+// call (the bytes it stored less the emulation prevention bytes among them, and the bits it still holds).
+// A P_Skip macroblock gives 0 and 0: its run goes with the next coded macroblock.  I_PCM: the head only (the
+// samples follow in the byte sink, outside the count).  Returns 0 when the two row states ended equal and
+// nothing overflowed.
+extern "C" int ei4h_count(int idr, int mbw, const uint32_t *cmd, const uint8_t *cbp, const int16_t *coef,
+                          const uint64_t *modes, const uint8_t *pcm, int64_t *counted, int64_t *written) {
+  const RowData d{cmd, cbp, coef, modes, pcm};
+  std::vector<uint8_t> buf(static_cast<size_t>(64 + static_cast<int64_t>(mbw) * ecab::kMbBytes));
+  Sink o{buf.data(), static_cast<int64_t>(buf.size())};
+  auto rbsp_bits = [&]() {
+    int64_t ep = 0;
+    for (int64_t i = 0, zeros = 0; i < o.n; ++i) {
+      if (zeros >= 2 && buf[i] == 3) {
+        ++ep;
+        zeros = 0;
+        continue;
+      }
+      zeros = buf[i] ? 0 : zeros + 1;
+    }
+    return 8 * (o.n - ep) + o.nacc;
+  };
+  Row zw, zc;
+  zw.start();
+  zc.start();
+  int bad = 0;
+  for (int mx = 0; mx < mbw; ++mx) {
+    BitCount b;
+    const int64_t before = rbsp_bits();
+    cavlc_mb(b, idr != 0, zc, d, mx);
+    cavlc_mb(o, idr != 0, zw, d, mx);
+    counted[mx] = b.n;
+    written[mx] = rbsp_bits() - before;
+    if (cmd[mx] == edb::kPcmCmd) pcm_samples(o, pcm + 384 * mx);
+    bad |= std::memcmp(zw.lnz, zc.lnz, sizeof zw.lnz) || std::memcmp(zw.lnzc, zc.lnzc, sizeof zw.lnzc) ||
+           zw.skip != zc.skip || zw.left_modes != zc.left_modes || zw.a_ok != zc.a_ok || zw.amx != zc.amx || zw.amy != zc.amy;
   }
-  return at;
+  return bad || o.over;
 }
 
 #ifndef EI4H_NO_SPS_PPS  // enc_intra4_main.cpp links no stream writer

@@ -11,8 +11,10 @@ exposes them.
             9.3.3.2 returns the bins.
   contexts: the I and the cabac_init_idc 0 columns against the formula.
   slices:   seeded macroblock rows of every kind the encoder has are written
-            as CABAC through the header and as CAVLC by the harness; the CPU
-            oracle's general decoder gives the same pictures for both.
+            as CABAC through the header and as CAVLC through `csrc/enc_cavlc.h`,
+            the header the `enc_write` kernel calls; the CPU oracle's general
+            decoder gives the same pictures for both.
+  sinks:    the kernels' dword sink against the byte sink (`csrc/enc_rbsp.h`).
 """
 from __future__ import annotations
 
@@ -49,6 +51,7 @@ def lib(tmp_path_factory):
     L.ech_sps_pps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ech_pictures.argtypes = [C.c_int] * 6 + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]
     L.ech_pictures.restype = C.c_int64
+    L.ech_sinks.argtypes = [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3
     return L
 
 
@@ -421,6 +424,46 @@ def test_slices_decode_to_the_pictures_of_the_same_rows_as_cavlc(lib, tmp_path, 
         sizes[1] += nb
     assert seen == set(range(6))             # every kind of macroblock was written
     print(f"mbw {mbw}: CAVLC {sizes[0]} bytes, CABAC {sizes[1]} bytes")
+
+
+def _sinks(lib, idr, mbw, qp, dbk, row, cap, room):
+    """ech_sinks into buffers of `room` bytes filled with 0xAB: (bytes, dword sink's bytes, res)."""
+    cmd, cbp, coef, pcm = row
+    by, wd, res = np.full(room, 0xAB, np.uint8), np.full(room // 4, 0xABABABAB, np.uint32), np.zeros(4, np.int64)
+    lib.ech_sinks(idr, mbw, qp, dbk, cmd.ctypes.data, cbp.ctypes.data, coef.ctypes.data, pcm.ctypes.data, cap,
+                  by.ctypes.data, wd.ctypes.data, res.ctypes.data)
+    return by, wd.view(np.uint8), res.tolist()
+
+
+def test_the_dword_sink_and_the_byte_sink_agree(lib):
+    """The kernel's sink (four bytes per aligned dword store) against the harness's byte sink over the same
+    CAVLC slices: the same bytes and length, with emulation prevention bytes and every length mod 4; short
+    of the length by 1 .. 5 bytes both report the overflow and nothing is stored at or past `cap`."""
+    residues, escaped = set(), 0
+    for seed in range(24):
+        rng = np.random.default_rng(900 + seed)
+        mbw = (1, 2, 5)[seed % 3]
+        cmd, cbp, coef, pcm, _ = _rows(rng, mbw, 1, 2, 1500 if seed % 4 == 0 else 60)
+        pcm[rng.random(pcm.shape) < 0.5] = 0             # zero runs: emulation prevention inside the samples
+        coef[rng.random(coef.shape) < 0.5] = 0
+        for idr in (1, 0):                               # picture 0 holds the kinds of an I slice
+            sl = slice(0, mbw) if idr else slice(mbw, 2 * mbw)
+            row = tuple(np.ascontiguousarray(a[sl]) for a in (cmd, cbp, coef, pcm))
+            room = mbw * 9024 + 64
+            by, wd, (nb, ob, nw, ow) = _sinks(lib, idr, mbw, 20 + seed, seed & 1, row, room, room + 64)
+            assert (ob, ow) == (0, 0) and nb == nw > 0
+            full = by[:nb].tobytes()
+            assert wd[:nb].tobytes() == full
+            assert (by[nb:] == 0xAB).all() and (wd[(nb + 3) // 4 * 4:] == 0xAB).all()
+            residues.add(nb % 4)
+            escaped += full.count(b"\x00\x00\x03")
+            for short in (1, 2, 3, 4, 5):
+                cap = nb - short
+                by, wd, (n1, o1, n2, o2) = _sinks(lib, idr, mbw, 20 + seed, seed & 1, row, cap, room + 64)
+                assert (n1, o1, n2, o2) == (nb, 1, nb, 1), f"seed {seed} idr {idr} cap -{short}"
+                assert (by[cap:] == 0xAB).all() and (wd[cap:] == 0xAB).all()
+                assert by[:cap].tobytes() == full[:cap] and wd[:cap // 4 * 4].tobytes() == full[:cap // 4 * 4]
+    assert residues == {0, 1, 2, 3} and escaped > 100
 
 
 def test_sanitizer_run_of_the_stand_alone_driver(tmp_path):

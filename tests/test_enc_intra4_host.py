@@ -12,7 +12,9 @@ the CABAC writer.  The harness (tests/native/enc_intra4_host.cpp) exposes them.
   rows:     seeded macroblock rows mixing I_NxN with Intra16x16, I_PCM, P_Skip
             and coded inter neighbours are coded by the harness, written as
             CAVLC and as CABAC (directly and through BinRing, the same bytes),
-            and the CPU oracle decodes both to the harness's reconstruction.
+            and the CPU oracle decodes both to the harness's reconstruction;
+  counts:   `csrc/enc_cavlc.h`, the CAVLC writer of the `enc_write` kernel and of
+            the harness: what it counts is what it writes.
 """
 from __future__ import annotations
 
@@ -60,6 +62,7 @@ def lib(tmp_path_factory):
     L.ei4h_write.argtypes = [C.c_int] * 5 + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p]
     L.ei4h_write.restype = C.c_int64
     L.ei4h_sps_pps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ei4h_count.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 7
     return L
 
 
@@ -332,6 +335,78 @@ def test_rows_decode_to_the_harness_reconstruction(lib, tmp_path, mbw, qp):
     assert files[1] == files[2]                          # BinRing and drain(): the bytes of the direct coder
     print(f"mbw {mbw} qp {qp}: CAVLC {len(files[0])} bytes, CABAC {len(files[1])} bytes; "
           f"I_NxN {int(i4.sum())}, Intra16x16 {int(i16.sum())}, I_PCM {int((cmd == PCM).sum())}, inter {int(inter.sum())}")
+
+
+# ------------------------------------------- counting equals writing
+KINDS = ("pcm", "i16", "i16ac", "i4", "i4cbp", "skip", "inter")
+
+
+def _levels(rng, n):
+    """[n][384] levels: per 16-level block empty, sparse, dense or full (16 coefficients); mostly small
+    magnitudes, trailing ones, and escapes up to |level| = 2047."""
+    dens = rng.choice([0.0, 0.15, 0.6, 1.0], (n, 24, 1), p=[0.2, 0.4, 0.25, 0.15])
+    on = rng.random((n, 24, 16)) < dens
+    k = rng.integers(0, 20, on.shape)
+    mag = np.where(k < 9, 1, np.where(k < 15, rng.integers(1, 5, on.shape),
+                   np.where(k < 18, rng.integers(1, 70, on.shape), rng.integers(1, 2048, on.shape))))
+    mag[rng.random(on.shape) < 0.004] = 2047
+    return (on * mag * rng.choice([-1, 1], on.shape)).astype(np.int16).reshape(n, 384)
+
+
+def _count_row(rng, idr, mbw):
+    """One slice's macroblocks of seeded kinds; returns the arrays ei4h_count reads and the kinds."""
+    cmd, cbp, modes = np.zeros(mbw, np.uint32), np.zeros(mbw, np.uint8), np.full(mbw, NONE, np.uint64)
+    coef, pcm = _levels(rng, mbw), rng.integers(1, 256, (mbw, 384)).astype(np.uint8)
+    kinds = [str(rng.choice(KINDS[:5] if idr else KINDS)) for _ in range(mbw)]
+    for mx, kind in enumerate(kinds):
+        cm = int(rng.integers(0, 2)) if mx else 0
+        cc = int(rng.integers(0, 3))
+        if kind == "pcm":
+            cmd[mx] = PCM
+        elif kind in ("i16", "i16ac"):
+            cmd[mx] = 0x80000000 | (int(rng.integers(1, 3)) if mx else 2) | (cm << 2) | (((15 if kind == "i16ac" else 0) | (cc << 4)) << 4)
+        elif kind in ("i4", "i4cbp"):
+            c = int(rng.integers(1, 48)) if kind == "i4cbp" else 0
+            cmd[mx] = 0x80004000 | (cm << 2) | (c << 4)
+            cbp[mx] = c
+            modes[mx] = _word(rng.integers(0, 9, 16))
+        elif kind == "inter":
+            mv = rng.integers(-67, 68, 2)
+            cbp[mx] = int(rng.integers(0, 48))
+            if not mv.any() and not cbp[mx]:
+                mv[1] = -67
+            cmd[mx] = (int(mv[0]) & 0xffff) | ((int(mv[1]) & 0xffff) << 16)
+    return cmd, cbp, coef, modes, pcm, kinds
+
+
+@pytest.mark.parametrize("mbw", [1, 2, 5])
+def test_counted_bits_equal_the_bits_written(lib, mbw):
+    """What enc_intra's choice between Intra16x16, I_NxN and I_PCM rests on: every macroblock kind of
+    enc_cavlc.h adds to the counting sink exactly the RBSP bits it gives the byte sink, whatever the left
+    macroblock was (none, I_PCM: 16s, P_Skip: 0s, coded), a P_Skip run in front of it included."""
+    rng = np.random.default_rng(7000 + mbw)
+    seen, runs, top, full = set(), 0, 0, False
+    for trial in range(240):
+        idr = trial % 3 == 0
+        cmd, cbp, coef, modes, pcm, kinds = _count_row(rng, idr, mbw)
+        counted, written = np.zeros(mbw, np.int64), np.zeros(mbw, np.int64)
+        assert lib.ei4h_count(int(idr), mbw, cmd.ctypes.data, cbp.ctypes.data, coef.ctypes.data, modes.ctypes.data,
+                              pcm.ctypes.data, counted.ctypes.data, written.ctypes.data) == 0
+        assert counted.tolist() == written.tolist(), f"trial {trial}: {kinds}"
+        top = max(top, int(np.abs(coef).max()))
+        full |= bool((coef[:, :256].reshape(-1, 16) != 0).all(axis=1).any())
+        for mx, kind in enumerate(kinds):
+            left = "none" if mx == 0 else {"pcm": "pcm", "skip": "skip"}.get(kinds[mx - 1], "coded")
+            seen.add((left, kind))
+            if kind == "skip":
+                assert counted[mx] == 0
+            else:
+                assert counted[mx] > 0
+                runs += mx > 0 and kinds[mx - 1] == "skip"
+    assert top == 2047 and full
+    lefts = ("none",) if mbw == 1 else ("none", "pcm", "skip", "coded")
+    assert seen == {(l, k) for l in lefts for k in KINDS}
+    assert mbw == 1 or runs > 20                         # mb_skip_run > 0 ahead of a coded macroblock
 
 
 def test_sanitizer_run_of_the_stand_alone_driver(tmp_path):

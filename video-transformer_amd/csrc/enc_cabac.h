@@ -5,8 +5,8 @@
 //   Encoder<Sink>  the arithmetic encoder of 9.3.4 (Figures 9-7 .. 9-12):
 //                  InitEncoder, EncodeDecision, EncodeBypass, EncodeTerminate,
 //                  EncodeFlush, PutBit with outstanding bits; its bits go into
-//                  a Sink (ByteSink here, NalOut in the kernel: RBSP bits ->
-//                  EBSP bytes with emulation prevention).
+//                  a Sink (enc_rbsp.h: ByteSink in the harness, WordSink in the
+//                  kernel: RBSP bits -> EBSP bytes with emulation prevention).
 //   init_contexts  9.3.1.1 from h264_cabac_tables.h: the I column or
 //                  cabac_init_idc 0, the only column the device decoder reads.
 //   one function per syntax element of 7.3.4 / 7.3.5 that the encoder has:
@@ -33,6 +33,7 @@
 
 #include "enc_deblock.h"
 #include "enc_intra4.h"
+#include "enc_rbsp.h"
 #include "h264_cabac_tables.h"
 
 namespace vts {
@@ -93,76 +94,13 @@ VTS_HD inline void init_contexts(uint8_t *st, bool islice, int qp) {
   for (int i = 0; i < kNumCtx; ++i) st[i] = init_context(i, islice, qp);
 }
 
-// RBSP bits -> EBSP bytes (7.4.1.1 emulation prevention) into a bounded
-// buffer; `over` instead of a store past `cap`.  The kernel's NalOut has the
-// same members and stores dwords.
-struct ByteSink {
-  uint8_t *p;
-  int64_t cap, n;
-  uint64_t acc;
-  int nacc, zeros;
-  bool over;
-  VTS_HD void put(uint32_t b) {
-    if (n < cap) p[n] = static_cast<uint8_t>(b);
-    else over = true;
-    ++n;
-  }
-  VTS_HD void byte(uint32_t b) {
-    if (zeros >= 2 && b <= 3) {
-      put(3);
-      zeros = 0;
-    }
-    put(b);
-    zeros = b ? 0 : zeros + 1;
-  }
-  VTS_HD void bits(int k, uint32_t v) {  // k <= 32
-    acc = (acc << k) | v;
-    nacc += k;
-    while (nacc >= 8) {
-      nacc -= 8;
-      byte(static_cast<uint32_t>(acc >> nacc) & 0xffu);
-    }
-  }
-  VTS_HD void ue(uint32_t v) {
-    const uint32_t x = v + 1;
-    const int len = 31 - __builtin_clz(x);
-    if (len) bits(len, 0);
-    bits(len + 1, x);
-  }
-  VTS_HD void se(int v) { ue(v > 0 ? static_cast<uint32_t>(2 * v - 1) : static_cast<uint32_t>(-2 * v)); }
-  VTS_HD void align() {
-    if (nacc) bits(8 - nacc, 0);
-  }
-};
+using erbsp::ByteSink;  // the harness's sink; the kernel's is erbsp::WordSink (enc_rbsp.h)
 
-// The slice header of the encoder's slices (7.3.3) with
-// entropy_coding_mode_flag = 1: what enc_write writes, cabac_init_idc in its
-// place in P slices, then cabac_alignment_one_bits (7.3.4).  dbk: the slice
-// asks for the filter inside the slice with the two offsets.
+// The slice header with entropy_coding_mode_flag = 1 and SliceQPY = qp
 template <class Sink>
-VTS_HD inline void slice_header(Sink &o, bool idr, int first_mb, int frame_num, int idr_pic_id, int qp, bool dbk,
-                                int dbk_alpha, int dbk_beta) {
-  o.put(idr ? 0x65 : 0x41);  // nal_ref_idc 3 IDR / 2 non-IDR
-  o.ue(static_cast<uint32_t>(first_mb));
-  o.ue(idr ? 7 : 5);  // slice_type I / P (all slices of the picture)
-  o.ue(0);            // pic_parameter_set_id
-  o.bits(16, static_cast<uint32_t>(frame_num) & 0xffffu);
-  if (idr) {
-    o.ue(static_cast<uint32_t>(idr_pic_id));
-    o.bits(2, 0);  // no_output_of_prior_pics, long_term_reference
-  } else {
-    o.bits(3, 0);  // num_ref_idx_active_override, ref_pic_list_modification_l0, adaptive_ref_pic_marking
-    o.ue(0);       // cabac_init_idc
-  }
-  o.se(qp - 26);  // slice_qp_delta (pic_init_qp 26)
-  if (dbk) {
-    o.ue(2);  // disable_deblocking_filter_idc: filtered, but not across slice boundaries
-    o.se(dbk_alpha);
-    o.se(dbk_beta);
-  } else {
-    o.ue(1);
-  }
-  if (o.nacc) o.bits(8 - o.nacc, (1u << (8 - o.nacc)) - 1u);  // cabac_alignment_one_bit
+VTS_HD VTS_INLINE void slice_header(Sink &o, bool idr, int first_mb, int frame_num, int idr_pic_id, int qp, bool dbk,
+                                    int dbk_alpha, int dbk_beta) {
+  erbsp::slice_header(o, true, idr, first_mb, frame_num, idr_pic_id, qp - 26, dbk, dbk_alpha, dbk_beta);
 }
 
 // 9.3.4: st holds kNumCtx context variables (LDS in the kernel).

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "enc_cabac.h"
+#include "enc_cavlc.h"
 #include "enc_deblock.h"
 #include "enc_rate.h"
 #include "mp4.h"
@@ -177,34 +178,18 @@ __global__ void __launch_bounds__(256) downscale_nv12(DsArgs a) {
 // qbits) with qbits = 15 + qp / 6 and f = 2^qbits / 6 (chroma DC through the
 // 2x2 Hadamard at qbits + 1 and 2f), the decoder's own scaling + inverse
 // transform (full::scale_idct4) for the reconstruction, and CAVLC
-// residual_block (9.2) for the bits.  Restated in oracle/transcode_oracle.c.
+// residual_block (9.2, enc_cavlc.h) for the bits.  Restated in
+// oracle/transcode_oracle.c.
 constexpr int kCoefPerMb = 384;  // luma 16 x 16 by luma4x4BlkIdx, Cb / Cr DC 2 x 4, Cb / Cr AC 8 x 15 (scan order)
 constexpr int kPcmBits = 3072;   // I_PCM payload: a residual bounded above it is not worth coding
-__device__ __constant__ static const uint8_t kCtLen[4][17][4] = VTS_CT_LEN_DATA;
-__device__ __constant__ static const uint8_t kCtCode[4][17][4] = VTS_CT_CODE_DATA;
-__device__ __constant__ static const uint8_t kTzLen[15][16] = VTS_TZ_LEN_DATA;
-__device__ __constant__ static const uint8_t kTzCode[15][16] = VTS_TZ_CODE_DATA;
-__device__ __constant__ static const uint8_t kTzcLen[3][4] = VTS_TZC_LEN_DATA;
-__device__ __constant__ static const uint8_t kTzcCode[3][4] = VTS_TZC_CODE_DATA;
-__device__ __constant__ static const uint8_t kRbLen[7][15] = VTS_RB_LEN_DATA;
-__device__ __constant__ static const uint8_t kRbCode[7][15] = VTS_RB_CODE_DATA;
 __device__ __constant__ static const uint8_t kZz4[16] = VTS_ZZ_DATA;
-__device__ __constant__ static const uint8_t kCbpInterTab[48] = VTS_CBPP_DATA;
 __device__ __constant__ static const uint8_t kQpcTab[52] = VTS_QPC_DATA;
 __device__ __constant__ static const uint8_t kBlkXd[16] = {0, 1, 0, 1, 2, 3, 2, 3, 0, 1, 0, 1, 2, 3, 2, 3};
 __device__ __constant__ static const uint8_t kBlkYd[16] = {0, 0, 1, 1, 0, 0, 1, 1, 2, 2, 3, 3, 2, 2, 3, 3};
-__device__ __constant__ static const uint8_t kCbpIntraTab[48] = VTS_CBPI_DATA;  // Intra_4x4 column of Table 9-4
 namespace er = full::erate;
 namespace eres = full::eres;  // the transform, the quantiser and the reconstruction (enc_residual.h)
 namespace ei4 = full::ei4;    // the Intra_4x4 decisions (enc_intra4.h)
-
-// bits of residual_block_cavlc (7.3.5.3.2, 9.2) of levels lv[0, maxNum) in
-// scan order with nC (-1: chroma DC); nC < -1: an upper bound (coeff_token
-// taken as the longest code over the nC classes and the 6-bit FLC).  With o,
-// the block is also written.
-struct NalOut;
-template <bool kWrite>
-__device__ int cavlc_block(NalOut *o, const int *lv, int maxNum, int nC);
+namespace ecav = full::ecav;  // the CAVLC slice writer and its bit counts (enc_cavlc.h)
 
 // ------------------------------------------------------ motion search
 struct SearchArgs {
@@ -734,7 +719,7 @@ __device__ __forceinline__ void finish_residual(const SearchArgs &a, int lane, c
     nzb = eres::code_block<false>(x, qp, z, lv, nullptr);
     full::scale_idct4(z, qp, false, res);
     luma_block_recon(lane, P, res, recy);
-    bits = cavlc_block<false>(nullptr, lv, 16, -2);
+    bits = ecav::count_block(lv, 16, -2);
   } else if (lane < 24) {
     nzb = chroma_block_code(lane, P.srcc, P, qpc, z, lv, dcw);
   }
@@ -752,10 +737,10 @@ __device__ __forceinline__ void finish_residual(const SearchArgs &a, int lane, c
   if (lane < 16) {
     contrib = ((cbp >> (lane >> 2)) & 1) ? bits : 0;
   } else if (lane < 24) {
-    contrib = cc == 2 ? cavlc_block<false>(nullptr, lv, 15, -2) : 0;
+    contrib = cc == 2 ? ecav::count_block(lv, 15, -2) : 0;
   } else if (lane < 26 && cc) {
     const int d4[4] = {dcl[lane - 24][0], dcl[lane - 24][1], dcl[lane - 24][2], dcl[lane - 24][3]};
-    contrib = cavlc_block<false>(nullptr, d4, 4, -1);
+    contrib = ecav::count_block(d4, 4, -1);
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) contrib += __shfl_xor(contrib, off);
@@ -855,139 +840,9 @@ struct WriteArgs {
   const uint64_t *i4;   // [entry][mb] the Intra4x4PredModes of the I_NxN macroblocks (intra4x4; else unread)
 };
 
-// RBSP bits -> EBSP bytes (emulation prevention) into a staging slot, four
-// bytes per (aligned) dword store.
-struct NalOut {
-  uint32_t *w;          // slot payload (slot + 4), 4-byte aligned
-  int64_t cap, n;       // bytes
-  uint32_t cur;         // the bytes of the word being filled
-  uint64_t acc;
-  int nacc, zeros;
-  bool over;
-  __device__ void put(uint32_t b) {
-    cur |= b << (8 * (n & 3));
-    if (!(++n & 3)) {
-      if (n <= cap) w[(n >> 2) - 1] = cur;
-      else over = true;
-      cur = 0;
-    }
-  }
-  __device__ void flush() {  // the partial word (its tail bytes are don't-care)
-    if (n & 3) {
-      if (n <= cap) w[n >> 2] = cur;
-      else over = true;
-    }
-  }
-  __device__ void byte(uint32_t b) {
-    if (zeros >= 2 && b <= 3) {
-      put(3);
-      zeros = 0;
-    }
-    put(b);
-    zeros = b ? 0 : zeros + 1;
-  }
-  __device__ void bits(int k, uint32_t v) {  // k <= 32
-    acc = (acc << k) | v;
-    nacc += k;
-    while (nacc >= 8) {
-      nacc -= 8;
-      byte(static_cast<uint32_t>(acc >> nacc) & 0xffu);
-    }
-  }
-  __device__ void ue(uint32_t v) {
-    const uint32_t x = v + 1;
-    const int len = 31 - __builtin_clz(x);
-    if (len) bits(len, 0);
-    bits(len + 1, x);
-  }
-  __device__ void se(int v) { ue(v > 0 ? static_cast<uint32_t>(2 * v - 1) : static_cast<uint32_t>(-2 * v)); }
-  __device__ void align() {
-    if (nacc) bits(8 - nacc, 0);
-  }
-};
-
-template <bool kWrite>
-__device__ int cavlc_block(NalOut *o, const int *lv, int maxNum, int nC) {
-  int tc = 0, t1 = 0, top = -1;
-  bool open = true;
-#pragma unroll
-  for (int i = 15; i >= 0; --i) {
-    const int v = i < maxNum ? lv[i] : 0;
-    if (!v) continue;
-    if (top < 0) top = i;
-    ++tc;
-    if (open && t1 < 3 && (v == 1 || v == -1)) ++t1;
-    else open = false;
-  }
-  int bits;
-  if (nC < -1) {  // the bound: the longest coeff_token over nC classes 0..2 and the FLC
-    bits = max(6, max(static_cast<int>(kCtLen[0][tc][t1]), max(static_cast<int>(kCtLen[1][tc][t1]),
-                                                              static_cast<int>(kCtLen[2][tc][t1]))));
-  } else if (nC >= 8) {
-    bits = 6;
-    if (kWrite) o->bits(6, tc == 0 ? 3u : static_cast<uint32_t>(((tc - 1) << 2) | t1));
-  } else {
-    const int col = nC == -1 ? 3 : (nC < 2 ? 0 : (nC < 4 ? 1 : 2));
-    bits = kCtLen[col][tc][t1];
-    if (kWrite) o->bits(bits, kCtCode[col][tc][t1]);
-  }
-  if (tc == 0) return bits;
-  int k = 0, sl = (tc > 10 && t1 < 3) ? 1 : 0;
-#pragma unroll
-  for (int i = 15; i >= 0; --i) {  // trailing ones' signs, then levels (9.2.2.1 inverted)
-    const int v = i < maxNum ? lv[i] : 0;
-    if (!v) continue;
-    if (k < t1) {
-      ++bits;
-      if (kWrite) o->bits(1, v < 0 ? 1u : 0u);
-    } else {
-      int code = v > 0 ? 2 * v - 2 : -2 * v - 1;
-      if (k == t1 && t1 < 3) code -= 2;
-      int prefix, suffix = 0, ssize = 0;
-      if (sl == 0) {
-        if (code < 14) prefix = code;
-        else if (code < 30) { prefix = 14; suffix = code - 14; ssize = 4; }
-        else { prefix = 15; suffix = code - 30; ssize = 12; }
-      } else if (code < (15 << sl)) {
-        prefix = code >> sl;
-        suffix = code & ((1 << sl) - 1);
-        ssize = sl;
-      } else {
-        prefix = 15;
-        suffix = code - (15 << sl);
-        ssize = 12;
-      }
-      bits += prefix + 1 + ssize;
-      if (kWrite) {
-        o->bits(prefix + 1, 1u);
-        if (ssize) o->bits(ssize, static_cast<uint32_t>(suffix));
-      }
-      if (sl == 0) sl = 1;
-      if (abs(v) > (3 << (sl - 1)) && sl < 6) ++sl;
-    }
-    ++k;
-  }
-  int zl = top + 1 - tc;  // total_zeros
-  if (tc < maxNum) {
-    const int len = maxNum == 4 ? kTzcLen[tc - 1][zl] : kTzLen[tc - 1][zl];
-    bits += len;
-    if (kWrite) o->bits(len, maxNum == 4 ? kTzcCode[tc - 1][zl] : kTzCode[tc - 1][zl]);
-  }
-  int prev = -1;
-#pragma unroll
-  for (int i = 15; i >= 0; --i) {  // run_before of every coefficient but the lowest
-    const int v = i < maxNum ? lv[i] : 0;
-    if (!v) continue;
-    if (prev >= 0 && zl > 0) {
-      const int run = prev - i - 1, row = min(zl, 7) - 1;
-      bits += kRbLen[row][run];
-      if (kWrite) o->bits(kRbLen[row][run], kRbCode[row][run]);
-      zl -= run;
-    }
-    prev = i;
-  }
-  return bits;
-}
+// RBSP bits -> EBSP bytes into a staging slot, four bytes per (aligned) dword
+// store: slot payload (slot + 4), 4-byte aligned
+using NalOut = full::erbsp::WordSink;
 
 // ------------------------------------------------------ intra coding
 // Intra16x16 in place of I_PCM (vts_transcode_params.intra).
@@ -1003,12 +858,6 @@ __device__ int cavlc_block(NalOut *o, const int *lv, int maxNum, int nC) {
 // 2..3 intra_chroma_pred_mode, 4..9 coded_block_pattern (luma 0 or 15).
 using full::edb::kIntraCmd;
 using full::edb::is_intra_cmd;
-__device__ __forceinline__ int ue_bits(uint32_t v) { return 2 * (31 - __builtin_clz(v + 1)) + 1; }
-// nC of 9.2.1 from the left (na) and upper (nb) blocks' total_coeff, -1 = unavailable
-__device__ __forceinline__ int nc_of(int na, int nb) {
-  return (na >= 0 && nb >= 0) ? (na + nb + 1) >> 1 : (na >= 0 ? na : (nb >= 0 ? nb : 0));
-}
-
 struct IntraArgs {
   const int4 *ent;      // the level's search entries: (frame, -, dst slot, 0)
   const uint8_t *small;
@@ -1023,13 +872,6 @@ struct IntraArgs {
                         // pictures); 0: the macroblocks enc_search left as kPcmCmd (dst holds the source)
   uint64_t *i4;         // enc_intra<true>: [entry][mb] the Intra4x4PredModes of an I_NxN macroblock, else ~0
 };
-
-// me(v) of an I_NxN macroblock's coded_block_pattern (Table 9-4, Intra_4x4 column)
-__device__ __forceinline__ uint32_t cbp_intra_code(int cbp) {
-  uint32_t code = 0;
-  while (kCbpIntraTab[code] != cbp) ++code;
-  return code;
-}
 
 // kI4 (vts_transcode_ext5.intra4x4, DESIGN.md §11 "Intra4x4"): every
 // candidate macroblock is also tried as I_NxN with sixteen Intra_4x4 blocks,
@@ -1192,27 +1034,24 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
     for (int q = 0; q < 16; ++q) dlv[q] = 0;
     if (lane < 16) {
       if (ac) {
-        const int na = bxl ? tcy[byl * 4 + bxl - 1] : lnz[byl], nb = byl ? tcy[(byl - 1) * 4 + bxl] : -1;
-        contrib = cavlc_block<false>(nullptr, lv, 15, nc_of(na, nb));
+        contrib = ecav::count_block(lv, 15, ecav::nc_luma(byl * 4 + bxl, tcy, lnz));
       }
     } else if (lane < 24) {
       if (cc == 2) {
-        const int pl = (lane - 16) >> 2, k = (lane - 16) & 3, bx = k & 1, by = k >> 1;
-        const int na = bx ? tcc[pl][by * 2] : lnzc[pl][by], nb = by ? tcc[pl][bx] : -1;
-        contrib = cavlc_block<false>(nullptr, lv, 15, nc_of(na, nb));
+        contrib = ecav::count_block(lv, 15, ecav::nc_chroma((lane - 16) >> 2, (lane - 16) & 3, tcc, lnzc));
       }
     } else if (lane < 26) {
       if (cc) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) dlv[q] = dcl[lane - 24][q];
-        contrib = cavlc_block<false>(nullptr, dlv, 4, -1);
+        contrib = ecav::count_block(dlv, 4, -1);
       }
     } else if (lane == 26) {  // the header and Intra16x16DCLevel (nC of block 0)
 #pragma unroll
       for (int q = 0; q < 16; ++q) dlv[q] = ydl[kZz4[q]];
       const int mbt = 1 + lmode + 4 * cc + (ac ? 12 : 0);
-      contrib = ue_bits(static_cast<uint32_t>(a.all ? mbt : 5 + mbt)) + ue_bits(static_cast<uint32_t>(cmode)) + 1 +
-                cavlc_block<false>(nullptr, dlv, 16, nc_of(lnz[0], -1));
+      contrib = ecav::ue_bits(static_cast<uint32_t>(a.all ? mbt : 5 + mbt)) + ecav::ue_bits(static_cast<uint32_t>(cmode)) + 1 +
+                ecav::count_block(dlv, 16, ecav::nc_luma(0, tcy, lnz));
     }
     [[maybe_unused]] int own = 0;  // kI4: lanes 16..25 hold the chroma bits, the same for both candidates
     if constexpr (kI4) own = contrib;
@@ -1298,14 +1137,13 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
       int c4 = 0;
       if (lane < 16) {
         if (coded8) {
-          const int na = bxl ? tc4[byl * 4 + bxl - 1] : lnz[byl], nb = byl ? tc4[(byl - 1) * 4 + bxl] : -1;
-          c4 = cavlc_block<false>(nullptr, lv4k, 16, nc_of(na, nb));
+          c4 = ecav::count_block(lv4k, 16, ecav::nc_luma(byl * 4 + bxl, tc4, lnz));
         }
       } else if (lane < 26) {
         c4 = own;
       } else if (lane == 26) {  // mb_type, the sixteen modes, intra_chroma_pred_mode, coded_block_pattern, mb_qp_delta
-        c4 = ue_bits(a.all ? 0u : 5u) + mbits + ue_bits(static_cast<uint32_t>(cmode)) + ue_bits(cbp_intra_code(cbp4)) +
-             (cbp4 ? 1 : 0);
+        c4 = ecav::ue_bits(a.all ? 0u : 5u) + mbits + ecav::ue_bits(static_cast<uint32_t>(cmode)) +
+             ecav::ue_bits(ecav::cbp_intra_code(cbp4)) + (cbp4 ? 1 : 0);
       }
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) c4 += __shfl_xor(c4, off);
@@ -1557,98 +1395,6 @@ __global__ void __launch_bounds__(256) enc_hash(const int4 *ent, const uint8_t *
     atomicAdd(acc, (part[0] + part[1] + part[2] + part[3]) * static_cast<unsigned long long>(en.x + 1));
 }
 
-// chroma DC and AC of residual() (7.3.5.3) as put_residual writes them, cc =
-// coded_block_pattern / 16 (a copy: put_residual keeps its own loop so that
-// the encoder without intra compiles to the code it was)
-__device__ void put_chroma_residual(NalOut &o, const int16_t *cp, int cc, const int (*lnzc)[2], int (*cnzc)[4]) {
-  int lv[16];
-  if (cc)
-    for (int pl = 0; pl < 2; ++pl) {
-      for (int q = 0; q < 4; ++q) lv[q] = cp[256 + 4 * pl + q];
-      cavlc_block<true>(&o, lv, 4, -1);
-    }
-  if (cc == 2)
-    for (int pl = 0; pl < 2; ++pl)
-      for (int k = 0; k < 4; ++k) {
-        const int bx = k & 1, by = k >> 1;
-        const int na = bx ? cnzc[pl][by * 2] : lnzc[pl][by], nb = by ? cnzc[pl][bx] : -1;
-        int tc = 0;
-        for (int q = 0; q < 15; ++q) {
-          lv[q] = cp[264 + 60 * pl + 15 * k + q];
-          tc += lv[q] != 0;
-        }
-        cavlc_block<true>(&o, lv, 15, nc_of(na, nb));
-        cnzc[pl][k] = tc;
-      }
-}
-
-// residual() of an Intra16x16 macroblock: Intra16x16DCLevel (nC of block 0),
-// the 16 Intra16x16ACLevel blocks when the luma coded_block_pattern is 15,
-// chroma.  The arguments as put_residual's.
-__device__ void put_intra_residual(NalOut &o, const int16_t *cp, int cbp, const int *lnz, const int (*lnzc)[2],
-                                   int *cnz, int (*cnzc)[4]) {
-  for (int i = 0; i < 16; ++i) cnz[i] = 0;
-  for (int i = 0; i < 4; ++i) cnzc[0][i] = cnzc[1][i] = 0;
-  int lv[16];
-  for (int q = 0; q < 16; ++q) lv[q] = cp[q];
-  cavlc_block<true>(&o, lv, 16, nc_of(lnz[0], -1));
-  if (cbp & 15)
-    for (int k = 0; k < 16; ++k) {
-      const int bx = kBlkXd[k], by = kBlkYd[k];
-      const int na = bx ? cnz[by * 4 + bx - 1] : lnz[by], nb = by ? cnz[(by - 1) * 4 + bx] : -1;
-      int tc = 0;
-      for (int q = 0; q < 15; ++q) {
-        lv[q] = cp[16 + 15 * k + q];
-        tc += lv[q] != 0;
-      }
-      cavlc_block<true>(&o, lv, 15, nc_of(na, nb));
-      cnz[by * 4 + bx] = tc;
-    }
-  put_chroma_residual(o, cp, cbp >> 4, lnzc, cnzc);
-}
-
-// residual() of an inter macroblock (7.3.5.3): cp the levels, cnz / cnzc
-// receive the blocks' total_coeff; lnz / lnzc the left macroblock's right
-// column (-1: unavailable; the macroblock above is another slice)
-__device__ void put_residual(NalOut &o, const int16_t *cp, int cbp, const int *lnz, const int (*lnzc)[2], int *cnz,
-                             int (*cnzc)[4]) {
-  for (int i = 0; i < 16; ++i) cnz[i] = 0;
-  for (int i = 0; i < 4; ++i) cnzc[0][i] = cnzc[1][i] = 0;
-  int lv[16];
-  for (int k = 0; k < 16; ++k) {
-    if (!((cbp >> (k >> 2)) & 1)) continue;
-    const int bx = kBlkXd[k], by = kBlkYd[k];
-    const int na = bx ? cnz[by * 4 + bx - 1] : lnz[by], nb = by ? cnz[(by - 1) * 4 + bx] : -1;
-    const int nC = (na >= 0 && nb >= 0) ? (na + nb + 1) >> 1 : (na >= 0 ? na : (nb >= 0 ? nb : 0));
-    int tc = 0;
-    for (int q = 0; q < 16; ++q) {
-      lv[q] = cp[16 * k + q];
-      tc += lv[q] != 0;
-    }
-    cavlc_block<true>(&o, lv, 16, nC);
-    cnz[by * 4 + bx] = tc;
-  }
-  if (cbp >> 4)
-    for (int pl = 0; pl < 2; ++pl) {
-      for (int q = 0; q < 4; ++q) lv[q] = cp[256 + 4 * pl + q];
-      cavlc_block<true>(&o, lv, 4, -1);
-    }
-  if ((cbp >> 4) == 2)
-    for (int pl = 0; pl < 2; ++pl)
-      for (int k = 0; k < 4; ++k) {
-        const int bx = k & 1, by = k >> 1;
-        const int na = bx ? cnzc[pl][by * 2] : lnzc[pl][by], nb = by ? cnzc[pl][bx] : -1;
-        const int nC = (na >= 0 && nb >= 0) ? (na + nb + 1) >> 1 : (na >= 0 ? na : (nb >= 0 ? nb : 0));
-        int tc = 0;
-        for (int q = 0; q < 15; ++q) {
-          lv[q] = cp[264 + 60 * pl + 15 * k + q];
-          tc += lv[q] != 0;
-        }
-        cavlc_block<true>(&o, lv, 15, nC);
-        cnzc[pl][k] = tc;
-      }
-}
-
 // I_PCM: pcm_alignment_zero_bits, then 384 sample bytes that enc_pcm fills in
 // later (the gap's bytes in the partial words either side are don't-care
 // here: enc_pcm runs after enc_gather).  The samples are >= 1 (downscale
@@ -1665,6 +1411,10 @@ __device__ void pcm_gap(NalOut &o, uint4 *job, int s, int mx) {
   o.zeros = 0;
 }
 
+// The CAVLC slices, one lane per slice: the header (enc_rbsp.h), then a
+// dispatch over enc_cavlc.h's macroblock kinds, which hold all the syntax and
+// the state a slice carries (ecav::Row); here are the counters, the I_PCM
+// jobs and the slot.
 // kIntra: enc_intra ran on every level, so IDR pictures have commands too and
 // a command may be kIntraCmd (the other instance is the encoder without it).
 // kDbk: the slices ask for the in-loop filter inside the slice (enc_deblock
@@ -1677,162 +1427,49 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   const int4 en = a.ent[e];
   const bool idr = en.y == 0;  // GOP position 0
   uint8_t *slot = a.staging + static_cast<int64_t>(s) * a.cap;
-  NalOut o{reinterpret_cast<uint32_t *>(slot + 4), a.cap - 4, 0, 0, 0, 0, 0, false};
-  o.put(idr ? 0x65 : 0x41);  // nal_ref_idc 3 IDR / 2 non-IDR; every picture is a reference
-  o.ue(static_cast<uint32_t>(row * a.mbw));  // first_mb_in_slice
-  o.ue(idr ? 7 : 5);                       // slice_type I / P (all slices of the picture)
-  o.ue(0);                                   // pic_parameter_set_id
-  o.bits(16, static_cast<uint32_t>(en.y) & 0xffffu);  // frame_num (16 bits)
-  if (idr) {
-    o.ue(static_cast<uint32_t>(en.z));       // idr_pic_id
-    o.bits(2, 0);                            // no_output_of_prior_pics, long_term_reference
-  } else {
-    o.bits(3, 0);  // num_ref_idx_active_override, ref_pic_list_modification_l0, adaptive_ref_pic_marking
-  }
-  o.se(a.qp >= 1 ? a.qp - 26 : 0);  // slice_qp_delta: SliceQPY = the residual's QP (pic_init_qp 26)
-  if constexpr (kDbk) {
-    o.ue(2);  // disable_deblocking_filter_idc: filtered, but not across slice boundaries
-    o.se(a.dbk_alpha);  // slice_alpha_c0_offset_div2
-    o.se(a.dbk_beta);   // slice_beta_offset_div2
-  } else {
-    o.ue(1);  // disable_deblocking_filter_idc
-  }
-  unsigned long long npcm = 0, ninter = 0, nskip = 0, nintra = 0;
-  uint32_t skip = 0;
-  bool a_ok = false;
-  int amx = 0, amy = 0;
+  NalOut o = full::erbsp::word_sink(reinterpret_cast<uint32_t *>(slot + 4), a.cap - 4);
+  // slice_qp_delta: SliceQPY = the residual's QP; every picture is a reference
+  full::erbsp::slice_header(o, false, idr, row * a.mbw, en.y, en.z, a.qp >= 1 ? a.qp - 26 : 0, kDbk, a.dbk_alpha, a.dbk_beta);
+  unsigned long long npcm = 0, ninter = 0, nskip = 0, nintra = 0, ni4 = 0;
   const uint32_t *cmd = a.cmd + static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw;
   const uint8_t *cbpr = a.cbp + static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw;
   const int16_t *coef_row =
       a.coef + ((static_cast<int64_t>(en.y % a.ring) * a.coef_per_level + en.w) * a.mbh + row) * a.mbw * kCoefPerMb;
-  // total_coeff of the left macroblock's right column for nC (9.2.1); -1 none
-  int lnz[4] = {-1, -1, -1, -1}, lnzc[2][2] = {{-1, -1}, {-1, -1}}, cnz[16], cnzc[2][4];
-  // I_NxN: the row's mode words; the last I_NxN macroblock's word and column (predIntra4x4PredMode's A)
   const uint64_t *i4r = kIntra && a.i4 ? a.i4 + static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw : nullptr;
-  uint64_t i4_left = ei4::kNoModes;
-  int i4_mx = -2;
-  unsigned long long ni4 = 0;
+  const bool all_pcm = idr && !kIntra;  // level 0 without intra holds no commands
   // reserve this slice's I_PCM jobs
   uint32_t njob = 0;
-  if (idr && !kIntra) {
+  if (all_pcm) {
     njob = static_cast<uint32_t>(a.mbw);
   } else {
     for (int mx = 0; mx < a.mbw; ++mx) njob += cmd[mx] == kPcmCmd;
   }
   uint4 *job = a.jobs + (njob ? atomicAdd(a.n_jobs, njob) : 0u);
+  ecav::Row z;
+  z.start();
   for (int mx = 0; mx < a.mbw; ++mx) {
-    if (idr && !kIntra) {
-      o.ue(25);
+    const uint32_t c = all_pcm ? kPcmCmd : cmd[mx];
+    const int16_t *cp = coef_row + static_cast<int64_t>(mx) * kCoefPerMb;
+    if (c == kPcmCmd) {
+      ecav::mb_pcm_head(o, idr, z);
       pcm_gap(o, job++, s, mx);
       ++npcm;
-      continue;
-    }
-    const uint32_t c = cmd[mx];
-    if (kIntra && ei4::is_i4_cmd(c)) {  // I_NxN (7.3.5, 7.3.5.1): mb_type 0, 5 in a P slice; no transform_size_8x8_flag
-      const int cbp = static_cast<int>(c >> 4) & 63;
-      if (!idr) {
-        o.ue(skip);
-        skip = 0;
-      }
-      o.ue(idr ? 0 : 5);
-      const uint64_t modes = i4r[mx], lw = i4_mx == mx - 1 ? i4_left : ei4::kNoModes;
-      for (int k = 0; k < 16; ++k) {
-        const int m = ei4::mode_at(modes, k), pm = ei4::pred_mode_of(k, modes, mx > 0, lw);
-        if (m == pm) o.bits(1, 1);  // prev_intra4x4_pred_mode_flag
-        else o.bits(4, static_cast<uint32_t>(ei4::rem_mode(m, pm)));  // the flag 0, rem_intra4x4_pred_mode
-      }
-      o.ue((c >> 2) & 3u);  // intra_chroma_pred_mode
-      o.ue(cbp_intra_code(cbp));
-      if (cbp) {
-        o.se(0);  // mb_qp_delta
-        put_residual(o, coef_row + static_cast<int64_t>(mx) * kCoefPerMb, cbp, lnz, lnzc, cnz, cnzc);
-      } else {
-        for (int i = 0; i < 16; ++i) cnz[i] = 0;
-        for (int i = 0; i < 4; ++i) cnzc[0][i] = cnzc[1][i] = 0;
-      }
-      for (int i = 0; i < 4; ++i) lnz[i] = cnz[i * 4 + 3];
-      for (int pl = 0; pl < 2; ++pl) {
-        lnzc[pl][0] = cnzc[pl][1];
-        lnzc[pl][1] = cnzc[pl][3];
-      }
-      a_ok = false;
-      i4_left = modes;
-      i4_mx = mx;
+    } else if (kIntra && ei4::is_i4_cmd(c)) {
+      ecav::mb_intra4(o, idr, z, c, i4r[mx], cp);
       ++nintra;
       ++ni4;
-      continue;
-    }
-    if (kIntra && is_intra_cmd(c)) {  // Intra16x16 (7.3.5, Table 7-11; 5 more in a P slice)
-      const int cbp = static_cast<int>(c >> 4) & 63;
-      const uint32_t mbt = 1 + (c & 3u) + 4 * static_cast<uint32_t>(cbp >> 4) + ((cbp & 15) ? 12 : 0);
-      if (!idr) {
-        o.ue(skip);
-        skip = 0;
-      }
-      o.ue(idr ? mbt : 5 + mbt);
-      o.ue((c >> 2) & 3u);  // intra_chroma_pred_mode
-      o.se(0);              // mb_qp_delta
-      put_intra_residual(o, coef_row + static_cast<int64_t>(mx) * kCoefPerMb, cbp, lnz, lnzc, cnz, cnzc);
-      for (int i = 0; i < 4; ++i) lnz[i] = cnz[i * 4 + 3];
-      for (int pl = 0; pl < 2; ++pl) {
-        lnzc[pl][0] = cnzc[pl][1];
-        lnzc[pl][1] = cnzc[pl][3];
-      }
-      a_ok = false;  // as after I_PCM: no motion to predict from
+    } else if (kIntra && is_intra_cmd(c)) {
+      ecav::mb_intra16(o, idr, z, c, cp);
       ++nintra;
-      continue;
-    }
-    if (c == kPcmCmd) {
-      if (!idr) {
-        o.ue(skip);
-        skip = 0;
-      }
-      o.ue(idr ? 25 : 30);  // I_PCM in an I / a P slice
-      pcm_gap(o, job++, s, mx);
-      a_ok = false;
-      ++npcm;
-      for (int i = 0; i < 4; ++i) lnz[i] = 16;
-      lnzc[0][0] = lnzc[0][1] = lnzc[1][0] = lnzc[1][1] = 16;
-      continue;
-    }
-    const int mvx = static_cast<int16_t>(c & 0xffffu), mvy = static_cast<int16_t>(c >> 16);
-    const int cbp = cbpr[mx];
-    if (mvx == 0 && mvy == 0 && cbp == 0) {  // P_Skip (neighbour B lies in another slice: skip motion is 0)
-      ++skip;
+    } else if (c == 0 && cbpr[mx] == 0) {  // P_Skip: vector (0, 0), nothing coded
+      ecav::mb_skip(z);
       ++nskip;
-      for (int i = 0; i < 4; ++i) lnz[i] = 0;
-      lnzc[0][0] = lnzc[0][1] = lnzc[1][0] = lnzc[1][1] = 0;
     } else {
-      const int px = a_ok ? amx : 0, py = a_ok ? amy : 0;  // 8.4.1.3, A the only neighbour
-      o.ue(skip);
-      skip = 0;
-      o.ue(0);  // P_L0_16x16
-      o.se(mvx - px);
-      o.se(mvy - py);
-      int code = 0;
-      while (kCbpInterTab[code] != cbp) ++code;
-      o.ue(static_cast<uint32_t>(code));  // coded_block_pattern me(v)
-      if (cbp) {
-        o.se(0);  // mb_qp_delta
-        put_residual(o, coef_row + static_cast<int64_t>(mx) * kCoefPerMb, cbp, lnz, lnzc, cnz, cnzc);
-      } else {
-        for (int i = 0; i < 16; ++i) cnz[i] = 0;
-        for (int i = 0; i < 4; ++i) cnzc[0][i] = cnzc[1][i] = 0;
-      }
-      for (int i = 0; i < 4; ++i) lnz[i] = cnz[i * 4 + 3];
-      for (int pl = 0; pl < 2; ++pl) {
-        lnzc[pl][0] = cnzc[pl][1];
-        lnzc[pl][1] = cnzc[pl][3];
-      }
+      ecav::mb_inter(o, z, c, cbpr[mx], cp);
       ++ninter;
     }
-    a_ok = true;
-    amx = mvx;
-    amy = mvy;
   }
-  if (skip) o.ue(skip);
-  o.bits(1, 1);  // rbsp_stop_one_bit
-  o.align();
+  ecav::slice_end(o, z);
   o.flush();
   const int64_t len = o.n;
   if (o.over) {
@@ -1893,7 +1530,7 @@ __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
     for (int off = 32; off > 0; off >>= 1) njob += __shfl_xor(njob, off);
   }
   uint8_t *slot = a.staging + static_cast<int64_t>(s) * a.cap;
-  NalOut o{reinterpret_cast<uint32_t *>(slot + 4), a.cap - 4, 0, 0, 0, 0, 0, false};
+  NalOut o = full::erbsp::word_sink(reinterpret_cast<uint32_t *>(slot + 4), a.cap - 4);
   ec::Encoder<NalOut> coder{&o, st, 0, 510, 0, true};
   ec::BinRing<NalOut> enc{&coder, ring, 0};
   ec::Left left = ec::left_none();
