@@ -1,5 +1,6 @@
 // session.h — the per-video device session (vts_ctx) shared by session.hip
-// (open / decode + score) and transcode.hip (360p upload transcode).
+// (open / decode + score), downscale.hip (the small store) and
+// transcode_driver.cpp (360p upload transcode).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -54,7 +55,7 @@ struct Window {
   std::vector<int32_t> dlv_early;
 };
 
-// Downscaled copy of every decoded frame (transcode.hip), filled by run_all
+// Downscaled copy of every decoded frame (downscale.hip), filled by run_all
 // after each window's reconstruction when `on`.
 struct SmallStore {
   bool on = false;
@@ -62,7 +63,7 @@ struct SmallStore {
   int cw = 0, ch = 0;           // coded size (16-aligned); NV12, pitch cw, UV at cw * ch
   int64_t stride = 0;           // bytes per frame
   uint8_t *d = nullptr;         // [frame]
-  int32_t *d_taps = nullptr;    // area-filter tap tables (transcode.hip area_taps)
+  int32_t *d_taps = nullptr;    // area-filter tap tables (downscale.hip area_taps)
   int64_t off[4] = {0, 0, 0, 0};  // luma x, luma y, chroma x, chroma y tables in d_taps
   int taps_x = 0, taps_y = 0, taps_cx = 0, taps_cy = 0;  // taps per output sample
   int32_t tl = 1, tc = 1;       // luma / chroma normalisers
@@ -266,6 +267,8 @@ int finish_general(vts_ctx *c);
 bool general_by_headers(const vts_ctx *c);
 bool wants_general(const vts_ctx *c, const uint8_t *es, const std::vector<int64_t> &es_off,
                    const std::vector<uint32_t> &sizes, int nal_length_size);
-// downscale the window's frames (transcode.hip)
+// the small store (downscale.hip): sized and allocated for output height sh
+// (kept when it already has that size); downscale the window's frames into it
+int setup_small(vts_ctx *c, int sh);
 int small_window(vts_ctx *c, int ring, int64_t f0, int64_t f1, hipStream_t s);
 }  // namespace vts

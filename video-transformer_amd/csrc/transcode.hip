@@ -1,15 +1,18 @@
-// transcode.hip — vts_transcode: the 360p upload transcode on the device
-// (replaces the pixel work of the reference's
+// transcode.hip — the kernels of vts_transcode, the 360p upload transcode on
+// the device (replaces the pixel work of the reference's
 // ContentAnalyzer._compress_video_for_upload, content_analyzer.py:167-236,
-// `ffmpeg -vf scale=-2:360 -c:v libx264 -crf 28`).  DESIGN.md §11.
+// `ffmpeg -vf scale=-2:360 -c:v libx264 -crf 28`), and one launch function per
+// stage (transcode.h).  The host driver that queues them is
+// transcode_driver.cpp, the downscale that feeds them downscale.hip.
+// DESIGN.md §11.
 //
 // Pipeline, all device work after the one decode:
 //   1. the session's decode + score run (run_all), with `small_window`
 //      downscaling every window's frames (area filter, NV12 -> NV12 at
 //      (w, 360), coded 16-aligned) into a whole-video store while they sit
 //      in the decode ring;
-//   2. GOP plan on the host: IDR at frame 0 and every `keyint` frames (and,
-//      opt-in, at every scene cut from the scores);
+//   2. GOP plan on the host (enc_plan.h): IDR at frame 0 and every `keyint`
+//      frames (and, opt-in, at every scene cut from the scores);
 //   3. per GOP position j ("level", every GOP at once, as the decoder's
 //      reconstruct levels): `enc_search` — one wave per macroblock, full
 //      integer motion search in LDS against the previous reconstruction
@@ -29,27 +32,19 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
-#include <cstring>
-#include <memory>
-#include <numeric>
-#include <string>
-#include <vector>
+#include <type_traits>
 
 #include "enc_cabac.h"
 #include "enc_cavlc.h"
 #include "enc_deblock.h"
 #include "enc_rate.h"
-#include "mp4.h"
 #include "recon_full.h"
-#include "session.h"
+#include "transcode.h"
 
 namespace vts {
 namespace {
 
 using full::edb::kPcmCmd;  // (mvx, mvy) = (-32768, -32768): never a motion (enc_deblock.h)
-constexpr int kMaxTaps = 16;
-constexpr int kMaxRange = 16;
 constexpr int kWinPitch = 16 + 2 * kMaxRange + 4;  // LDS window row pitch (bytes)
 // Sub-sample refinement (vts_transcode_ext.subpel): the window grows by the
 // 6-tap filter's reach around every integer candidate, 2 + 1 samples before
@@ -59,119 +54,6 @@ constexpr int kSpLoX = 4, kSpLoY = 3, kSpHi = 3;
 constexpr int kWinPitchSp = 16 + 2 * kMaxRange + 12;  // >= 4 ceil((16 + 2 R + kSpLoX + kSpHi) / 4), + a dword
 constexpr int kSpPitch = 20;                          // half-sample plane row pitch: 18 samples, 5 dwords
 
-// ----------------------------------------------------------- downscale
-// Area filter, per axis: destination o covers source footprint [o n, (o+1) n)
-// in units of 1/m; source i covers [i m, (i+1) m).  Tap table entry o =
-// [i0, w_0 .. w_{K-1}] (weights / gcd(n, m)); outputs past the display size
-// (coded padding) repeat the last display entry.
-struct DsArgs {
-  const uint8_t *src;      // ring surface of the window's first frame
-  int64_t src_stride;
-  int32_t pitch, uv_rows;  // UV plane at pitch * uv_rows
-  int32_t sw, sh;          // source display size
-  uint8_t *dst;            // small store, the window's first frame
-  int64_t dst_stride;
-  int32_t cw, ch;          // destination coded size
-  const int32_t *tx, *ty, *tcx, *tcy;
-  int32_t kx, ky, kcx, kcy;
-  int32_t tl, tc;          // normalisers (product of the axes' n / gcd)
-  int64_t n_frames;
-};
-
-__device__ __forceinline__ uint32_t area_px(const uint8_t *p, int pitch, int step, const int32_t *ex,
-                                            int kx, const int32_t *ey, int ky, int nx, int ny, int t) {
-  uint32_t sum = 0;
-  const int x0 = ex[0], y0 = ey[0];
-  for (int j = 0; j < ky; ++j) {
-    const uint32_t wy = static_cast<uint32_t>(ey[1 + j]);
-    if (!wy) continue;
-    const uint8_t *row = p + static_cast<int64_t>(min(y0 + j, ny - 1)) * pitch;
-    uint32_t s = 0;
-    for (int i = 0; i < kx; ++i) s += static_cast<uint32_t>(ex[1 + i]) * row[min(x0 + i, nx - 1) * step];
-    sum += wy * s;
-  }
-  const uint32_t v = (sum + static_cast<uint32_t>(t) / 2) / static_cast<uint32_t>(t);
-  return v < 1 ? 1u : v;
-}
-
-// Integer ratio K on both axes (720p -> 360p: 2, 1080p -> 360p: 3): four
-// outputs from K rows of 4K contiguous bytes, dword loads; luma and NV12
-// chroma (4 bytes U0 V0 U1 V1 from 2K source pairs) share the addressing.
-template <int K>
-__device__ __forceinline__ uint32_t box4(const uint8_t *p, int pitch, bool chroma) {
-  uint32_t acc[4] = {0, 0, 0, 0};
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    const uint32_t *r = reinterpret_cast<const uint32_t *>(p + static_cast<int64_t>(j) * pitch);
-#pragma unroll
-    for (int w = 0; w < K; ++w) {
-      const uint32_t v = r[w];
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const int byte = 4 * w + b;  // 0 .. 4K-1
-        // luma: output byte / K; chroma: pair byte / 2 -> output pair (pair / K), plane byte & 1
-        const int q = chroma ? 2 * ((byte >> 1) / K) + (byte & 1) : byte / K;
-        acc[q] += (v >> (8 * b)) & 255u;
-      }
-    }
-  }
-  uint32_t out = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const uint32_t m = (acc[q] + K * K / 2) / (K * K);
-    out |= (m < 1 ? 1u : m) << (8 * q);
-  }
-  return out;
-}
-
-template <int K>
-__global__ void __launch_bounds__(256) downscale_nv12(DsArgs a) {
-  const int groups = a.cw / 4;
-  const int64_t t = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
-  const int rows = a.ch + a.ch / 2;
-  if (t >= static_cast<int64_t>(groups) * rows) return;
-  const int64_t f = blockIdx.y;
-  const int g = static_cast<int>(t % groups), row = static_cast<int>(t / groups);
-  const uint8_t *src = a.src + f * a.src_stride;
-  uint8_t *dst = a.dst + f * a.dst_stride;
-  if constexpr (K > 0) {
-    const int dw = a.sw / K, dh = a.sh / K;  // output display size
-    if (row < dh && 4 * g + 3 < dw) {
-      *reinterpret_cast<uint32_t *>(dst + static_cast<int64_t>(row) * a.cw + 4 * g) =
-          box4<K>(src + static_cast<int64_t>(K * row) * a.pitch + 4 * K * g, a.pitch, false);
-      return;
-    }
-    if (row >= a.ch && row - a.ch < dh / 2 && 4 * g + 3 < dw) {
-      const int cy = row - a.ch;
-      const uint8_t *uv = src + static_cast<int64_t>(a.pitch) * a.uv_rows;
-      *reinterpret_cast<uint32_t *>(dst + static_cast<int64_t>(a.cw) * a.ch + static_cast<int64_t>(cy) * a.cw +
-                                    4 * g) = box4<K>(uv + static_cast<int64_t>(K * cy) * a.pitch + 4 * K * g, a.pitch, true);
-      return;
-    }
-  }
-  uint32_t out = 0;
-  if (row < a.ch) {
-    const int32_t *ey = a.ty + static_cast<int64_t>(row) * (1 + a.ky);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int32_t *ex = a.tx + static_cast<int64_t>(4 * g + q) * (1 + a.kx);
-      out |= area_px(src, a.pitch, 1, ex, a.kx, ey, a.ky, a.sw, a.sh, a.tl) << (8 * q);
-    }
-    *reinterpret_cast<uint32_t *>(dst + static_cast<int64_t>(row) * a.cw + 4 * g) = out;
-  } else {
-    const int cy = row - a.ch;
-    const uint8_t *uv = src + static_cast<int64_t>(a.pitch) * a.uv_rows;
-    const int32_t *ey = a.tcy + static_cast<int64_t>(cy) * (1 + a.kcy);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {  // bytes U0 V0 U1 V1 of chroma columns 2g, 2g+1
-      const int32_t *ex = a.tcx + static_cast<int64_t>(2 * g + (q >> 1)) * (1 + a.kcx);
-      out |= area_px(uv + (q & 1), a.pitch, 2, ex, a.kcx, ey, a.kcy, a.sw / 2, a.sh / 2, a.tc) << (8 * q);
-    }
-    *reinterpret_cast<uint32_t *>(dst + static_cast<int64_t>(a.cw) * a.ch + static_cast<int64_t>(cy) * a.cw +
-                                  4 * g) = out;
-  }
-}
-
 // ------------------------------------------------------ residual coding
 // Quantised residual of P_L0_16x16 macroblocks: the forward
 // core transform W = Cf X Cf^T, levels sign(W) min(2047, (|W| MF + f) >>
@@ -180,7 +62,6 @@ __global__ void __launch_bounds__(256) downscale_nv12(DsArgs a) {
 // transform (full::scale_idct4) for the reconstruction, and CAVLC
 // residual_block (9.2, enc_cavlc.h) for the bits.  Restated in
 // oracle/transcode_oracle.c.
-constexpr int kCoefPerMb = 384;  // luma 16 x 16 by luma4x4BlkIdx, Cb / Cr DC 2 x 4, Cb / Cr AC 8 x 15 (scan order)
 constexpr int kPcmBits = 3072;   // I_PCM payload: a residual bounded above it is not worth coding
 __device__ __constant__ static const uint8_t kZz4[16] = VTS_ZZ_DATA;
 __device__ __constant__ static const uint8_t kQpcTab[52] = VTS_QPC_DATA;
@@ -192,24 +73,6 @@ namespace ei4 = full::ei4;    // the Intra_4x4 decisions (enc_intra4.h)
 namespace ecav = full::ecav;  // the CAVLC slice writer and its bit counts (enc_cavlc.h)
 
 // ------------------------------------------------------ motion search
-struct SearchArgs {
-  const int4 *ent;      // per frame of the level: (frame, ref slot or -1 = small[frame-1], dst slot, 0)
-  const uint8_t *small;
-  int64_t stride;
-  uint8_t *recon;       // [slot]
-  uint32_t *cmd;        // [entry][mb]
-  uint8_t *cbp;         // [entry][mb] coded_block_pattern (residual coding)
-  int16_t *coef;        // [entry][mb][kCoefPerMb] levels (this level's ring slot)
-  int32_t cw, ch, mbw, nmb;
-  int32_t range, max_sad;
-  int32_t qp, rate;     // qp >= 1: residual coding at that QP; RC: bit 0 mvcost, bit 1 early_skip (enc_rate.h)
-  unsigned long long *sp_stats;  // SP > 0: inter macroblocks with a fractional vector: [0] no odd component, [1] one
-  // RC only
-  const uint32_t *cmd_prev;      // the previous level's final words [entry][mb]; ent[e].w = the GOP's entry there
-  int32_t gop_pos, lambda16;     // the level's GOP position j; lambda16 of the vector cost
-  unsigned long long *es_stat;   // macroblocks the early P_Skip probe decided
-};
-
 __device__ __forceinline__ uint32_t u32_at(const uint8_t *lds_row, int off) {  // 4 bytes at any offset
   const uint32_t *p = reinterpret_cast<const uint32_t *>(lds_row + (off & ~3));
   return __builtin_amdgcn_alignbyte(p[1], p[0], off & 3);  // byte shift
@@ -818,28 +681,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) en
 }
 
 // ------------------------------------------------------ slice writer
-struct WriteArgs {
-  const int4 *ent;      // per frame of the level: (frame, GOP position j, IDR parity, index within its level)
-  const uint32_t *cmd;  // [entry][mb] (P levels; with intra every level)
-  const uint8_t *cbp;   // [entry][mb] coded_block_pattern
-  const int16_t *coef;  // level ring: [ring slot][index within level][mb][kCoefPerMb]
-  int64_t coef_per_level;  // entries a ring slot holds
-  int32_t ring, qp;     // ring slots (levels); qp >= 1: residual coding (slice_qp_delta = qp - 26)
-  const uint8_t *small;
-  int64_t stride;
-  int32_t cw, ch, mbw, mbh;
-  uint8_t *staging;     // [slice][cap]
-  int64_t cap;
-  int32_t *sizes;       // [slice] bytes incl. the 4-byte length prefix
-  unsigned long long *stats;  // pcm, inter, skip, intra
-  uint32_t *err;
-  uint4 *jobs;          // I_PCM payloads left for enc_pcm: (slice, byte offset in the slot, mx, 0)
-  uint32_t *n_jobs;
-  int32_t n_slices;
-  int32_t dbk_alpha, dbk_beta, _pad;  // enc_write<., true>: slice_alpha_c0_offset_div2, slice_beta_offset_div2
-  const uint64_t *i4;   // [entry][mb] the Intra4x4PredModes of the I_NxN macroblocks (intra4x4; else unread)
-};
-
 // RBSP bits -> EBSP bytes into a staging slot, four bytes per (aligned) dword
 // store: slot payload (slot + 4), 4-byte aligned
 using NalOut = full::erbsp::WordSink;
@@ -858,21 +699,6 @@ using NalOut = full::erbsp::WordSink;
 // 2..3 intra_chroma_pred_mode, 4..9 coded_block_pattern (luma 0 or 15).
 using full::edb::kIntraCmd;
 using full::edb::is_intra_cmd;
-struct IntraArgs {
-  const int4 *ent;      // the level's search entries: (frame, -, dst slot, 0)
-  const uint8_t *small;
-  int64_t stride;
-  uint8_t *recon;       // [slot]
-  uint32_t *cmd;        // [entry][mb]
-  uint8_t *cbp;         // [entry][mb]
-  int16_t *coef;        // [entry][mb][kCoefPerMb] (this level's ring slot)
-  int32_t cw, ch, mbw, mbh;
-  int32_t qp;
-  int32_t all;          // 1: every macroblock is a candidate and dst is unwritten (level 0, the IDR
-                        // pictures); 0: the macroblocks enc_search left as kPcmCmd (dst holds the source)
-  uint64_t *i4;         // enc_intra<true>: [entry][mb] the Intra4x4PredModes of an I_NxN macroblock, else ~0
-};
-
 // kI4 (vts_transcode_ext5.intra4x4, DESIGN.md §11 "Intra4x4"): every
 // candidate macroblock is also tried as I_NxN with sixteen Intra_4x4 blocks,
 // and that is what it becomes when its CAVLC bits are strictly fewer than the
@@ -1243,17 +1069,6 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
 // (last two chroma pairs), bytes 4..19 this macroblock.  A macroblock ends
 // with one 16-byte store per row: the left macroblock's final columns 12..15
 // and this one's columns 0..11 (the next edge 0 still changes 13..15).
-struct DeblockArgs {
-  const int4 *ent;      // the level's search entries: (frame, -, dst slot, 0)
-  uint8_t *recon;       // [slot]
-  int64_t stride;
-  const uint32_t *cmd;  // [entry][mb]
-  const uint8_t *cbp;   // [entry][mb]
-  const int16_t *coef;  // [entry][mb][kCoefPerMb] (this level's ring slot)
-  int32_t cw, ch, mbw, mbh;
-  int32_t qp, off_a, off_b, _pad;  // SliceQPY, FilterOffsetA, FilterOffsetB
-  unsigned long long *count;       // macroblocks with a filtered line
-};
 constexpr int kDbPitch = 20;
 
 __global__ void __launch_bounds__(64) enc_deblock(DeblockArgs a) {
@@ -1479,11 +1294,11 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   }
   *reinterpret_cast<uint32_t *>(slot) = __builtin_bswap32(static_cast<uint32_t>(len));  // big-endian length
   a.sizes[s] = static_cast<int32_t>(len + 4);
-  atomicAdd(&a.stats[0], npcm);
-  atomicAdd(&a.stats[1], ninter);
-  atomicAdd(&a.stats[2], nskip);
-  if (nintra) atomicAdd(&a.stats[3], nintra);
-  if (ni4) atomicAdd(&a.stats[9], ni4);
+  atomicAdd(&a.stats[kStPcm], npcm);
+  atomicAdd(&a.stats[kStInter], ninter);
+  atomicAdd(&a.stats[kStSkip], nskip);
+  if (nintra) atomicAdd(&a.stats[kStIntra], nintra);
+  if (ni4) atomicAdd(&a.stats[kStI4], ni4);
 }
 
 // The slices with entropy_coding_mode_flag = 1 (vts_transcode_ext4.cabac,
@@ -1596,11 +1411,11 @@ __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
   }
   *reinterpret_cast<uint32_t *>(slot) = __builtin_bswap32(static_cast<uint32_t>(len));  // big-endian length
   a.sizes[s] = static_cast<int32_t>(len + 4);
-  atomicAdd(&a.stats[0], npcm);
-  atomicAdd(&a.stats[1], ninter);
-  atomicAdd(&a.stats[2], nskip);
-  if (nintra) atomicAdd(&a.stats[3], nintra);
-  if (ni4) atomicAdd(&a.stats[9], ni4);
+  atomicAdd(&a.stats[kStPcm], npcm);
+  atomicAdd(&a.stats[kStInter], ninter);
+  atomicAdd(&a.stats[kStSkip], nskip);
+  if (nintra) atomicAdd(&a.stats[kStIntra], nintra);
+  if (ni4) atomicAdd(&a.stats[kStI4], ni4);
 }
 
 // Slice offsets of one level on the device: offs[s] = running output total +
@@ -1682,754 +1497,87 @@ __global__ void __launch_bounds__(64) enc_pcm(const uint4 *jobs, const uint32_t 
   }
 }
 
-// ------------------------------------------------------------ host
-int64_t gcd64(int64_t a, int64_t b) {
-  while (b) {
-    const int64_t t = a % b;
-    a = b;
-    b = t;
-  }
-  return a;
-}
 
-// tap table for n source -> m destination samples over `coded` outputs
-std::vector<int32_t> area_taps(int64_t n, int64_t m, int coded, int *k_out, int32_t *t_out) {
-  const int64_t g = gcd64(n, m);
-  int k = 1;
-  for (int64_t o = 0; o < m; ++o) {
-    const int64_t i0 = o * n / m, i1 = ((o + 1) * n + m - 1) / m;
-    k = std::max<int>(k, static_cast<int>(i1 - i0));
+// f(std::integral_constant<int, V>{}) for the V that equals v; the last V
+// stands for every other value.  The launch functions below pick their
+// kernel's instance with it, so that each set of instances is written once.
+template <int V, int... Rest, class F>
+void with_const(int v, F &&f) {
+  if constexpr (sizeof...(Rest) == 0) {
+    f(std::integral_constant<int, V>{});
+  } else {
+    if (v == V) f(std::integral_constant<int, V>{});
+    else with_const<Rest...>(v, f);
   }
-  std::vector<int32_t> t(static_cast<size_t>(coded) * (1 + k), 0);
-  for (int x = 0; x < coded; ++x) {
-    const int64_t o = std::min<int64_t>(x, m - 1);
-    const int64_t i0 = o * n / m;
-    int32_t *e = &t[static_cast<size_t>(x) * (1 + k)];
-    e[0] = static_cast<int32_t>(i0);
-    for (int i = 0; i < k; ++i) {
-      const int64_t si = i0 + i;
-      const int64_t lo = std::max(o * n, si * m), hi = std::min((o + 1) * n, (si + 1) * m);
-      e[1 + i] = (si < n && hi > lo) ? static_cast<int32_t>((hi - lo) / g) : 0;
-    }
-  }
-  *k_out = k;
-  *t_out = static_cast<int32_t>(n / g);
-  return t;
-}
-
-template <class T>
-int dev_alloc(T **p, size_t n) {
-  HIP_TRY(vts::dmalloc(reinterpret_cast<void **>(p), std::max<size_t>(1, n) * sizeof(T)));
-  return VTS_OK;
-}
-
-// Transcode scratch, freed on every exit path.  vts::dfree hands a range
-// straight back to the process-wide cache (no implicit device synchronisation
-// as with hipFree), so the streams whose kernels may still use the buffers
-// are drained first: an early return after the searches were queued must not
-// let a later allocation reuse memory those kernels still write.
-struct DevBufs {
-  std::vector<void *> ptrs;
-  std::vector<hipStream_t> streams;  // synchronised before anything is freed
-  template <class T>
-  int get(T **p, size_t n) {
-    VTS_TRY(dev_alloc(p, n));
-    ptrs.push_back(*p);
-    return VTS_OK;
-  }
-  ~DevBufs() {
-    for (hipStream_t s : streams) (void)hipStreamSynchronize(s);
-    for (void *p : ptrs) vts::dfree(p);
-  }
-};
-
-int setup_small(vts_ctx *c, int sh) {
-  SmallStore &S = c->small;
-  const int W = c->width, H = c->height;
-  const int sw = static_cast<int>((static_cast<int64_t>(sh) * W + H) / (2 * static_cast<int64_t>(H))) * 2;
-  if (sw < 2) return fail(VTS_E_INVALID, "output width %d from %dx%d at height %d", sw, W, H, sh);
-  if (S.d && S.w == sw && S.h == sh) return VTS_OK;
-  if (S.d) vts::dfree(S.d);
-  if (S.d_taps) vts::dfree(S.d_taps);
-  S = SmallStore{};
-  S.w = sw;
-  S.h = sh;
-  S.cw = (sw + 15) & ~15;
-  S.ch = (sh + 15) & ~15;
-  S.stride = (static_cast<int64_t>(S.cw) * S.ch * 3 / 2 + 255) & ~int64_t(255);
-  int32_t tl_x, tl_y, tc_x, tc_y;
-  const auto tx = area_taps(W, sw, S.cw, &S.taps_x, &tl_x);
-  const auto ty = area_taps(H, sh, S.ch, &S.taps_y, &tl_y);
-  const auto tcx = area_taps(W / 2, sw / 2, S.cw / 2, &S.taps_cx, &tc_x);
-  const auto tcy = area_taps(H / 2, sh / 2, S.ch / 2, &S.taps_cy, &tc_y);
-  if (std::max({S.taps_x, S.taps_y, S.taps_cx, S.taps_cy}) > kMaxTaps)
-    return fail(VTS_E_UNSUPPORTED, "downscale ratio %dx%d -> %dx%d needs more than %d taps", W, H, sw, sh,
-                kMaxTaps);
-  if (static_cast<int64_t>(tl_x) * tl_y * 255 > 0x7fffffffll || static_cast<int64_t>(tc_x) * tc_y * 255 > 0x7fffffffll)
-    return fail(VTS_E_UNSUPPORTED, "downscale ratio %dx%d -> %dx%d overflows 32-bit sums", W, H, sw, sh);
-  S.tl = tl_x * tl_y;
-  S.tc = tc_x * tc_y;
-  std::vector<int32_t> all;
-  S.off[0] = 0;
-  for (const auto *v : {&tx, &ty, &tcx, &tcy}) {
-    all.insert(all.end(), v->begin(), v->end());
-  }
-  S.off[1] = static_cast<int64_t>(tx.size());
-  S.off[2] = S.off[1] + static_cast<int64_t>(ty.size());
-  S.off[3] = S.off[2] + static_cast<int64_t>(tcx.size());
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(vts::dmalloc(&S.d_taps, all.size() * sizeof(int32_t)));
-  HIP_TRY(hipMemcpy(S.d_taps, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  const size_t bytes = static_cast<size_t>(S.stride * c->n_frames + 256);
-  if (vts::dmalloc(&S.d, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    S.d = nullptr;
-    return fail(VTS_E_HIP, "cannot allocate %.1f GiB for the %dx%d frames", bytes / 1073741824.0, sw, sh);
-  }
-  return VTS_OK;
 }
 
 }  // namespace
 
-int small_window(vts_ctx *c, int ring, int64_t f0, int64_t f1, hipStream_t s) {
-  const SmallStore &S = c->small;
-  DsArgs a{};
-  a.src = c->d_surf[ring];
-  a.src_stride = c->frame_stride;
-  a.pitch = c->pitch;
-  a.uv_rows = c->coded_h;
-  a.sw = c->width;
-  a.sh = c->height;
-  a.dst = S.d + f0 * S.stride;
-  a.dst_stride = S.stride;
-  a.cw = S.cw;
-  a.ch = S.ch;
-  a.tx = S.d_taps + S.off[0];
-  a.ty = S.d_taps + S.off[1];
-  a.tcx = S.d_taps + S.off[2];
-  a.tcy = S.d_taps + S.off[3];
-  a.kx = S.taps_x;
-  a.ky = S.taps_y;
-  a.kcx = S.taps_cx;
-  a.kcy = S.taps_cy;
-  a.tl = S.tl;
-  a.tc = S.tc;
-  a.n_frames = f1 - f0;
-  const int64_t threads = static_cast<int64_t>(S.cw / 4) * (S.ch + S.ch / 2);
-  // integer ratio on both axes (equal): the dword box path; else the tap tables
-  const int W = c->width, H = c->height;
-  const int k = (W % S.w == 0 && H % S.h == 0 && W / S.w == H / S.h) ? W / S.w : 0;
-  for (int64_t g0 = 0; g0 < f1 - f0; g0 += 65535) {  // grid.y <= 65535 frames per launch
-    DsArgs b = a;
-    b.src = a.src + g0 * a.src_stride;
-    b.dst = a.dst + g0 * a.dst_stride;
-    b.n_frames = std::min<int64_t>(65535, f1 - f0 - g0);
-    const dim3 grid(static_cast<unsigned>((threads + 255) / 256), static_cast<unsigned>(b.n_frames));
-    switch (k) {
-      case 2: hipLaunchKernelGGL(downscale_nv12<2>, grid, dim3(256), 0, s, b); break;
-      case 3: hipLaunchKernelGGL(downscale_nv12<3>, grid, dim3(256), 0, s, b); break;
-      case 4: hipLaunchKernelGGL(downscale_nv12<4>, grid, dim3(256), 0, s, b); break;
-      default: hipLaunchKernelGGL(downscale_nv12<0>, grid, dim3(256), 0, s, b); break;
-    }
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(VTS_E_HIP, "downscale_nv12 launch: %s", hipGetErrorString(e));
-  return VTS_OK;
+// ------------------------------------------------------------ launches
+static_assert(kPcmCmdWord == kPcmCmd && kNoI4Modes == ei4::kNoModes, "transcode.h restates the kernels' two words");
+
+// An I_PCM macroblock is < 400 bytes, and so is an inter one (its residual is
+// coded only under a 3072-bit bound); the rest is headroom for emulation
+// prevention bytes in residual data.  With cabac the decisions are still
+// bounded in CAVLC bits, which bounds no CABAC length: the slot holds the
+// worst case of the bins themselves (full::ecab::kMbBytes, derived there; the
+// larger of the two bounds)
+int64_t slice_slot_bytes(int mbw, bool cabac) {
+  return ((64 + static_cast<int64_t>(mbw) * (cabac ? std::max(600, full::ecab::kMbBytes) : 600)) + 255) & ~int64_t(255);
 }
 
-namespace {
-template <int SP, bool RC>
-void launch_search(int R, dim3 grid, hipStream_t s, const SearchArgs &sa) {
-  switch (R) {
-    case 4: hipLaunchKernelGGL((enc_search<4, SP, RC>), grid, dim3(64), 0, s, sa); break;
-    case 8: hipLaunchKernelGGL((enc_search<8, SP, RC>), grid, dim3(64), 0, s, sa); break;
-    case 16: hipLaunchKernelGGL((enc_search<16, SP, RC>), grid, dim3(64), 0, s, sa); break;
-    default: hipLaunchKernelGGL((enc_search<0, SP, RC>), grid, dim3(64), 0, s, sa); break;
-  }
+int32_t search_lambda16(int qp, int mv_lambda16) { return er::lambda16(qp, mv_lambda16); }
+
+// one wave per macroblock; RT: the range compiled in (0: any), SP: subpel,
+// RC: the instances with the rate-aware decisions compiled in
+void launch_enc_search(const SearchArgs &a, int subpel, bool rate_aware, int64_t entries, hipStream_t s) {
+  const dim3 grid(static_cast<unsigned>(entries * a.nmb));
+  with_const<4, 8, 16, 0>(a.range, [&](auto rt) {
+    with_const<1, 2, 0>(subpel, [&](auto sp) {
+      with_const<1, 0>(rate_aware, [&](auto rc) {
+        hipLaunchKernelGGL((enc_search<rt(), sp(), rc() != 0>), grid, dim3(64), 0, s, a);
+      });
+    });
+  });
 }
 
-// What a vts_transcode_ex call asks for, defaults applied and checked.
-struct TranscodeOpts {
-  int subpel = 0, deblock = 0, dbk_alpha = 0, dbk_beta = 0;
-  int mvcost = 0, mv_lambda16 = 0, early_skip = 0;
-  int cabac = 0;
-  int intra4x4 = 0;
-  uint32_t *cmd_out = nullptr;
-  int64_t cmd_cap = 0;
-  uint64_t *i4_out = nullptr;
-  int64_t i4_cap = 0;
-  int rate = 0;         // SearchArgs.rate: mvcost | early_skip << 1
-  int sh = 0, R = 0, T = 0, qp = 0, keyint = 0;  // output height, search range, max SAD, residual QP (0: none)
-  bool intra = false, idr_at_cuts = false;
-  bool hashed = false;  // recon_hash is computed
-  float thr = 0;        // scene-cut threshold of idr_at_cuts
-};
-// The size-tagged structs (only the prefix known here is read) and the
-// parameters into `o`; VTS_OK or the error
-int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_transcode_ext *ext,
-              const vts_transcode_ext_info *xinfo, TranscodeOpts *out) {
-  TranscodeOpts &o = *out;
-  if (ext) {
-    if (ext->struct_size < 8) return fail(VTS_E_INVALID, "vts_transcode_ext.struct_size %u < 8", ext->struct_size);
-    o.subpel = ext->subpel;
-    if (o.subpel < 0 || o.subpel > 2) return fail(VTS_E_INVALID, "subpel %d: 0, 1 or 2", o.subpel);
-    // vts_transcode_ext2: each field only when the caller's struct holds it
-    const vts_transcode_ext2 *x2 = reinterpret_cast<const vts_transcode_ext2 *>(ext);
-    if (ext->struct_size >= 12) o.deblock = x2->deblock;
-    if (ext->struct_size >= 16) o.dbk_alpha = x2->deblock_alpha;
-    if (ext->struct_size >= 20) o.dbk_beta = x2->deblock_beta;
-    if (o.deblock != 0 && o.deblock != 1) return fail(VTS_E_INVALID, "deblock %d: 0 or 1", o.deblock);
-    if (o.dbk_alpha < -6 || o.dbk_alpha > 6) return fail(VTS_E_INVALID, "deblock_alpha %d: -6 .. 6", o.dbk_alpha);
-    if (o.dbk_beta < -6 || o.dbk_beta > 6) return fail(VTS_E_INVALID, "deblock_beta %d: -6 .. 6", o.dbk_beta);
-    if (!o.deblock && o.dbk_alpha) return fail(VTS_E_INVALID, "deblock_alpha %d without deblock = 1", o.dbk_alpha);
-    if (!o.deblock && o.dbk_beta) return fail(VTS_E_INVALID, "deblock_beta %d without deblock = 1", o.dbk_beta);
-    // vts_transcode_ext3, the same way
-    const vts_transcode_ext3 *x3 = reinterpret_cast<const vts_transcode_ext3 *>(ext);
-    if (ext->struct_size >= 28) o.mvcost = x3->mvcost;
-    if (ext->struct_size >= 32) o.mv_lambda16 = x3->mv_lambda16;
-    if (ext->struct_size >= 36) o.early_skip = x3->early_skip;
-    if (ext->struct_size >= 48) o.cmd_out = x3->cmd_out;
-    if (ext->struct_size >= 56) o.cmd_cap = x3->cmd_cap;
-    if (o.mvcost != 0 && o.mvcost != 1) return fail(VTS_E_INVALID, "mvcost %d: 0 or 1", o.mvcost);
-    if (o.early_skip != 0 && o.early_skip != 1) return fail(VTS_E_INVALID, "early_skip %d: 0 or 1", o.early_skip);
-    if (o.mv_lambda16 < 0 || o.mv_lambda16 > 4096) return fail(VTS_E_INVALID, "mv_lambda16 %d: 0 .. 4096", o.mv_lambda16);
-    if (!o.mvcost && o.mv_lambda16) return fail(VTS_E_INVALID, "mv_lambda16 %d without mvcost = 1", o.mv_lambda16);
-    // vts_transcode_ext4, the same way
-    if (ext->struct_size >= 60) o.cabac = reinterpret_cast<const vts_transcode_ext4 *>(ext)->cabac;
-    if (o.cabac != 0 && o.cabac != 1) return fail(VTS_E_INVALID, "cabac %d: 0 or 1", o.cabac);
-    // vts_transcode_ext5, the same way
-    const vts_transcode_ext5 *x5 = reinterpret_cast<const vts_transcode_ext5 *>(ext);
-    if (ext->struct_size >= 68) o.intra4x4 = x5->intra4x4;
-    if (ext->struct_size >= 80) o.i4_out = x5->i4_out;
-    if (ext->struct_size >= 88) o.i4_cap = x5->i4_cap;
-    if (o.intra4x4 != 0 && o.intra4x4 != 1) return fail(VTS_E_INVALID, "intra4x4 %d: 0 or 1", o.intra4x4);
-  }
-  o.rate = o.mvcost | (o.early_skip << 1);
-  if (xinfo && xinfo->struct_size < 8)
-    return fail(VTS_E_INVALID, "vts_transcode_ext_info.struct_size %u < 8", xinfo->struct_size);
-  vts_transcode_params p{};
-  if (pin) p = *pin;
-  o.sh = p.height > 0 ? p.height : 360;
-  o.R = p.search_range == 0 ? 8 : std::max(0, p.search_range);
-  o.T = p.max_mb_sad == 0 ? 1536 : p.max_mb_sad;
-  o.qp = p.qp == 0 ? 28 : (p.qp < 0 ? 0 : p.qp);  // 0: no residual coding (the round-2 encoder)
-  if (o.qp > 51) return fail(VTS_E_INVALID, "qp %d > 51", o.qp);
-  if (p.intra != 0 && p.intra != 1) return fail(VTS_E_INVALID, "intra %d: 0 or 1", p.intra);
-  o.intra = p.intra == 1;
-  o.hashed = o.intra || o.subpel != 0 || o.deblock || o.rate;
-  if (o.intra4x4 && o.qp < 1) return fail(VTS_E_INVALID, "intra4x4 = 1 needs residual coding (qp >= 0)");
-  if (o.intra4x4 && !o.intra) return fail(VTS_E_INVALID, "intra4x4 = 1 needs intra = 1");
-  if (o.intra && o.qp < 1) return fail(VTS_E_INVALID, "intra = 1 needs residual coding (qp >= 0)");
-  if (o.deblock && o.qp < 1) return fail(VTS_E_INVALID, "deblock = 1 needs residual coding (qp >= 0)");
-  if (o.mvcost && o.qp < 1) return fail(VTS_E_INVALID, "mvcost = 1 needs residual coding (qp >= 0)");
-  if (o.early_skip && o.qp < 1) return fail(VTS_E_INVALID, "early_skip = 1 needs residual coding (qp >= 0)");
-  if (o.cabac && o.qp < 1) return fail(VTS_E_INVALID, "cabac = 1 needs residual coding (qp >= 0)");
-  o.keyint = p.keyint > 0 ? p.keyint : 250;
-  o.idr_at_cuts = p.idr_at_cuts != 0;
-  o.thr = p.cut_threshold > 0 ? p.cut_threshold : c->params.cut_threshold;
-  if ((o.sh & 1) || o.sh < 16 || o.sh > c->height)
-    return fail(VTS_E_INVALID, "output height %d: even, 16 .. source height %d", o.sh, c->height);
-  if (o.R > kMaxRange) return fail(VTS_E_INVALID, "search_range %d > %d", o.R, kMaxRange);
-  return VTS_OK;
+// one wave per (entry, macroblock row)
+void launch_enc_intra(const IntraArgs &a, bool intra4x4, int64_t entries, hipStream_t s) {
+  with_const<1, 0>(intra4x4, [&](auto i4) {
+    hipLaunchKernelGGL(enc_intra<i4() != 0>, dim3(static_cast<unsigned>(entries * a.mbh)), dim3(64), 0, s, a);
+  });
 }
 
-// The GOPs (IDR at frame 0, at cuts, every keyint frames) and their levels:
-// level j holds position j of every GOP that long, as search entries (frame,
-// ref slot, dst slot, w) and write entries (frame, j, idr parity, index within
-// the level); level j's entries are [lvl_off[j], lvl_off[j + 1]).
-struct GopPlan {
-  std::vector<int64_t> gop_start;
-  int64_t ngop = 0, maxlen = 0;  // GOPs; frames of the longest = levels
-  std::vector<int4> sent, went;
-  std::vector<int64_t> lvl_off;
-};
-GopPlan plan_gops(int64_t n, const std::vector<float> &scores, const TranscodeOpts &o) {
-  GopPlan g;
-  for (int64_t f = 0; f < n; ++f)
-    if (f == 0 || (o.idr_at_cuts && scores[f] > o.thr) || f - g.gop_start.back() >= o.keyint) g.gop_start.push_back(f);
-  g.ngop = static_cast<int64_t>(g.gop_start.size());
-  std::vector<int64_t> gop_len(static_cast<size_t>(g.ngop));
-  for (int64_t k = 0; k < g.ngop; ++k) {
-    gop_len[k] = (k + 1 < g.ngop ? g.gop_start[k + 1] : n) - g.gop_start[k];
-    g.maxlen = std::max(g.maxlen, gop_len[k]);
-  }
-  g.lvl_off.assign(static_cast<size_t>(g.maxlen) + 1, 0);
-  // with a rate-aware search, w of a search entry: the GOP's entry index in the previous level (GOPs of
-  // different lengths: the indices differ between levels), where enc_search finds the previous picture's words
-  std::vector<int> lvl_idx(static_cast<size_t>(g.ngop), 0);
-  for (int64_t j = 0; j < g.maxlen; ++j) {
-    g.lvl_off[j] = static_cast<int64_t>(g.went.size());
-    for (int64_t k = 0; k < g.ngop; ++k) {
-      if (gop_len[k] <= j) continue;
-      const int f = static_cast<int>(g.gop_start[k] + j);
-      const int prev_idx = o.rate ? lvl_idx[k] : 0;
-      lvl_idx[k] = static_cast<int>(static_cast<int64_t>(g.went.size()) - g.lvl_off[j]);
-      // level 1 predicts from the IDR picture: its source (all I_PCM) or, with intra, its reconstruction
-      g.sent.push_back(make_int4(f, j == 1 && !o.intra ? -1 : static_cast<int>(2 * k + ((j - 1) & 1)),
-                                 static_cast<int>(2 * k + (j & 1)), prev_idx));
-      g.went.push_back(make_int4(f, static_cast<int>(j), static_cast<int>(k & 1), lvl_idx[k]));
-    }
-  }
-  g.lvl_off[g.maxlen] = static_cast<int64_t>(g.went.size());
-  return g;
+void launch_enc_deblock(const DeblockArgs &a, int64_t entries, hipStream_t s) {
+  hipLaunchKernelGGL(enc_deblock, dim3(static_cast<unsigned>(entries * a.mbh)), dim3(64), 0, s, a);
 }
-}  // namespace
+
+// up to 64 workgroups share a picture, 4096 bytes each
+void launch_enc_hash(const HashArgs &a, int64_t entries, hipStream_t s) {
+  const int hb = std::max(1, std::min(64, (a.w * a.h * 3 / 2 + 4095) / 4096));
+  hipLaunchKernelGGL(enc_hash, dim3(static_cast<unsigned>(hb * entries)), dim3(256), 0, s, a.ent, a.pics, a.stride, a.cw,
+                     a.ch, a.w, a.h, hb, a.acc);
+}
+
+// a.n_slices slices: CAVLC one lane per slice, CABAC one wave per slice
+void launch_enc_write(const WriteArgs &a, bool cabac, bool intra, bool deblock, hipStream_t s) {
+  const unsigned ns = static_cast<unsigned>(a.n_slices);
+  with_const<1, 0>(intra, [&](auto in) {
+    with_const<1, 0>(deblock, [&](auto db) {
+      if (cabac) hipLaunchKernelGGL((enc_write_cabac<in() != 0, db() != 0>), dim3(ns), dim3(64), 0, s, a);
+      else hipLaunchKernelGGL((enc_write<in() != 0, db() != 0>), dim3((ns + 63) / 64), dim3(64), 0, s, a);
+    });
+  });
+}
+
+void launch_enc_pack(const PackArgs &a, int64_t entries, int32_t nmb, hipStream_t s) {
+  const int ns = static_cast<int>(entries * a.mbh);
+  hipLaunchKernelGGL(enc_scan, dim3(1), dim3(1024), 0, s, a.sizes, ns, a.ent, a.mbh, a.offs, a.total, a.fr_off,
+                     a.fr_size);
+  hipLaunchKernelGGL(enc_gather, dim3(static_cast<unsigned>(ns)), dim3(256), 0, s, a.staging, a.cap, a.sizes, a.offs,
+                     a.base, a.out);
+  hipLaunchKernelGGL(enc_pcm, dim3(static_cast<unsigned>(std::min<int64_t>(16384, entries * nmb))), dim3(64), 0, s,
+                     a.jobs, a.n_jobs, a.ent, a.small, a.stride, a.cw, a.ch, a.mbh, a.offs, a.base, a.out);
+}
 
 }  // namespace vts
-
-using namespace vts;
-
-extern "C" int vts_transcode(vts_ctx *c, const char *out_path, const vts_transcode_params *pin,
-                             vts_transcode_info *info) {
-  return vts_transcode_ex(c, out_path, pin, nullptr, info, nullptr);
-}
-
-extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_transcode_params *pin,
-                                const vts_transcode_ext *ext, vts_transcode_info *info,
-                                vts_transcode_ext_info *xinfo) {
-  clear_error();
-  if (!c || !out_path) return fail(VTS_E_INVALID, "NULL argument");
-  TranscodeOpts opt;
-  VTS_TRY(read_opts(c, pin, ext, xinfo, &opt));
-  using clk = std::chrono::steady_clock;
-  // constant frame rate (the writer's stts is one entry)
-  const int64_t n = c->n_frames;
-  int64_t delta = n > 1 ? c->pts[1] - c->pts[0] : std::max<int64_t>(1, c->info.track_timescale / 30);
-  for (int64_t i = 1; i < n; ++i)
-    if (c->pts[i] - c->pts[i - 1] != delta)
-      return fail(VTS_E_UNSUPPORTED, "variable frame rate (frame %lld) is not transcoded",
-                  static_cast<long long>(i));
-  HIP_TRY(hipSetDevice(c->device));
-  VTS_TRY(setup_small(c, opt.sh));
-  const SmallStore &S = c->small;
-  const int mbw = S.cw / 16, mbh = S.ch / 16, nmb = mbw * mbh;
-  double ms[4] = {0, 0, 0, 0};
-  // the command words of every macroblock, [frame][my][mx]: reported always, copied out when asked
-  const int64_t cmd_words = c->n_frames * nmb;
-  if (xinfo && xinfo->struct_size >= 48) reinterpret_cast<vts_transcode_ext_info3 *>(xinfo)->cmd_words = cmd_words;
-  if (opt.cmd_out && opt.cmd_cap < cmd_words)
-    return fail(VTS_E_CAPACITY, "cmd_cap %lld < %lld command words", static_cast<long long>(opt.cmd_cap),
-                static_cast<long long>(cmd_words));
-  // the Intra4x4PredModes word of every macroblock, the same way
-  if (xinfo && xinfo->struct_size >= 64) reinterpret_cast<vts_transcode_ext_info4 *>(xinfo)->i4_words = cmd_words;
-  if (opt.i4_out && opt.i4_cap < cmd_words)
-    return fail(VTS_E_CAPACITY, "i4_cap %lld < %lld mode words", static_cast<long long>(opt.i4_cap),
-                static_cast<long long>(cmd_words));
-
-  // 1. decode + score + downscale
-  auto t0 = clk::now();
-  c->small.on = true;
-  const int rc = run_all(c);
-  c->small.on = false;
-  VTS_TRY(rc);
-  VTS_TRY(fetch_scores(c));
-  ms[0] = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-
-  // 2. GOPs and their levels
-  const GopPlan plan = plan_gops(n, c->host_scores, opt);
-
-  // 3. device encode, level by level
-  // staging slot per slice: an I_PCM macroblock is < 400 bytes, and so is an
-  // inter one (its residual is coded only under a 3072-bit bound); the rest
-  // is headroom for emulation prevention bytes in residual data.  With cabac
-  // the decisions are still bounded in CAVLC bits, which bounds no CABAC
-  // length: the slot holds the worst case of the bins themselves
-  // (full::ecab::kMbBytes, derived there; the larger of the two bounds)
-  const int64_t cap =
-      ((64 + static_cast<int64_t>(mbw) * (opt.cabac ? std::max(600, full::ecab::kMbBytes) : 600)) + 255) & ~int64_t(255);
-  DevBufs B;
-  int4 *d_sent, *d_went;
-  uint8_t *d_recon, *d_stage, *d_out;
-  uint32_t *d_cmd, *d_err;
-  int32_t *d_sizes;
-  int64_t *d_offs;
-  unsigned long long *d_stats;
-  VTS_TRY(B.get(&d_sent, plan.sent.size()));
-  VTS_TRY(B.get(&d_went, plan.went.size()));
-  VTS_TRY(B.get(&d_recon, static_cast<size_t>(2 * plan.ngop * S.stride + 256)));
-  VTS_TRY(B.get(&d_cmd, static_cast<size_t>(plan.went.size()) * nmb));  // every frame: searches run ahead
-  uint8_t *d_cbp;
-  VTS_TRY(B.get(&d_cbp, static_cast<size_t>(plan.went.size()) * nmb));
-  // intra4x4: the mode word of every macroblock, [entry][mb] as the command words; ~0 where enc_intra<true>
-  // writes none (a macroblock that enc_search coded)
-  uint64_t *d_i4 = nullptr;
-  if (opt.intra4x4) VTS_TRY(B.get(&d_i4, static_cast<size_t>(plan.went.size()) * nmb));
-  // residual levels: a ring of kRing levels (the searches run at most kRing
-  // levels ahead of the slice writing that reads them)
-  constexpr int64_t kRing = 32;
-  int16_t *d_coef = nullptr;
-  if (opt.qp >= 1) VTS_TRY(B.get(&d_coef, static_cast<size_t>(kRing * plan.ngop * nmb * kCoefPerMb)));
-  constexpr int64_t kChunkLevels = 16;  // levels written and drained together
-  int64_t max_chunk = 0;                 // entries of the largest chunk
-  for (int64_t j0 = 0; j0 < plan.maxlen; j0 += kChunkLevels)
-    max_chunk = std::max(max_chunk, plan.lvl_off[std::min(plan.maxlen, j0 + kChunkLevels)] - plan.lvl_off[j0]);
-  VTS_TRY(B.get(&d_stage, static_cast<size_t>(max_chunk * mbh * cap)));
-  VTS_TRY(B.get(&d_out, static_cast<size_t>(max_chunk * mbh * cap)));
-  int64_t *d_total, *d_base, *d_fr;
-  VTS_TRY(B.get(&d_total, 1));
-  VTS_TRY(B.get(&d_base, 1));
-  VTS_TRY(B.get(&d_fr, static_cast<size_t>(2 * n)));  // per frame: absolute offset, size
-  VTS_TRY(B.get(&d_sizes, static_cast<size_t>(max_chunk * mbh)));
-  VTS_TRY(B.get(&d_offs, static_cast<size_t>(max_chunk * mbh)));
-  // pcm, inter, skip, intra macroblocks; the reconstruction hash; enc_search's two sub-sample counts;
-  // enc_deblock's filtered macroblocks; enc_search's early P_Skip macroblocks; the writers' I_NxN macroblocks
-  VTS_TRY(B.get(&d_stats, 10));
-  VTS_TRY(B.get(&d_err, 1));
-  uint4 *d_jobs;
-  uint32_t *d_njobs;
-  VTS_TRY(B.get(&d_jobs, static_cast<size_t>(max_chunk * nmb)));
-  VTS_TRY(B.get(&d_njobs, 1));
-  // Two streams: every level's motion search is enqueued up front on s1
-  // (level j needs only level j-1's reconstruction); the slice writing of a
-  // chunk of 16 levels (write, device offset scan, gather, I_PCM payloads,
-  // drain to the host) runs on s2 behind the chunk's last search event,
-  // overlapping the searches of later chunks.
-  hipStream_t s1 = c->s_dec, s2 = c->s_score;
-  B.streams = {s1, s2};
-  HIP_TRY(hipMemcpy(d_sent, plan.sent.data(), plan.sent.size() * sizeof(int4), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_went, plan.went.data(), plan.went.size() * sizeof(int4), hipMemcpyHostToDevice));
-  int4 *d_hent = nullptr;  // level 0's entries with the frame as the slot (enqueue_hash)
-  if (opt.hashed && !opt.intra) {
-    std::vector<int4> hent(plan.sent.begin(), plan.sent.begin() + plan.lvl_off[1]);
-    for (int4 &h : hent) h.z = h.x;
-    VTS_TRY(B.get(&d_hent, hent.size()));
-    HIP_TRY(hipMemcpy(d_hent, hent.data(), hent.size() * sizeof(int4), hipMemcpyHostToDevice));
-  }
-  HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), s2));
-  // enc_hash, enc_search<., SP > 0> and enc_deblock (s1) add into these
-  if (opt.hashed) HIP_TRY(hipMemsetAsync(d_stats + 4, 0, (opt.rate ? 5 : 4) * sizeof(unsigned long long), s1));
-  HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(uint32_t), s2));
-  if (opt.intra4x4) {
-    HIP_TRY(hipMemsetAsync(d_stats + 9, 0, sizeof(unsigned long long), s2));
-    HIP_TRY(hipMemsetAsync(d_i4, 0xff, plan.went.size() * static_cast<size_t>(nmb) * sizeof(uint64_t), s1));
-  }
-  const int64_t nchunks = (plan.maxlen + kChunkLevels - 1) / kChunkLevels;
-  std::vector<hipEvent_t> ev(static_cast<size_t>(plan.maxlen + 5 + nchunks), nullptr);
-  struct EvGuard {
-    std::vector<hipEvent_t> &v;
-    ~EvGuard() {
-      for (hipEvent_t e : v)
-        if (e) (void)hipEventDestroy(e);
-    }
-  } ev_guard{ev};
-  for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-  hipEvent_t es0 = ev[plan.maxlen], es1 = ev[plan.maxlen + 1], ew0 = ev[plan.maxlen + 2], ew1 = ev[plan.maxlen + 3];
-  hipEvent_t *wev = &ev[plan.maxlen + 5];  // per chunk: its slices written (its ring slots free again)
-  HIP_TRY(hipEventRecord(es0, s1));
-  // intra: the level's kPcmCmd macroblocks (level 0: every macroblock) become
-  // Intra16x16 where cheaper, then the level's reconstruction is hashed; both
-  // on the search stream, before the next level's search reads the slots
-  auto enqueue_intra = [&](int64_t j) {
-    const int64_t ne = plan.lvl_off[j + 1] - plan.lvl_off[j];
-    IntraArgs ia{};
-    ia.ent = d_sent + plan.lvl_off[j];
-    ia.small = S.d;
-    ia.stride = S.stride;
-    ia.recon = d_recon;
-    ia.cmd = d_cmd + plan.lvl_off[j] * nmb;
-    ia.cbp = d_cbp + plan.lvl_off[j] * nmb;
-    ia.coef = d_coef + (j % kRing) * plan.ngop * nmb * kCoefPerMb;
-    ia.cw = S.cw;
-    ia.ch = S.ch;
-    ia.mbw = mbw;
-    ia.mbh = mbh;
-    ia.qp = opt.qp;
-    ia.all = j == 0;
-    if (opt.intra4x4) {
-      ia.i4 = d_i4 + plan.lvl_off[j] * nmb;
-      hipLaunchKernelGGL(enc_intra<true>, dim3(static_cast<unsigned>(ne * mbh)), dim3(64), 0, s1, ia);
-    } else {
-      hipLaunchKernelGGL(enc_intra<false>, dim3(static_cast<unsigned>(ne * mbh)), dim3(64), 0, s1, ia);
-    }
-  };
-  // deblock: the level's reconstruction filtered in place (8.7, inside each
-  // macroblock row's slice) behind its search and intra coding, before it is
-  // hashed and the next level predicts from it.  Level 0 without intra is all
-  // I_PCM (qPav 0, alpha' 0: nothing is filtered) and is not launched
-  auto enqueue_deblock = [&](int64_t j) {
-    const int64_t ne = plan.lvl_off[j + 1] - plan.lvl_off[j];
-    DeblockArgs da{};
-    da.ent = d_sent + plan.lvl_off[j];
-    da.recon = d_recon;
-    da.stride = S.stride;
-    da.cmd = d_cmd + plan.lvl_off[j] * nmb;
-    da.cbp = d_cbp + plan.lvl_off[j] * nmb;
-    da.coef = d_coef + (j % kRing) * plan.ngop * nmb * kCoefPerMb;
-    da.cw = S.cw;
-    da.ch = S.ch;
-    da.mbw = mbw;
-    da.mbh = mbh;
-    da.qp = opt.qp;
-    da.off_a = 2 * opt.dbk_alpha;
-    da.off_b = 2 * opt.dbk_beta;
-    da.count = d_stats + 7;
-    hipLaunchKernelGGL(enc_deblock, dim3(static_cast<unsigned>(ne * mbh)), dim3(64), 0, s1, da);
-  };
-  // the level's pictures hashed where the next level reads them: the
-  // reconstruction slots, or (level 0 without intra: the IDR pictures are
-  // their source) the small store, through entries whose slot is the frame
-  auto enqueue_hash = [&](int64_t j) {
-    const int64_t ne = plan.lvl_off[j + 1] - plan.lvl_off[j];
-    const bool from_source = j == 0 && !opt.intra;
-    const int hb = std::max(1, std::min(64, (S.w * S.h * 3 / 2 + 4095) / 4096));
-    hipLaunchKernelGGL(enc_hash, dim3(static_cast<unsigned>(hb * ne)), dim3(256), 0, s1,
-                       from_source ? d_hent : d_sent + plan.lvl_off[j], from_source ? S.d : d_recon, S.stride, S.cw, S.ch,
-                       S.w, S.h, hb, d_stats + 4);
-  };
-  if (opt.intra) enqueue_intra(0);
-  if (opt.intra && opt.deblock) enqueue_deblock(0);
-  if (opt.hashed) enqueue_hash(0);
-  if (opt.intra) HIP_TRY(hipEventRecord(ev[0], s1));
-  int64_t next_search = 1;
-  bool searches_done = false;
-  // enqueue the searches of levels < upto; level j reuses the ring slot of
-  // level j - kRing, whose chunk's slice writing must have finished
-  auto enqueue_searches = [&](int64_t upto) -> int {
-    for (; next_search < std::min(plan.maxlen, upto); ++next_search) {
-      const int64_t j = next_search;
-      if (opt.qp >= 1 && j >= kRing) HIP_TRY(hipStreamWaitEvent(s1, wev[(j - kRing) / kChunkLevels], 0));
-      const int64_t ne = plan.lvl_off[j + 1] - plan.lvl_off[j];
-      SearchArgs sa{};
-      sa.ent = d_sent + plan.lvl_off[j];
-      sa.small = S.d;
-      sa.stride = S.stride;
-      sa.recon = d_recon;
-      sa.cmd = d_cmd + plan.lvl_off[j] * nmb;
-      sa.cbp = d_cbp + plan.lvl_off[j] * nmb;
-      sa.coef = d_coef ? d_coef + (j % kRing) * plan.ngop * nmb * kCoefPerMb : nullptr;
-      sa.cw = S.cw;
-      sa.ch = S.ch;
-      sa.mbw = mbw;
-      sa.nmb = nmb;
-      sa.range = opt.R;
-      sa.max_sad = opt.T;
-      sa.qp = opt.qp;
-      sa.sp_stats = d_stats + 5;
-      const dim3 grid(static_cast<unsigned>(ne * nmb));
-      if (opt.rate) {  // the instances with the rate-aware decisions compiled in
-        sa.rate = opt.rate;
-        sa.cmd_prev = d_cmd + plan.lvl_off[j - 1] * nmb;
-        sa.gop_pos = static_cast<int32_t>(j);
-        sa.lambda16 = full::erate::lambda16(opt.qp, opt.mv_lambda16);
-        sa.es_stat = d_stats + 8;
-        switch (opt.subpel) {
-          case 1: launch_search<1, true>(opt.R, grid, s1, sa); break;
-          case 2: launch_search<2, true>(opt.R, grid, s1, sa); break;
-          default: launch_search<0, true>(opt.R, grid, s1, sa); break;
-        }
-      } else {
-        switch (opt.subpel) {
-          case 1: launch_search<1, false>(opt.R, grid, s1, sa); break;
-          case 2: launch_search<2, false>(opt.R, grid, s1, sa); break;
-          default: launch_search<0, false>(opt.R, grid, s1, sa); break;
-        }
-      }
-      if (opt.intra) enqueue_intra(j);
-      if (opt.deblock) enqueue_deblock(j);
-      if (opt.hashed) enqueue_hash(j);
-      HIP_TRY(hipEventRecord(ev[j], s1));
-    }
-    if (next_search >= plan.maxlen && !searches_done) {
-      HIP_TRY(hipEventRecord(es1, s1));
-      searches_done = true;
-    }
-    return VTS_OK;
-  };
-  VTS_TRY(enqueue_searches(opt.qp >= 1 ? kRing : plan.maxlen));
-  HIP_TRY(hipGetLastError());
-  // Output drained to the host every chunk (absolute bytes [chunk_start[c],
-  // chunk_start[c+1])) and appended to the MP4's mdat while the GPU works on
-  // the next chunk; the sample table (display order) points into mdat.
-  Mp4Writer mw;
-  std::string e = mw.open(out_path);
-  if (!e.empty()) return fail(VTS_E_IO, "%s: %s", out_path, e.c_str());
-  std::vector<std::unique_ptr<uint8_t[]>> host;
-  std::vector<int64_t> chunk_start{0}, chunk_file;  // chunk c's file offset
-  hipEvent_t ev_d2h = ev[plan.maxlen + 4];              // reused: the last chunk's D2H
-  bool pending = false;                            // a chunk's D2H not yet written out
-  double mux_ms = 0;
-  auto write_pending = [&]() -> int {
-    if (!pending) return VTS_OK;
-    HIP_TRY(hipEventSynchronize(ev_d2h));
-    const auto tw = clk::now();
-    const size_t c = host.size() - 1;
-    int64_t off = 0;
-    const std::string we = mw.append(host[c].get(), static_cast<size_t>(chunk_start[c + 1] - chunk_start[c]), &off);
-    if (!we.empty()) return fail(VTS_E_IO, "%s: %s", out_path, we.c_str());
-    chunk_file.push_back(off);
-    host[c].reset();
-    pending = false;
-    mux_ms += std::chrono::duration<double, std::milli>(clk::now() - tw).count();
-    return VTS_OK;
-  };
-  int status = VTS_OK;
-  HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(int64_t), s2));
-  HIP_TRY(hipEventRecord(ew0, s2));
-  for (int64_t j0 = 0; j0 < plan.maxlen && status == VTS_OK; j0 += kChunkLevels) {
-    // one chunk of levels = one contiguous run of entries: written, scanned,
-    // gathered and drained together (wide launches instead of one per level)
-    const int64_t j1 = std::min(plan.maxlen, j0 + kChunkLevels);
-    const int64_t e0 = plan.lvl_off[j0], ne = plan.lvl_off[j1] - e0;
-    const int ns = static_cast<int>(ne * mbh);
-    if (j1 - 1 > 0 || opt.intra) HIP_TRY(hipStreamWaitEvent(s2, ev[j1 - 1], 0));  // searches run in level order
-    HIP_TRY(hipMemcpyAsync(d_base, d_total, sizeof(int64_t), hipMemcpyDeviceToDevice, s2));
-    HIP_TRY(hipMemsetAsync(d_njobs, 0, sizeof(uint32_t), s2));
-    WriteArgs wa{};
-    wa.ent = d_went + e0;
-    wa.cmd = d_cmd + e0 * nmb;
-    wa.cbp = d_cbp + e0 * nmb;
-    wa.coef = d_coef;
-    wa.coef_per_level = plan.ngop;
-    wa.ring = static_cast<int32_t>(kRing);
-    wa.qp = opt.qp;
-    wa.small = S.d;
-    wa.stride = S.stride;
-    wa.cw = S.cw;
-    wa.ch = S.ch;
-    wa.mbw = mbw;
-    wa.mbh = mbh;
-    wa.staging = d_stage;
-    wa.cap = cap;
-    wa.sizes = d_sizes;
-    wa.stats = d_stats;
-    wa.err = d_err;
-    wa.jobs = d_jobs;
-    wa.n_jobs = d_njobs;
-    wa.n_slices = ns;
-    wa.dbk_alpha = opt.dbk_alpha;
-    wa.dbk_beta = opt.dbk_beta;
-    wa.i4 = d_i4 ? d_i4 + e0 * nmb : nullptr;
-    const dim3 wgrid(static_cast<unsigned>((ns + 63) / 64));
-    if (opt.cabac) {  // one wave per slice
-      const dim3 cgrid(static_cast<unsigned>(ns));
-      if (opt.deblock) {
-        if (opt.intra) hipLaunchKernelGGL((enc_write_cabac<true, true>), cgrid, dim3(64), 0, s2, wa);
-        else hipLaunchKernelGGL((enc_write_cabac<false, true>), cgrid, dim3(64), 0, s2, wa);
-      } else {
-        if (opt.intra) hipLaunchKernelGGL((enc_write_cabac<true, false>), cgrid, dim3(64), 0, s2, wa);
-        else hipLaunchKernelGGL((enc_write_cabac<false, false>), cgrid, dim3(64), 0, s2, wa);
-      }
-    } else if (opt.deblock) {
-      if (opt.intra) hipLaunchKernelGGL((enc_write<true, true>), wgrid, dim3(64), 0, s2, wa);
-      else hipLaunchKernelGGL((enc_write<false, true>), wgrid, dim3(64), 0, s2, wa);
-    } else {
-      if (opt.intra) hipLaunchKernelGGL((enc_write<true, false>), wgrid, dim3(64), 0, s2, wa);
-      else hipLaunchKernelGGL((enc_write<false, false>), wgrid, dim3(64), 0, s2, wa);
-    }
-    HIP_TRY(hipEventRecord(wev[j0 / kChunkLevels], s2));
-    VTS_TRY(enqueue_searches(j1 + kRing));  // the ring slots of this chunk's levels are free once it is written
-    hipLaunchKernelGGL(enc_scan, dim3(1), dim3(1024), 0, s2, d_sizes, ns, d_went + e0, mbh, d_offs, d_total,
-                       d_fr, d_fr + n);
-    hipLaunchKernelGGL(enc_gather, dim3(static_cast<unsigned>(ns)), dim3(256), 0, s2, d_stage, cap, d_sizes, d_offs,
-                       d_base, d_out);
-    hipLaunchKernelGGL(enc_pcm, dim3(static_cast<unsigned>(std::min<int64_t>(16384, ne * nmb))), dim3(64), 0, s2,
-                       d_jobs, d_njobs, d_went + e0, S.d, S.stride, S.cw, S.ch, mbh, d_offs, d_base, d_out);
-    const hipError_t he = hipGetLastError();
-    if (he != hipSuccess) {
-      status = fail(VTS_E_HIP, "encoder launch: %s", hipGetErrorString(he));
-      break;
-    }
-    if (status != VTS_OK) break;
-    int64_t tot = 0;
-    if (hipMemcpyAsync(&tot, d_total, sizeof tot, hipMemcpyDeviceToHost, s2) != hipSuccess) {
-      status = fail(VTS_E_HIP, "encoder levels %lld.. failed", static_cast<long long>(j0));
-      break;
-    }
-    status = write_pending();  // the previous chunk, while this one runs
-    if (status != VTS_OK) break;
-    if (hipStreamSynchronize(s2) != hipSuccess) {
-      status = fail(VTS_E_HIP, "encoder levels %lld.. failed", static_cast<long long>(j0));
-      break;
-    }
-    const int64_t bytes = tot - chunk_start.back();
-    host.emplace_back(new uint8_t[static_cast<size_t>(std::max<int64_t>(bytes, 1))]);
-    HIP_TRY(hipMemcpyAsync(host.back().get(), d_out, static_cast<size_t>(bytes), hipMemcpyDeviceToHost, s2));
-    HIP_TRY(hipEventRecord(ev_d2h, s2));
-    pending = true;
-    chunk_start.push_back(tot);
-  }
-  if (status == VTS_OK) status = write_pending();
-  std::vector<int64_t> fr(static_cast<size_t>(2 * n), 0);
-  if (status == VTS_OK)
-    HIP_TRY(hipMemcpyAsync(fr.data(), d_fr, sizeof(int64_t) * 2 * n, hipMemcpyDeviceToHost, s2));
-  HIP_TRY(hipEventRecord(ew1, s2));
-  if (hipStreamSynchronize(s2) != hipSuccess || hipStreamSynchronize(s1) != hipSuccess)
-    status = status ? status : fail(VTS_E_HIP, "encoder failed");
-  if (status == VTS_OK) {
-    float a_ms = 0, b_ms = 0;
-    (void)hipEventElapsedTime(&a_ms, es0, es1);
-    (void)hipEventElapsedTime(&b_ms, ew0, ew1);
-    ms[1] = a_ms;
-    ms[2] = b_ms;
-  }
-  VTS_TRY(status);
-  uint32_t err = 0;
-  unsigned long long st[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  HIP_TRY(hipMemcpy(&err, d_err, sizeof err, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost));
-  if (err) return fail(VTS_E_CAPACITY, "a slice exceeded its %lld-byte staging slot", static_cast<long long>(cap));
-  if (opt.cmd_out) {  // entry order -> frame order; a level the encoder writes no words for (the I_PCM IDR pictures) is I_PCM
-    std::vector<uint32_t> words(plan.went.size() * static_cast<size_t>(nmb));
-    HIP_TRY(hipMemcpy(words.data(), d_cmd, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < plan.went.size(); ++i) {
-      uint32_t *o = opt.cmd_out + static_cast<int64_t>(plan.went[i].x) * nmb;
-      if (plan.went[i].y == 0 && !opt.intra) std::fill(o, o + nmb, kPcmCmd);
-      else std::memcpy(o, words.data() + i * static_cast<size_t>(nmb), static_cast<size_t>(nmb) * sizeof(uint32_t));
-    }
-  }
-
-  if (opt.i4_out) {  // as cmd_out; without intra4x4 no macroblock is I_NxN
-    std::fill(opt.i4_out, opt.i4_out + cmd_words, ei4::kNoModes);
-    if (opt.intra4x4) {
-      std::vector<uint64_t> words(plan.went.size() * static_cast<size_t>(nmb));
-      HIP_TRY(hipMemcpy(words.data(), d_i4, words.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-      for (size_t i = 0; i < plan.went.size(); ++i)
-        std::memcpy(opt.i4_out + static_cast<int64_t>(plan.went[i].x) * nmb, words.data() + i * static_cast<size_t>(nmb),
-                    static_cast<size_t>(nmb) * sizeof(uint64_t));
-    }
-  }
-
-  // 4. MP4 sample table (display order) over the mdat written above
-  t0 = clk::now();
-  std::vector<uint8_t> sps, pps;
-  const double fps = static_cast<double>(c->info.track_timescale) / static_cast<double>(delta);
-  make_sps_pps(mbw, mbh, S.cw - S.w, S.ch - S.h, h264_pick_level(nmb, nmb * fps), &sps, &pps, 0, opt.cabac != 0);
-  std::vector<uint8_t> is_idr(static_cast<size_t>(n), 0);
-  for (int64_t f : plan.gop_start) is_idr[f] = 1;
-  for (int64_t f = 0; f < n && e.empty(); ++f) {
-    const int64_t off = fr[f], size = fr[n + f];
-    const size_t ci = static_cast<size_t>(std::upper_bound(chunk_start.begin(), chunk_start.end(), off) -
-                                          chunk_start.begin()) - 1;
-    if (ci >= chunk_file.size() || off + size > chunk_start[ci + 1])
-      return fail(VTS_E_HIP, "frame %lld: output bookkeeping mismatch", static_cast<long long>(f));
-    e = mw.add_sample_at(chunk_file[ci] + (off - chunk_start[ci]), static_cast<size_t>(size), is_idr[f] != 0);
-  }
-  if (e.empty()) e = mw.finish(S.w, S.h, c->info.track_timescale, delta, sps, pps);
-  if (!e.empty()) return fail(VTS_E_IO, "%s: %s", out_path, e.c_str());
-  ms[3] = mux_ms + std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-  if (info) {
-    std::memset(info, 0, sizeof *info);
-    info->width = S.w;
-    info->height = S.h;
-    info->n_frames = n;
-    info->n_idr = plan.ngop;
-    info->pcm_mbs = static_cast<int64_t>(st[0]);
-    info->inter_mbs = static_cast<int64_t>(st[1]);
-    info->skip_mbs = static_cast<int64_t>(st[2]);
-    info->intra_mbs = static_cast<int64_t>(st[3]);
-    info->recon_hash = opt.hashed ? st[4] : 0;
-    info->bytes_written = mw.bytes_written();
-    for (int i = 0; i < 4; ++i) info->ms[i] = ms[i];
-  }
-  if (xinfo) {
-    if (xinfo->struct_size >= 16) xinfo->subpel_mbs = opt.subpel ? static_cast<int64_t>(st[5] + st[6]) : 0;
-    if (xinfo->struct_size >= 24) xinfo->qpel_mbs = opt.subpel ? static_cast<int64_t>(st[6]) : 0;
-    if (xinfo->struct_size >= 32)
-      reinterpret_cast<vts_transcode_ext_info2 *>(xinfo)->deblock_mbs = opt.deblock ? static_cast<int64_t>(st[7]) : 0;
-    if (xinfo->struct_size >= 40)
-      reinterpret_cast<vts_transcode_ext_info3 *>(xinfo)->early_skip_mbs = opt.early_skip ? static_cast<int64_t>(st[8]) : 0;
-    if (xinfo->struct_size >= 56)
-      reinterpret_cast<vts_transcode_ext_info4 *>(xinfo)->intra4x4_mbs = opt.intra4x4 ? static_cast<int64_t>(st[9]) : 0;
-  }
-  return VTS_OK;
-}
