@@ -627,6 +627,50 @@ typedef struct vts_transcode_ext_info4 {
   int64_t i4_words;        /* n_frames * macroblocks per picture               */
 } vts_transcode_ext_info4;
 
+/* Inter partitions, DESIGN.md §11 "Partitions".  As the structs above: begun
+ * with them, passed by pointer cast, struct_size = their own sizeof.  Read:
+ * partitions when struct_size >= 92, mv_out at >= 104, mv_cap at >= 112 (an
+ * 88-byte vts_transcode_ext5 or anything smaller: off / NULL); written:
+ * p16x8_mbs at >= 72, p8x16_mbs at >= 80, p8x8_mbs at >= 88, mv_words at >= 96.
+ * partitions = 1 (needs mvcost = 1, residual coding and max_mb_sad >= 0): the
+ * motion search keeps every candidate's SAD per 8x8 quadrant and gives a
+ * macroblock one vector, a top and a bottom one (16x8), a left and a right one
+ * (8x16) or one per quadrant (P_8x8 of four P_L0_8x8; nothing below 8x8, one
+ * reference picture).  Each of the nine blocks takes its least (16 SAD +
+ * lambda16 bits(v - p), candidate) over the window, p the macroblock's
+ * predictor guess; a shape costs its blocks' sum plus lambda16 times its
+ * mb_type / sub_mb_type bits (1, 3, 3, 9), the least wins, ties to fewer
+ * vectors.  With subpel each block of that shape is refined on its own.  The
+ * macroblock is then coded in the coarsest shape its four quadrant vectors
+ * allow, so equal vectors are never sent twice; all equal is P_L0_16x16 (or
+ * P_Skip by the rule above).  inter_mbs counts partitioned macroblocks too;
+ * subpel_mbs / qpel_mbs count a macroblock once (quarter if any vector has an
+ * odd component, else half if any is fractional).
+ * Command word of a partitioned macroblock: 0x00008000 | shape << 16, shape 1
+ * 16x8, 2 8x16, 3 8x8.  mv_out[frame][my][mx][4]: the quadrant vectors (raster
+ * order) of every inter macroblock as mvx | mvy << 16, a 16x16 macroblock's
+ * word four times, P_Skip four 0; every word of an intra or I_PCM macroblock
+ * is 0x80008000.  Reported with any settings, as cmd_out is.
+ * VTS_E_INVALID, the field named: partitions not 0 or 1, partitions = 1 with
+ * qp < 0, with max_mb_sad < 0 or without mvcost = 1 (a SAD-only split always
+ * prefers the finest shape).  VTS_E_CAPACITY before any encoding: mv_out with
+ * mv_cap < mv_words.  recon_hash is filled (mvcost = 1 does that). */
+typedef struct vts_transcode_ext6 {
+  vts_transcode_ext5 base;
+  int32_t partitions;      /* 0 off (every output byte as before), 1 on         */
+  int32_t _pad4;
+  uint32_t *mv_out;        /* NULL, or mv_cap words, four per macroblock        */
+  int64_t mv_cap;          /* words mv_out holds                                */
+} vts_transcode_ext6;
+
+typedef struct vts_transcode_ext_info5 {
+  vts_transcode_ext_info4 base;
+  int64_t p16x8_mbs;       /* macroblocks coded P_L0_L0_16x8; these three 0 when */
+  int64_t p8x16_mbs;       /* ... P_L0_L0_8x16               partitions is off  */
+  int64_t p8x8_mbs;        /* ... P_8x8                                         */
+  int64_t mv_words;        /* 4 * n_frames * macroblocks per picture            */
+} vts_transcode_ext_info5;
+
 /* vts_transcode with the settings of `ext` (NULL: none) and the further facts
  * in `ext_info` (NULL: not wanted).  vts_transcode(c, o, p, i) is
  * vts_transcode_ex(c, o, p, NULL, i, NULL). */

@@ -33,6 +33,7 @@
 
 #include "enc_deblock.h"
 #include "enc_intra4.h"
+#include "enc_part.h"
 #include "enc_rbsp.h"
 #include "h264_cabac_tables.h"
 
@@ -69,6 +70,11 @@ constexpr int kNumCtx = 277;  // ctxIdx 0 .. 276: the frame-coded 4x4 syntax and
 //   (eres::quant1), so a level's UEG0 suffix and sign take at most 10 + 1 + 10
 //   + 1 bits and a level 16 x 6 + 22 = 118, not 124: 384 x 118 + 546 + 156 =
 //   46014 bits = 5752 bytes, 8628 with emulation prevention.  9024 bounds it.
+//   A partitioned macroblock (mb_p_part) is an inter one with up to 4
+//   sub_mb_type bins and 6 more mvd (prefix 9 bins at 7 bits, suffix and sign
+//   32 bits): 28 + 6 x 95 = 598 bits over the inter macroblock's 45791 of the
+//   arithmetic just given, 46389 bits = 5799 bytes, 8699 with emulation
+//   prevention.  9024 bounds it.
 constexpr int kMbBytes = 9024;
 
 #if defined(__HIPCC__)
@@ -199,7 +205,8 @@ struct Encoder {
 //   a residual block: coded_block_flag 1, significant and last 15 + 15, and
 //     for each of 16 levels 14 prefix bins, a UEG0 suffix of at most 15 + 1 +
 //     15 bins (|level| <= 2^15) and the sign: 31 + 16 x 46 = 767;
-//   a macroblock's header: well under that (two mvd of 9 + 30 + 1 bins the most).
+//   a macroblock's header: well under that (mvd of 9 + 30 + 1 bins each, two, or
+//     with partitions eight and four sub_mb_type bins: 340 with the rest).
 constexpr int kRingBins = 2048, kBlockBins = 768;
 constexpr uint32_t kBinBypass = 1u << 10, kBinTerminate = 1u << 11;
 
@@ -269,6 +276,7 @@ struct Left {        // the macroblock to the left in the slice (mx = 0: kNone)
   int amvd[2];       // |mvd_l0| (inter that is not skipped; else 0)
   uint32_t cbf;
   uint64_t i4 = ei4::kNoModes;  // I_NxN: its Intra4x4PredModes (enc_intra4.h), else ~0
+  int bmvd[2] = {0, 0};         // |mvd_l0| of its quadrant 3 (amvd: of its quadrant 1; partitions, else unread)
 };
 VTS_HD VTS_INLINE Left left_none() { return Left{kNone, 0, 0, {0, 0}, 0, ei4::kNoModes}; }
 
@@ -538,6 +546,72 @@ VTS_HD inline void mb_inter(E &e, Left &l, int dx, int dy, int cbp, const int16_
   e.terminate(last);
   const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
   l = Left{kInter, cbp, 0, {ax < 33 ? ax : 33, ay < 33 ? ay : 33}, cbf};
+  l.bmvd[0] = l.amvd[0];
+  l.bmvd[1] = l.amvd[1];
+}
+// mb_type of the partitioned P macroblocks (Table 9-37): P_L0_L0_16x8 (1) bins
+// 0 1 1 at ctxIdx 14, 15, 17; P_L0_L0_8x16 (2) 0 1 0; P_8x8 (3) 0 0 1 at 14,
+// 15, 16
+template <class E>
+VTS_HD VTS_INLINE void mb_type_p_part(E &e, int shape) {
+  e.decision(14, 0);
+  if (shape == epart::k8x8) {
+    e.decision(15, 0);
+    e.decision(16, 1);
+  } else {
+    e.decision(15, 1);
+    e.decision(17, shape == epart::k16x8);
+  }
+}
+// A partitioned macroblock (enc_part.h) of `shape` with the quadrant vectors
+// mv4 (words); lmv: the left macroblock's vectors for epart::pred_block.
+// mb_type, for P_8x8 four sub_mb_type P_L0_8x8 (the one bin 1 at ctxIdx 21),
+// the mvds in syntax order, then as mb_inter.  ctxIdxInc of an mvd's first bin
+// is by |mvd| of A plus |mvd| of B (9.3.3.1.1.7): B lies in another slice (0)
+// for the upper blocks and inside the macroblock for the lower ones, A is the
+// left macroblock's right column (its quadrant 1 or 3) or the block to the
+// left inside the macroblock.
+template <class E>
+VTS_HD inline void mb_p_part(E &e, Left &l, int shape, const uint32_t *mv4, const epart::Left &lmv, int cbp,
+                             const int16_t *cp, bool last) {
+  epart::Mv q[4];
+  for (int i = 0; i < 4; ++i) q[i] = epart::mv_of_word(mv4[i]);
+  e.block_begin();
+  mb_skip_flag(e, l, 0);
+  mb_type_p_part(e, shape);
+  if (shape == epart::k8x8)
+    for (int i = 0; i < 4; ++i) e.decision(21, 1);
+  int cur[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};  // |mvd| by quadrant
+  for (int part = 0; part < epart::shape_blocks(shape); ++part) {
+    const int fq = epart::part_quad(shape, part), mask = epart::block_quads(epart::shape_first(shape) + part);
+    const epart::Mv p = epart::pred_block(shape, part, q, lmv);
+    const int d[2] = {q[fq].x - p.x, q[fq].y - p.y};
+    for (int c = 0; c < 2; ++c) {
+      const int a = (fq & 1) ? cur[fq - 1][c] : (fq == 0 ? l.amvd[c] : l.bmvd[c]);
+      const int b = fq >= 2 ? cur[fq - 2][c] : 0;
+      mvd(e, c ? 47 : 40, a + b, d[c]);
+    }
+    for (int i = 0; i < 4; ++i)
+      if ((mask >> i) & 1)
+        for (int c = 0; c < 2; ++c) {
+          const int a = d[c] < 0 ? -d[c] : d[c];
+          cur[i][c] = a < 33 ? a : 33;
+        }
+  }
+  coded_block_pattern(e, l, cbp);
+  uint32_t cbf = 0;
+  if (cbp) {
+    mb_qp_delta0(e);
+    for (int k = 0; k < 16; ++k)
+      if ((cbp >> (k >> 2)) & 1)
+        cbf |= static_cast<uint32_t>(residual_block(e, 2, cbf_inc_luma(l, cbf, k, false), cp + 16 * k, 16))
+               << (1 + edb::raster_of_blk(k));
+    cbf = chroma_residual(e, l, cp, cbp >> 4, false, cbf);
+  }
+  e.terminate(last);
+  l = Left{kInter, cbp, 0, {cur[1][0], cur[1][1]}, cbf};
+  l.bmvd[0] = cur[3][0];
+  l.bmvd[1] = cur[3][1];
 }
 // I_PCM up to the samples: mb_type through the terminate bin and the flush.
 // The caller writes pcm_alignment_zero_bits and the 384 samples (or leaves

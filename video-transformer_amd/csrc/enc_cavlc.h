@@ -1,7 +1,7 @@
 // enc_cavlc.h — CAVLC slice data (7.3.4, 7.3.5, 9.2) of the device encoder's
 // slices (transcode.hip: enc_write), written once for the
 // kernels and for the CPU harnesses (tests/native/enc_cabac_host.cpp,
-// enc_intra4_host.cpp).  oracle/transcode_oracle.c restates it independently.
+// enc_intra4_host.cpp, enc_part_host.cpp).  oracle/transcode_oracle.c restates it independently.
 //
 //   residual_block  residual_block_cavlc of one block into a Sink (enc_rbsp.h:
 //                   the kernel's WordSink, the harness's ByteSink, BitCount),
@@ -22,6 +22,7 @@
 
 #include "enc_deblock.h"
 #include "enc_intra4.h"
+#include "enc_part.h"
 #include "enc_rbsp.h"
 #include "h264_tables.h"
 
@@ -191,13 +192,14 @@ struct Row {
   uint64_t left_modes;      // the left macroblock's Intra4x4PredModes when it is I_NxN, else ~0
   bool has_left;
   bool a_ok;                // the left macroblock has a motion vector (8.4.1.3: A the only neighbour)
-  int amx, amy;
+  int amx, amy;             // ... of its quadrant 1, beside this macroblock's upper half
+  int a3x, a3y;             // ... of its quadrant 3 (partitions, enc_part.h; else the same vector)
   uint32_t skip;            // the pending mb_skip_run
   VTS_EV void start() {     // of a slice
     all(-1);
     left_modes = ei4::kNoModes;
     has_left = a_ok = false;
-    amx = amy = 0;
+    amx = amy = a3x = a3y = 0;
     skip = 0;
   }
   VTS_EV void all(int v) {  // 16 after I_PCM, 0 after P_Skip
@@ -220,9 +222,10 @@ struct Row {
     left_modes = modes;
     has_left = true;
     a_ok = mv;
-    amx = mvx;
-    amy = mvy;
+    amx = a3x = mvx;
+    amy = a3y = mvy;
   }
+  VTS_EV epart::Left left_mv() const { return epart::Left{a_ok, {amx, amy}, {a3x, a3y}}; }
 };
 
 // ------------------------------------------------------- residual() (7.3.5.3)
@@ -303,6 +306,38 @@ VTS_EV void mb_inter(Sink &o, Row &z, uint32_t cmd, int cbp, const int16_t *cp) 
   }
   z.shift();
   z.left_is(ei4::kNoModes, true, mvx, mvy);
+}
+// A partitioned macroblock (enc_part.h) from its command word (0x8000 | shape
+// << 16, shape 1 P_L0_L0_16x8, 2 P_L0_L0_8x16, 3 P_8x8 of four P_L0_8x8), its
+// four quadrant vectors mv4 (words), coded_block_pattern and levels: mb_type,
+// the sub_mb_types, the mvds in syntax order against epart::pred_block (one
+// reference picture: no ref_idx_l0), then as mb_inter
+template <class Sink>
+VTS_EV void mb_p_part(Sink &o, Row &z, uint32_t cmd, const uint32_t *mv4, int cbp, const int16_t *cp) {
+  const int shape = epart::part_shape(cmd);
+  epart::Mv q[4];
+  for (int i = 0; i < 4; ++i) q[i] = epart::mv_of_word(mv4[i]);
+  skip_run(o, false, z);
+  o.ue(static_cast<uint32_t>(shape));  // mb_type
+  if (shape == epart::k8x8)
+    for (int i = 0; i < 4; ++i) o.ue(0);  // sub_mb_type P_L0_8x8
+  const epart::Left l = z.left_mv();
+  for (int part = 0; part < epart::shape_blocks(shape); ++part) {
+    const epart::Mv p = epart::pred_block(shape, part, q, l), v = q[epart::part_quad(shape, part)];
+    o.se(v.x - p.x);
+    o.se(v.y - p.y);
+  }
+  o.ue(cbp_inter_code(cbp));
+  z.clear();
+  if (cbp) {
+    o.se(0);  // mb_qp_delta
+    luma_residual(o, cp, cbp, z);
+    chroma_residual(o, cp, cbp >> 4, z);
+  }
+  z.shift();
+  z.left_is(ei4::kNoModes, true, q[1].x, q[1].y);
+  z.a3x = q[3].x;
+  z.a3y = q[3].y;
 }
 // macroblock_layer() of Intra16x16 from mb_type on (Table 7-11; 5 more in a P
 // slice), from its command word (bits 0..1 Intra16x16PredMode, 2..3

@@ -32,6 +32,9 @@ struct Mb {
   int kind;      // kInter (P_L0_16x16 or P_Skip, one reference picture), kI16, kPcm
   int mvx, mvy;  // quarter samples (inter; P_Skip is (0, 0) here: the row above is another slice)
   uint32_t nz;   // inter: bit b set = the raster 4x4 luma block b has a non-zero level
+  bool part;     // inter with partitions (enc_part.h): the vector is per 8x8 quadrant, in q0 .. q3
+  uint32_t q0, q1, q2, q3;  // part: the quadrants' vectors as words mvx | mvy << 16, raster order (scalars: no
+                            // member is ever indexed, so the struct stays in registers)
 };
 
 // luma4x4BlkIdx -> raster 4x4 index (6.4.3)
@@ -63,23 +66,62 @@ VTS_HD VTS_INLINE Mb mb_of_cmd(uint32_t cmd, uint32_t nz) {
   m.mvx = m.kind == kInter ? static_cast<int16_t>(cmd & 0xffffu) : 0;
   m.mvy = m.kind == kInter ? static_cast<int16_t>(cmd >> 16) : 0;
   m.nz = m.kind == kInter ? nz : 0;
+  m.part = false;
+  m.q0 = m.q1 = m.q2 = m.q3 = 0;
   return m;
 }
+// The same with partitions on: mv4 the macroblock's four quadrant vectors
+// (enc_part.h: the level's mv4 array), which every inter macroblock has; a
+// partitioned macroblock's command word (low half 0x8000, high half 1..3) is
+// inter and carries no vector itself
+VTS_HD VTS_INLINE Mb mb_of_cmd4(uint32_t cmd, uint32_t nz, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3) {
+  Mb m = mb_of_cmd(cmd, nz);
+  const bool inter = m.kind == kInter;
+  m.part = inter;
+  m.q0 = inter ? v0 : 0;
+  m.q1 = inter ? v1 : 0;
+  m.q2 = inter ? v2 : 0;
+  m.q3 = inter ? v3 : 0;
+  return m;
+}
+VTS_HD VTS_INLINE Mb mb_of_cmd4(uint32_t cmd, uint32_t nz, const uint32_t *mv4) {
+  return mb_of_cmd4(cmd, nz, mv4[0], mv4[1], mv4[2], mv4[3]);
+}
+// the quadrant of raster 4x4 block b
+VTS_HD VTS_INLINE int quad_of_raster(int b) { return ((b >> 3) << 1) | ((b >> 1) & 1); }
 
-// bS of a line between raster 4x4 blocks bp of p and bq of q (8.7.2.1)
+// quadrant i's vector, by selects: the index is a lane's own
+VTS_HD VTS_INLINE uint32_t quad_word(const Mb &m, int i) { return i == 0 ? m.q0 : (i == 1 ? m.q1 : (i == 2 ? m.q2 : m.q3)); }
+// The motion part of bS (8.7.2.1, one reference picture): the two 4x4 blocks'
+// vectors differ by >= 4 quarter samples in a component.  Without partitions a
+// macroblock has one vector; with them each block has its quadrant's, so the
+// inner edges at x = 8 and y = 8 can be 1 and the left edge is 1 per half.
+VTS_HD VTS_INLINE bool blocks_far(const Mb &p, int bp, const Mb &q, int bq) {
+  if (!p.part && !q.part) return mv_far(p.mvx, p.mvy, q.mvx, q.mvy);
+  const uint32_t a = quad_word(p, quad_of_raster(bp)), b = quad_word(q, quad_of_raster(bq));
+  return mv_far(static_cast<int16_t>(a & 0xffffu), static_cast<int16_t>(a >> 16), static_cast<int16_t>(b & 0xffffu),
+                static_cast<int16_t>(b >> 16));
+}
+
+// bS of a line between raster 4x4 blocks bp of p and bq of q (8.7.2.1).
+// kPart = false: no macroblock has quadrant vectors (the encoder without
+// partitions: the code is what it was)
+template <bool kPart = true>
 VTS_HD VTS_INLINE int bs(const Mb &p, int bp, const Mb &q, int bq, bool mb_edge) {
   if (p.kind != kInter || q.kind != kInter) return mb_edge ? 4 : 3;
   if (((p.nz >> bp) | (q.nz >> bq)) & 1u) return 2;
-  return mv_far(p.mvx, p.mvy, q.mvx, q.mvy) ? 1 : 0;
+  if constexpr (kPart) return blocks_far(p, bp, q, bq) ? 1 : 0;
+  else return mv_far(p.mvx, p.mvy, q.mvx, q.mvy) ? 1 : 0;
 }
 
 // bS of line k (0..15, luma samples along the edge) of edge e (0: the left
 // macroblock edge, p = the macroblock to the left; 1..3: inner, p = q) in
 // direction dir (0: vertical edges, 1: horizontal edges)
+template <bool kPart = true>
 VTS_HD VTS_INLINE int line_bs(const Mb &p, const Mb &q, int dir, int e, int k) {
   const int bq = dir ? e * 4 + (k >> 2) : (k >> 2) * 4 + e;
   const int bp = dir ? ((e + 3) & 3) * 4 + (k >> 2) : (k >> 2) * 4 + ((e + 3) & 3);
-  return bs(p, bp, q, bq, e == 0);
+  return bs<kPart>(p, bp, q, bq, e == 0);
 }
 
 // qPp / qPq of 8.7.2.2: 0 for I_PCM, else the slice's QP (mb_qp_delta is 0)

@@ -24,6 +24,9 @@ enum StatSlot : int {
   kStDeblocked,  // enc_deblock: macroblocks with a filtered line
   kStEarlySkip,  // enc_search<., ., true>: macroblocks the early P_Skip probe decided
   kStI4,         // the writers: I_NxN macroblocks
+  kStP16x8,      // the writers: inter macroblocks coded as P_L0_L0_16x8 (partitions)
+  kStP8x16,      // ... as P_L0_L0_8x16
+  kStP8x8,       // ... as P_8x8
   kStCount
 };
 
@@ -44,6 +47,9 @@ struct SearchArgs {
   const uint32_t *cmd_prev;      // the previous level's final words [entry][mb]; ent[e].w = the GOP's entry there
   int32_t gop_pos, lambda16;     // the level's GOP position j; lambda16 of the vector cost
   unsigned long long *es_stat;   // macroblocks the early P_Skip probe decided
+  // PT only (enc_part.h)
+  uint32_t *mv4;                 // [entry][mb][4] the quadrant vectors, kNoMv four times where not inter
+  const uint32_t *mv4_prev;      // the previous level's, as cmd_prev
 };
 
 // ------------------------------------------------------ slice writer
@@ -67,6 +73,7 @@ struct WriteArgs {
   int32_t n_slices;
   int32_t dbk_alpha, dbk_beta, _pad;  // enc_write<., true>: slice_alpha_c0_offset_div2, slice_beta_offset_div2
   const uint64_t *i4;   // [entry][mb] the Intra4x4PredModes of the I_NxN macroblocks (intra4x4; else unread)
+  const uint32_t *mv4;  // [entry][mb][4] the quadrant vectors (partitions; else NULL and unread)
 };
 
 // ------------------------------------------------------ intra coding
@@ -96,6 +103,7 @@ struct DeblockArgs {
   int32_t cw, ch, mbw, mbh;
   int32_t qp, off_a, off_b, _pad;  // SliceQPY, FilterOffsetA, FilterOffsetB
   unsigned long long *count;       // macroblocks with a filtered line
+  const uint32_t *mv4;             // [entry][mb][4] the quadrant vectors (partitions; else NULL and unread)
 };
 
 // ------------------------------------------------------ host-side only
@@ -129,7 +137,7 @@ struct PackArgs {
 // One launch function per stage, each holding its kernel's template dispatch.
 // They only queue (errors surface in hipGetLastError, as with a bare launch).
 // entries: the level's (chunk's) entries; a stage's grid follows from it.
-void launch_enc_search(const SearchArgs &a, int subpel, bool rate_aware, int64_t entries, hipStream_t s);
+void launch_enc_search(const SearchArgs &a, int subpel, bool rate_aware, bool partitions, int64_t entries, hipStream_t s);
 void launch_enc_intra(const IntraArgs &a, bool intra4x4, int64_t entries, hipStream_t s);
 void launch_enc_deblock(const DeblockArgs &a, int64_t entries, hipStream_t s);
 void launch_enc_hash(const HashArgs &a, int64_t entries, hipStream_t s);

@@ -37,6 +37,7 @@
 #include "enc_cabac.h"
 #include "enc_cavlc.h"
 #include "enc_deblock.h"
+#include "enc_part.h"
 #include "enc_rate.h"
 #include "recon_full.h"
 #include "transcode.h"
@@ -71,6 +72,7 @@ namespace er = full::erate;
 namespace eres = full::eres;  // the transform, the quantiser and the reconstruction (enc_residual.h)
 namespace ei4 = full::ei4;    // the Intra_4x4 decisions (enc_intra4.h)
 namespace ecav = full::ecav;  // the CAVLC slice writer and its bit counts (enc_cavlc.h)
+namespace ep = full::epart;   // the inter partitions (enc_part.h)
 
 // ------------------------------------------------------ motion search
 __device__ __forceinline__ uint32_t u32_at(const uint8_t *lds_row, int off) {  // 4 bytes at any offset
@@ -375,6 +377,114 @@ __device__ __forceinline__ IntegerMv integer_search(int lane, int R, const uint8
   return {r % side - R, r / side - R, key.sad(best)};
 }
 
+// ---- stage: the integer search with partitions (PT).  The same candidates
+// and LDS reads, but a candidate's SAD is kept as four quadrant sums (left /
+// right: the row's dwords 0, 1 against 2, 3; top / bottom: the source row),
+// from which each of enc_part.h's nine blocks takes its own; nine 64-bit
+// minima over the wave instead of one.  The rate term is the candidate's own,
+// the same for every block: they share the macroblock's predictor guess.
+struct PartMv {
+  uint64_t key[ep::kBlocks];  // the winning key of every block
+};
+__device__ __forceinline__ void part_take(uint64_t *best, const uint32_t *q, uint32_t index, uint32_t rate) {
+#pragma unroll
+  for (int b = 0; b < ep::kBlocks; ++b) {
+    const uint32_t sad = ep::block_sad(q, b);
+    const uint64_t k = er::key_of(16u * sad + rate, index, sad);
+    best[b] = k < best[b] ? k : best[b];
+  }
+}
+template <int RT, int SP>
+__device__ __forceinline__ PartMv integer_search_part(int lane, int R, const uint8_t *win, const uint32_t *srcy,
+                                                      const SearchKey<true> &key) {
+  using G = WinGeo<SP>;
+  constexpr int LX = G::LX, LY = G::LY, WP = G::WP;
+  const int side = 2 * R + 1, ncand = side * side, center = R * side + R;
+  PartMv m;
+#pragma unroll
+  for (int b = 0; b < ep::kBlocks; ++b) m.key[b] = ~0ull;
+  const uint4 *sr = reinterpret_cast<const uint4 *>(srcy);
+  if constexpr (RT > 0) {
+    // integer_search's register blocking, in passes of at most PB candidate
+    // rows a lane so that the 4 PB accumulators stay in registers; each half
+    // of the source rows walks its own 8 + PB - 1 window rows
+    constexpr int SIDE = 2 * RT + 1, NG = 64 / SIDE, NB = (SIDE + NG - 1) / NG, PB = NB < 6 ? NB : 6;
+    const int gx = lane % SIDE, gy = lane / SIDE, dy0 = gy * NB;
+    if (gy < NG && dy0 < SIDE) {
+      const int sh = gx & 3;
+      for (int p0 = 0; p0 < NB; p0 += PB) {
+        const int nv = min(PB, min(NB - p0, SIDE - dy0 - p0));  // the pass's candidate rows
+        if (nv <= 0) break;
+        uint32_t acc[PB][4];
+#pragma unroll
+        for (int g = 0; g < PB; ++g) acc[g][0] = acc[g][1] = acc[g][2] = acc[g][3] = 0;
+        const uint32_t *wb = reinterpret_cast<const uint32_t *>(win + (dy0 + p0 + LY) * WP + LX + (gx & ~3));
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+#pragma unroll 2
+          for (int w = 0; w < 8 + nv - 1; ++w) {
+            const uint32_t *wr = wb + (w + 8 * h) * (WP / 4);
+            const uint32_t w0 = wr[0], w1 = wr[1], w2 = wr[2], w3 = wr[3], w4 = wr[4];
+            const uint32_t r0 = __builtin_amdgcn_alignbyte(w1, w0, sh), r1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
+            const uint32_t r2 = __builtin_amdgcn_alignbyte(w3, w2, sh), r3 = __builtin_amdgcn_alignbyte(w4, w3, sh);
+#pragma unroll
+            for (int g = 0; g < PB; ++g) {
+              const int yy = w - g;
+              if (yy >= 0 && yy < 8) {
+                const uint4 q = sr[yy + 8 * h];  // broadcast read
+                acc[g][2 * h] = __builtin_amdgcn_sad_u8(r0, q.x, acc[g][2 * h]);
+                acc[g][2 * h] = __builtin_amdgcn_sad_u8(r1, q.y, acc[g][2 * h]);
+                acc[g][2 * h + 1] = __builtin_amdgcn_sad_u8(r2, q.z, acc[g][2 * h + 1]);
+                acc[g][2 * h + 1] = __builtin_amdgcn_sad_u8(r3, q.w, acc[g][2 * h + 1]);
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int g = 0; g < PB; ++g) {
+          const int dyi = dy0 + p0 + g;
+          if (g < nv) {
+            const int vx = 4 * (gx - RT), vy = 4 * (dyi - RT);
+            part_take(m.key, acc[g], cand_of_raster(dyi * SIDE + gx, center),
+                      static_cast<uint32_t>(key.lam16) * static_cast<uint32_t>(er::mv_bits(vx - key.p.x, vy - key.p.y)));
+          }
+        }
+      }
+    }
+  } else {
+    for (int c = lane; c < ncand; c += 64) {
+      const int r = raster_of_cand(c, center);
+      const int dy = r / side - R, dx = r % side - R;
+      uint32_t q4[4] = {0, 0, 0, 0};
+      const int ox = dx + R, sh = ox & 3;
+      const uint32_t *wr = reinterpret_cast<const uint32_t *>(win + (dy + R + LY) * WP + LX + (ox & ~3));
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+#pragma unroll 4
+        for (int yy = 0; yy < 8; ++yy) {
+          const uint32_t *w = wr + (yy + 8 * h) * (WP / 4);
+          const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
+          const uint4 sv = sr[yy + 8 * h];
+          q4[2 * h] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, sh), sv.x, q4[2 * h]);
+          q4[2 * h] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w2, w1, sh), sv.y, q4[2 * h]);
+          q4[2 * h + 1] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w3, w2, sh), sv.z, q4[2 * h + 1]);
+          q4[2 * h + 1] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w4, w3, sh), sv.w, q4[2 * h + 1]);
+        }
+      }
+      part_take(m.key, q4, static_cast<uint32_t>(c),
+                static_cast<uint32_t>(key.lam16) * static_cast<uint32_t>(er::mv_bits(4 * dx - key.p.x, 4 * dy - key.p.y)));
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < ep::kBlocks; ++b)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const uint64_t o = __shfl_xor(m.key[b], off);
+      m.key[b] = o < m.key[b] ? o : m.key[b];
+    }
+  return m;
+}
+
 // The prediction of quarter-sample offset (qx, qy) from an integer position
 // (8.4.2.2.1, Table 8-12) in terms of the half-sample grid around it, where
 // (X, Y) even/even is an integer sample G, odd/even b, even/odd h, odd/odd j:
@@ -400,12 +510,29 @@ __device__ __forceinline__ void sp_pair(int qx, int qy, int &XA, int &YA, int &X
 // rounding byte average of two dwords, no unpacking
 __device__ __forceinline__ uint32_t avg_u8x4(uint32_t p, uint32_t q) { return (p | q) - (((p ^ q) >> 1) & 0x7f7f7f7fu); }
 
+// What refine_and_predict works on: the whole macroblock, or with partitions
+// one block of it (enc_part.h).  A type, not an argument: with WholeMb the
+// function compiles to the code it was.
+struct WholeMb {
+  static constexpr bool kPart = false;
+};
+struct PartBlk {
+  static constexpr bool kPart = true;
+  ep::Rect r;
+};
 // ---- stage: the luma prediction at the winning vector, after (SP > 0) the
 // sub-sample refinement around the integer winner w: (cqx, cqy) receives the
-// refined vector in quarter samples from w; returned, the lane's 4 samples
-template <int SP, bool RC>
+// refined vector in quarter samples from w; returned, the lane's 4 samples.
+// PartBlk: the same for the block blk.r, called block after block
+// (wave-uniform): w is the block's integer winner and its SAD, the planes are
+// built around that winner as for a macroblock displaced by it, in the same
+// LDS, and a candidate's SAD is taken over the block's samples alone; the
+// returned samples are those of the macroblock at the block's vector.
+template <int SP, bool RC, class Blk = WholeMb>
 __device__ __forceinline__ uint32_t refine_and_predict(int lane, int R, const uint8_t *win, const uint32_t *srcy,
-                                                       const IntegerMv &w, const SearchKey<RC> &key, int &cqx, int &cqy) {
+                                                       const IntegerMv &w, const SearchKey<RC> &key, int &cqx, int &cqy,
+                                                       [[maybe_unused]] Blk blk = Blk{}) {
+  constexpr bool PT = Blk::kPart;
   using G = WinGeo<SP>;
   constexpr int WP = G::WP;
   const int ly = lane >> 2, lx = 4 * (lane & 3);
@@ -413,6 +540,7 @@ __device__ __forceinline__ uint32_t refine_and_predict(int lane, int R, const ui
   if constexpr (SP == 0) {
     return u32_at(win + (w.dy + R + ly) * WP, w.dx + R + lx);
   } else {
+    if constexpr (PT) __syncthreads();  // the lanes are done with the block before's planes
     // With (x, y) relative to the integer winner's block, whose sample (0, 0)
     // is win[oy][ox]: the half-sample planes b(x + 1/2, y), h(x, y + 1/2),
     // j(x + 1/2, y + 1/2) for every position a candidate of either step reads,
@@ -479,6 +607,15 @@ __device__ __forceinline__ uint32_t refine_and_predict(int lane, int R, const ui
         const uint32_t a0 = wa[0], a1 = wa[1], a2 = wa[2], a3 = wa[3], a4 = wa[4];
         const uint32_t b0 = wb[0], b1 = wb[1], b2 = wb[2], b3 = wb[3], b4 = wb[4];
         const int sa = A.off & 3, sb = B.off & 3;
+        if constexpr (PT) {  // the block's rows and halves of a row only (wave-uniform block, per-lane row)
+          uint32_t sl = 0, sr = 0;
+          sl = __builtin_amdgcn_sad_u8(avg_u8x4(__builtin_amdgcn_alignbyte(a1, a0, sa), __builtin_amdgcn_alignbyte(b1, b0, sb)), sv.x, sl);
+          sl = __builtin_amdgcn_sad_u8(avg_u8x4(__builtin_amdgcn_alignbyte(a2, a1, sa), __builtin_amdgcn_alignbyte(b2, b1, sb)), sv.y, sl);
+          sr = __builtin_amdgcn_sad_u8(avg_u8x4(__builtin_amdgcn_alignbyte(a3, a2, sa), __builtin_amdgcn_alignbyte(b3, b2, sb)), sv.z, sr);
+          sr = __builtin_amdgcn_sad_u8(avg_u8x4(__builtin_amdgcn_alignbyte(a4, a3, sa), __builtin_amdgcn_alignbyte(b4, b3, sb)), sv.w, sr);
+          if (row >= blk.r.y && row < blk.r.y + blk.r.h) s += (blk.r.x == 0 ? sl : 0u) + (blk.r.x + blk.r.w == 16 ? sr : 0u);
+          continue;
+        }
         s = __builtin_amdgcn_sad_u8(avg_u8x4(__builtin_amdgcn_alignbyte(a1, a0, sa), __builtin_amdgcn_alignbyte(b1, b0, sb)), sv.x, s);
         s = __builtin_amdgcn_sad_u8(avg_u8x4(__builtin_amdgcn_alignbyte(a2, a1, sa), __builtin_amdgcn_alignbyte(b2, b1, sb)), sv.y, s);
         s = __builtin_amdgcn_sad_u8(avg_u8x4(__builtin_amdgcn_alignbyte(a3, a2, sa), __builtin_amdgcn_alignbyte(b3, b2, sb)), sv.z, s);
@@ -562,9 +699,10 @@ __device__ __forceinline__ void finish_plain(const SearchArgs &a, int lane, cons
 
 // ---- epilogue with residual coding: the blocks by lane as MbPred lays them
 // out, then lanes 16 / 17 the chroma DC levels and 24 / 25 their bits; inter
-// when the residual's CAVLC bound is within an I_PCM payload, else I_PCM
+// when the residual's CAVLC bound is within an I_PCM payload, else I_PCM;
+// returned: inter
 template <int SP>
-__device__ __forceinline__ void finish_residual(const SearchArgs &a, int lane, const MbOut &o, const uint32_t *srcy, MbPred &P) {
+__device__ __forceinline__ bool finish_residual(const SearchArgs &a, int lane, const MbOut &o, const uint32_t *srcy, MbPred &P) {
   __shared__ uint32_t recy[64];
   __shared__ uint8_t recc[2][64];
   __shared__ int dcw[2][4], dcl[2][4];
@@ -621,6 +759,7 @@ __device__ __forceinline__ void finish_residual(const SearchArgs &a, int lane, c
     store_chroma_levels(cp, lane, lv, dcl);
   }
   if (lane == 0) write_words<SP>(a, o, inter, cbp);
+  return inter;
 }
 
 // RT: compile-time search range (register-blocked path), 0 = any range.
@@ -630,8 +769,19 @@ __device__ __forceinline__ void finish_residual(const SearchArgs &a, int lane, c
 // a.rate (wave-uniform); false: the code is the kernel's without them.  Every
 // instance asks for 5 waves/SIMD: they fit (88 .. 90 VGPRs, no scratch), but
 // left to itself the register allocator settles at 98 .. 102 and 4 waves.
-template <int RT, int SP, bool RC>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) enc_search(SearchArgs a) {
+// PT (with RC only): the inter partitions of enc_part.h.  The integer stage
+// keeps every candidate's quadrant SADs and decides the shape from the nine
+// blocks' winners; each block of that shape is refined on its own; every lane
+// predicts its luma samples and its Cb|Cr pair with the vector of the quadrant
+// they lie in, so the residual path sees one composite prediction; the four
+// quadrant vectors go to a.mv4 and the macroblock is coded in their canonical
+// shape.  These instances allow 4 waves/SIMD instead of asking for 5: those
+// without refinement at R = 4, 8, 16 take 98 VGPRs and run 4, the other nine
+// 88 .. 95 and 5; none uses scratch (profiles/part_resources.txt).
+// false: the code is the kernel's without it.
+template <int RT, int SP, bool RC, bool PT = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT ? 4 : 5))) enc_search(SearchArgs a) {
+  static_assert(RC || !PT, "partitions need the vector cost");
   __shared__ __attribute__((aligned(16))) uint8_t win[WinGeo<SP>::kBytes];
   __shared__ __attribute__((aligned(16))) uint32_t srcy[64];
   __shared__ MbPred P;
@@ -650,15 +800,65 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) en
   SearchKey<RC> key;
   if constexpr (RC) {
     const bool coded = a.qp >= 1 && a.max_sad >= 0;
-    if (coded && (a.rate & 2) && probe_skip(a, lane, o.mbi, mx, my, src, ref, o.dst, srcy, P)) return;
+    if (coded && (a.rate & 2) && probe_skip(a, lane, o.mbi, mx, my, src, ref, o.dst, srcy, P)) {
+      if constexpr (PT)
+        if (lane < 4) a.mv4[o.mbi * 4 + lane] = 0;
+      return;
+    }
     if (coded && (a.rate & 1)) {
       key.lam16 = a.lambda16;
-      key.p = er::pred_of_cmd(mx > 0 && a.gop_pos > 1 ? a.cmd_prev[static_cast<int64_t>(en.w) * a.nmb + mb - 1] : 0u, mx,
-                              a.gop_pos);
+      if constexpr (PT) {
+        const int64_t lp = mx > 0 && a.gop_pos > 1 ? static_cast<int64_t>(en.w) * a.nmb + mb - 1 : -1;
+        key.p = ep::pred_guess(lp >= 0 ? a.cmd_prev[lp] : 0u, lp >= 0 ? a.mv4_prev[lp * 4 + 1] : 0u, mx, a.gop_pos);
+      } else {
+        key.p = er::pred_of_cmd(mx > 0 && a.gop_pos > 1 ? a.cmd_prev[static_cast<int64_t>(en.w) * a.nmb + mb - 1] : 0u, mx,
+                                a.gop_pos);
+      }
     }
   }
   load_window<SP>(a, lane, ref, mx, my, win);
   __syncthreads();
+  if constexpr (PT) {
+    const int R = a.range, side = 2 * R + 1, center = R * side + R;
+    const PartMv pm = integer_search_part<RT, SP>(lane, R, win, srcy, key);
+    uint32_t cost9[ep::kBlocks];
+#pragma unroll
+    for (int b = 0; b < ep::kBlocks; ++b) cost9[b] = static_cast<uint32_t>(pm.key[b] >> 32);
+    const int shape = ep::decide_shape(cost9, key.lam16);  // wave-uniform: it comes out of wave reductions
+    const int lq = ep::quad_at(4 * (lane & 3), lane >> 2);  // the quadrant of the lane's luma samples
+    uint32_t qv[4] = {0, 0, 0, 0};
+    o.py = 0;
+    for (int i = 0; i < ep::shape_blocks(shape); ++i) {  // wave-uniform
+      const int b = ep::shape_first(shape) + i;
+      uint64_t k = pm.key[0];
+#pragma unroll
+      for (int bb = 1; bb < ep::kBlocks; ++bb) k = bb == b ? pm.key[bb] : k;
+      const int r = raster_of_cand(static_cast<int>(key.index(k)), center);
+      const IntegerMv w{r % side - R, r / side - R, key.sad(k)};
+      int cqx, cqy;
+      const uint32_t py = refine_and_predict<SP, true, PartBlk>(lane, R, win, srcy, w, key, cqx, cqy, PartBlk{ep::block_rect(b)});
+      const uint32_t word = ep::mv_word(4 * w.dx + cqx, 4 * w.dy + cqy);
+      const int m = ep::block_quads(b);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) qv[q] = ((m >> q) & 1) ? word : qv[q];
+      o.py = ((m >> lq) & 1) ? py : o.py;
+    }
+    const int cshape = ep::canonical_shape(qv);
+    o.mvw = cshape ? ep::part_cmd(cshape) : qv[0];
+    const int fc = ep::frac_class(qv);
+    o.frac = fc == 2 ? 1 : (fc == 1 ? 2 : 0);  // write_words: counted once, quarter before half
+    o.sy4 = srcy[lane];
+    const int cq = ep::quad_at(2 * (lane & 7), 2 * (lane >> 3));  // the quadrant of the lane's Cb|Cr pair
+    const ep::Mv cv = ep::mv_of_word(cq == 0 ? qv[0] : (cq == 1 ? qv[1] : (cq == 2 ? qv[2] : qv[3])));
+    const ChromaPx pc = chroma_pred(a, lane, ref, mx, my, cv.x, cv.y);
+    o.pc = static_cast<uint16_t>(pc.u | (pc.v << 8));
+    o.co = chroma_off(a, lane, mx, my);
+    o.suv = *reinterpret_cast<const uint16_t *>(src + o.co);
+    o.lo = luma_off(a, lane, mx, my);
+    const bool inter = finish_residual<SP>(a, lane, o, srcy, P);
+    if (lane < 4) a.mv4[o.mbi * 4 + lane] = !inter ? ep::kNoMv : (lane == 0 ? qv[0] : (lane == 1 ? qv[1] : (lane == 2 ? qv[2] : qv[3])));
+    return;
+  }
   const IntegerMv w = integer_search<RT, SP, RC>(lane, a.range, win, srcy, key);
   int cqx, cqy;
   o.py = refine_and_predict<SP, RC>(lane, a.range, win, srcy, w, key, cqx, cqy);
@@ -1071,6 +1271,9 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
 // and this one's columns 0..11 (the next edge 0 still changes 13..15).
 constexpr int kDbPitch = 20;
 
+// PT: a macroblock's motion is the four quadrant vectors of a.mv4 (enc_part.h);
+// false: the code is the kernel's without partitions
+template <bool PT>
 __global__ void __launch_bounds__(64) enc_deblock(DeblockArgs a) {
   namespace edb = full::edb;
   __shared__ __attribute__((aligned(16))) uint8_t T[24 * kDbPitch];
@@ -1102,6 +1305,8 @@ __global__ void __launch_bounds__(64) enc_deblock(DeblockArgs a) {
   if (lane < 32) pf_c = *reinterpret_cast<const uint32_t *>(gc);
   uint32_t n_cmd = a.cmd[mb0];
   int n_cbp = a.cbp[mb0];
+  [[maybe_unused]] uint4 n_mv{};  // PT: the macroblock's quadrant vectors
+  if constexpr (PT) n_mv = reinterpret_cast<const uint4 *>(a.mv4)[mb0];
   Lv n_lv{};
   load_lv(0, n_lv);
   // indexA, alpha' and beta' of this lane's plane for the three qPav an edge can have (qP is 0 for
@@ -1118,14 +1323,17 @@ __global__ void __launch_bounds__(64) enc_deblock(DeblockArgs a) {
     if (lane < 24) *reinterpret_cast<uint32_t *>(T + lane * kDbPitch) = carry;
     const uint32_t cmd = n_cmd;
     const bool nzb = lane < 16 && edb::blk_nz(n_lv.s, n_cbp, lane);
+    [[maybe_unused]] const uint4 mv = n_mv;
     if (mx + 1 < a.mbw) {
       pf_y = *reinterpret_cast<const uint32_t *>(gy + (mx + 1) * 16);
       if (lane < 32) pf_c = *reinterpret_cast<const uint32_t *>(gc + (mx + 1) * 16);
       n_cmd = a.cmd[mb0 + mx + 1];
       n_cbp = a.cbp[mb0 + mx + 1];
+      if constexpr (PT) n_mv = reinterpret_cast<const uint4 *>(a.mv4)[mb0 + mx + 1];
       load_lv(mx + 1, n_lv);
     }
-    const edb::Mb cur = edb::mb_of_cmd(cmd, edb::nz_raster(static_cast<uint32_t>(__ballot(nzb))));
+    const uint32_t nzr = edb::nz_raster(static_cast<uint32_t>(__ballot(nzb)));
+    const edb::Mb cur = PT ? edb::mb_of_cmd4(cmd, nzr, mv.x, mv.y, mv.z, mv.w) : edb::mb_of_cmd(cmd, nzr);
     __syncthreads();
     bool filtered = false;
 #pragma unroll
@@ -1133,10 +1341,17 @@ __global__ void __launch_bounds__(64) enc_deblock(DeblockArgs a) {
 #pragma unroll
       for (int ed = 0; ed < 4; ++ed) {
         if (ed == 0 && (dir == 1 || mx == 0)) continue;
-        const edb::Mb &p = ed == 0 ? left : cur;
+        [[maybe_unused]] const edb::Mb &p = ed == 0 ? left : cur;
         const bool mine = lane < 16 || (lane < 32 && !(ed & 1));
-        const int bS = mine ? edb::line_bs(p, cur, dir, ed, line) : 0;
-        const int qpp = edb::qp_of(p, a.qp), qpq = edb::qp_of(cur, a.qp);
+        int bS, qpp;
+        if constexpr (PT) {  // left or cur by name, not through p: the larger Mb then stays in registers
+          bS = !mine ? 0 : (ed == 0 ? edb::line_bs<true>(left, cur, dir, ed, line) : edb::line_bs<true>(cur, cur, dir, ed, line));
+          qpp = ed == 0 ? edb::qp_of(left, a.qp) : edb::qp_of(cur, a.qp);
+        } else {
+          bS = mine ? edb::line_bs<false>(p, cur, dir, ed, line) : 0;
+          qpp = edb::qp_of(p, a.qp);
+        }
+        const int qpq = edb::qp_of(cur, a.qp);
         const edb::Idx x = qpp != qpq ? x_mix : (qpp ? x_qp : x_pcm);
         const bool act = bS > 0 && x.alpha && x.beta;
         if (__ballot(act)) {  // wave-uniform
@@ -1233,8 +1448,10 @@ __device__ void pcm_gap(NalOut &o, uint4 *job, int s, int mx) {
 // kIntra: enc_intra ran on every level, so IDR pictures have commands too and
 // a command may be kIntraCmd (the other instance is the encoder without it).
 // kDbk: the slices ask for the in-loop filter inside the slice (enc_deblock
-// ran on the reconstruction); false: the header, and the code, without it
-template <bool kIntra, bool kDbk>
+// ran on the reconstruction); false: the header, and the code, without it.
+// kPart: a command may be a partitioned macroblock's (enc_part.h), its vectors
+// in a.mv4; false: the code is the kernel's without partitions
+template <bool kIntra, bool kDbk, bool kPart>
 __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= a.n_slices) return;
@@ -1251,6 +1468,9 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   const int16_t *coef_row =
       a.coef + ((static_cast<int64_t>(en.y % a.ring) * a.coef_per_level + en.w) * a.mbh + row) * a.mbw * kCoefPerMb;
   const uint64_t *i4r = kIntra && a.i4 ? a.i4 + static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw : nullptr;
+  [[maybe_unused]] const uint32_t *mv4r =
+      kPart ? a.mv4 + (static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw) * 4 : nullptr;
+  [[maybe_unused]] unsigned long long n16x8 = 0, n8x16 = 0, n8x8 = 0;
   const bool all_pcm = idr && !kIntra;  // level 0 without intra holds no commands
   // reserve this slice's I_PCM jobs
   uint32_t njob = 0;
@@ -1279,6 +1499,13 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
     } else if (c == 0 && cbpr[mx] == 0) {  // P_Skip: vector (0, 0), nothing coded
       ecav::mb_skip(z);
       ++nskip;
+    } else if (kPart && ep::is_part_cmd(c)) {
+      ecav::mb_p_part(o, z, c, mv4r + 4 * mx, cbpr[mx], cp);
+      ++ninter;
+      const int shape = ep::part_shape(c);
+      n16x8 += shape == ep::k16x8;
+      n8x16 += shape == ep::k8x16;
+      n8x8 += shape == ep::k8x8;
     } else {
       ecav::mb_inter(o, z, c, cbpr[mx], cp);
       ++ninter;
@@ -1299,6 +1526,11 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   atomicAdd(&a.stats[kStSkip], nskip);
   if (nintra) atomicAdd(&a.stats[kStIntra], nintra);
   if (ni4) atomicAdd(&a.stats[kStI4], ni4);
+  if constexpr (kPart) {
+    if (n16x8) atomicAdd(&a.stats[kStP16x8], n16x8);
+    if (n8x16) atomicAdd(&a.stats[kStP8x16], n8x16);
+    if (n8x8) atomicAdd(&a.stats[kStP8x8], n8x8);
+  }
 }
 
 // The slices with entropy_coding_mode_flag = 1 (vts_transcode_ext4.cabac,
@@ -1319,7 +1551,7 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
 // (downscale clamp), and pcm_gap's argument holds as it does for CAVLC: no
 // emulation prevention byte falls in or next to the samples and the zero run
 // after them is 0.  The encoder restarts behind them (9.3.1.2).
-template <bool kIntra, bool kDbk>
+template <bool kIntra, bool kDbk, bool kPart>
 __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
   namespace ec = full::ecab;
   __shared__ uint8_t st[320];             // ec::kNumCtx context variables
@@ -1353,6 +1585,10 @@ __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
   unsigned long long npcm = 0, ninter = 0, nskip = 0, nintra = 0;
   bool a_ok = false;
   int amx = 0, amy = 0;
+  [[maybe_unused]] int a3x = 0, a3y = 0;  // partitions: the left macroblock's quadrant 3 (amx, amy: its quadrant 1)
+  [[maybe_unused]] const uint32_t *mv4r =
+      kPart ? a.mv4 + (static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw) * 4 : nullptr;
+  [[maybe_unused]] unsigned long long n16x8 = 0, n8x16 = 0, n8x8 = 0;
   if (lane == 0) {
     if (njob) job += atomicAdd(a.n_jobs, njob);
     ec::slice_header(o, idr, row * a.mbw, en.y, en.z, a.qp, kDbk, a.dbk_alpha, a.dbk_beta);
@@ -1385,6 +1621,19 @@ __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
       ec::mb_intra16(enc, idr, left, c, lv, last);
       a_ok = false;
       ++nintra;
+    } else if (kPart && ep::is_part_cmd(c)) {
+      const uint32_t *v = mv4r + 4 * mx;
+      const int shape = ep::part_shape(c);
+      ec::mb_p_part(enc, left, shape, v, ep::Left{a_ok, {amx, amy}, {a3x, a3y}}, cbp, lv, last);
+      ++ninter;
+      n16x8 += shape == ep::k16x8;
+      n8x16 += shape == ep::k8x16;
+      n8x8 += shape == ep::k8x8;
+      a_ok = true;
+      amx = static_cast<int16_t>(v[1] & 0xffffu);
+      amy = static_cast<int16_t>(v[1] >> 16);
+      a3x = static_cast<int16_t>(v[3] & 0xffffu);
+      a3y = static_cast<int16_t>(v[3] >> 16);
     } else {
       const int mvx = static_cast<int16_t>(c & 0xffffu), mvy = static_cast<int16_t>(c >> 16);
       if (mvx == 0 && mvy == 0 && cbp == 0) {  // P_Skip
@@ -1395,8 +1644,8 @@ __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
         ++ninter;
       }
       a_ok = true;
-      amx = mvx;
-      amy = mvy;
+      amx = a3x = mvx;
+      amy = a3y = mvy;
     }
   }
   if (lane != 0) return;
@@ -1416,6 +1665,11 @@ __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
   atomicAdd(&a.stats[kStSkip], nskip);
   if (nintra) atomicAdd(&a.stats[kStIntra], nintra);
   if (ni4) atomicAdd(&a.stats[kStI4], ni4);
+  if constexpr (kPart) {
+    if (n16x8) atomicAdd(&a.stats[kStP16x8], n16x8);
+    if (n8x16) atomicAdd(&a.stats[kStP8x16], n8x16);
+    if (n8x8) atomicAdd(&a.stats[kStP8x8], n8x8);
+  }
 }
 
 // Slice offsets of one level on the device: offs[s] = running output total +
@@ -1530,10 +1784,15 @@ int32_t search_lambda16(int qp, int mv_lambda16) { return er::lambda16(qp, mv_la
 
 // one wave per macroblock; RT: the range compiled in (0: any), SP: subpel,
 // RC: the instances with the rate-aware decisions compiled in
-void launch_enc_search(const SearchArgs &a, int subpel, bool rate_aware, int64_t entries, hipStream_t s) {
+// PT: those with the partitions of enc_part.h on top (they exist with RC only)
+void launch_enc_search(const SearchArgs &a, int subpel, bool rate_aware, bool partitions, int64_t entries, hipStream_t s) {
   const dim3 grid(static_cast<unsigned>(entries * a.nmb));
   with_const<4, 8, 16, 0>(a.range, [&](auto rt) {
     with_const<1, 2, 0>(subpel, [&](auto sp) {
+      if (partitions) {
+        hipLaunchKernelGGL((enc_search<rt(), sp(), true, true>), grid, dim3(64), 0, s, a);
+        return;
+      }
       with_const<1, 0>(rate_aware, [&](auto rc) {
         hipLaunchKernelGGL((enc_search<rt(), sp(), rc() != 0>), grid, dim3(64), 0, s, a);
       });
@@ -1549,7 +1808,9 @@ void launch_enc_intra(const IntraArgs &a, bool intra4x4, int64_t entries, hipStr
 }
 
 void launch_enc_deblock(const DeblockArgs &a, int64_t entries, hipStream_t s) {
-  hipLaunchKernelGGL(enc_deblock, dim3(static_cast<unsigned>(entries * a.mbh)), dim3(64), 0, s, a);
+  with_const<1, 0>(a.mv4 != nullptr, [&](auto pt) {
+    hipLaunchKernelGGL(enc_deblock<pt() != 0>, dim3(static_cast<unsigned>(entries * a.mbh)), dim3(64), 0, s, a);
+  });
 }
 
 // up to 64 workgroups share a picture, 4096 bytes each
@@ -1564,8 +1825,10 @@ void launch_enc_write(const WriteArgs &a, bool cabac, bool intra, bool deblock, 
   const unsigned ns = static_cast<unsigned>(a.n_slices);
   with_const<1, 0>(intra, [&](auto in) {
     with_const<1, 0>(deblock, [&](auto db) {
-      if (cabac) hipLaunchKernelGGL((enc_write_cabac<in() != 0, db() != 0>), dim3(ns), dim3(64), 0, s, a);
-      else hipLaunchKernelGGL((enc_write<in() != 0, db() != 0>), dim3((ns + 63) / 64), dim3(64), 0, s, a);
+      with_const<1, 0>(a.mv4 != nullptr, [&](auto pt) {  // partitions: the level has quadrant vectors
+        if (cabac) hipLaunchKernelGGL((enc_write_cabac<in() != 0, db() != 0, pt() != 0>), dim3(ns), dim3(64), 0, s, a);
+        else hipLaunchKernelGGL((enc_write<in() != 0, db() != 0, pt() != 0>), dim3((ns + 63) / 64), dim3(64), 0, s, a);
+      });
     });
   });
 }

@@ -53,14 +53,19 @@ static_assert(VTS_END_OF(vts_transcode_ext, subpel) == 8 && VTS_END_OF(vts_trans
               VTS_END_OF(vts_transcode_ext3, early_skip) == 36 && VTS_END_OF(vts_transcode_ext3, cmd_out) == 48 &&
               VTS_END_OF(vts_transcode_ext3, cmd_cap) == 56 && VTS_END_OF(vts_transcode_ext4, cabac) == 60 &&
               VTS_END_OF(vts_transcode_ext5, intra4x4) == 68 && VTS_END_OF(vts_transcode_ext5, i4_out) == 80 &&
-              VTS_END_OF(vts_transcode_ext5, i4_cap) == 88,
-              "vts_transcode_ext .. ext5: struct_size >= 8, 12, 16, 20, 28, 32, 36, 48, 56, 60, 68, 80, 88");
+              VTS_END_OF(vts_transcode_ext5, i4_cap) == 88 && VTS_END_OF(vts_transcode_ext6, partitions) == 92 &&
+              VTS_END_OF(vts_transcode_ext6, mv_out) == 104 && VTS_END_OF(vts_transcode_ext6, mv_cap) == 112 &&
+              sizeof(vts_transcode_ext6) == 112,
+              "vts_transcode_ext .. ext6: struct_size >= 8, 12, 16, 20, 28, 32, 36, 48, 56, 60, 68, 80, 88, 92, 104, 112");
 static_assert(VTS_END_OF(vts_transcode_ext_info, _pad) == 8 && VTS_END_OF(vts_transcode_ext_info, subpel_mbs) == 16 &&
               VTS_END_OF(vts_transcode_ext_info, qpel_mbs) == 24 && VTS_END_OF(vts_transcode_ext_info2, deblock_mbs) == 32 &&
               VTS_END_OF(vts_transcode_ext_info3, early_skip_mbs) == 40 &&
               VTS_END_OF(vts_transcode_ext_info3, cmd_words) == 48 &&
-              VTS_END_OF(vts_transcode_ext_info4, intra4x4_mbs) == 56 && VTS_END_OF(vts_transcode_ext_info4, i4_words) == 64,
-              "vts_transcode_ext_info .. info4: struct_size >= 16, 24, 32, 40, 48, 56, 64");
+              VTS_END_OF(vts_transcode_ext_info4, intra4x4_mbs) == 56 && VTS_END_OF(vts_transcode_ext_info4, i4_words) == 64 &&
+              VTS_END_OF(vts_transcode_ext_info5, p16x8_mbs) == 72 && VTS_END_OF(vts_transcode_ext_info5, p8x16_mbs) == 80 &&
+              VTS_END_OF(vts_transcode_ext_info5, p8x8_mbs) == 88 && VTS_END_OF(vts_transcode_ext_info5, mv_words) == 96 &&
+              sizeof(vts_transcode_ext_info5) == 96,
+              "vts_transcode_ext_info .. info5: struct_size >= 16, 24, 32, 40, 48, 56, 64, 72, 80, 88, 96");
 
 // What a vts_transcode_ex call asks for, defaults applied and checked.
 struct TranscodeOpts {
@@ -72,6 +77,9 @@ struct TranscodeOpts {
   int64_t cmd_cap = 0;
   uint64_t *i4_out = nullptr;
   int64_t i4_cap = 0;
+  int partitions = 0;
+  uint32_t *mv_out = nullptr;
+  int64_t mv_cap = 0;
   int rate = 0;         // SearchArgs.rate: mvcost | early_skip << 1
   int sh = 0, R = 0, T = 0, qp = 0, keyint = 0;  // output height, search range, max SAD, residual QP (0: none)
   bool intra = false, idr_at_cuts = false;
@@ -115,6 +123,11 @@ int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_trans
     VTS_EXT_GET(o.i4_out, vts_transcode_ext5, i4_out);
     VTS_EXT_GET(o.i4_cap, vts_transcode_ext5, i4_cap);
     if (o.intra4x4 != 0 && o.intra4x4 != 1) return fail(VTS_E_INVALID, "intra4x4 %d: 0 or 1", o.intra4x4);
+    // vts_transcode_ext6, the same way
+    VTS_EXT_GET(o.partitions, vts_transcode_ext6, partitions);
+    VTS_EXT_GET(o.mv_out, vts_transcode_ext6, mv_out);
+    VTS_EXT_GET(o.mv_cap, vts_transcode_ext6, mv_cap);
+    if (o.partitions != 0 && o.partitions != 1) return fail(VTS_E_INVALID, "partitions %d: 0 or 1", o.partitions);
   }
   o.rate = o.mvcost | (o.early_skip << 1);
   if (xinfo && xinfo->struct_size < VTS_END_OF(vts_transcode_ext_info, _pad))
@@ -129,6 +142,9 @@ int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_trans
   if (p.intra != 0 && p.intra != 1) return fail(VTS_E_INVALID, "intra %d: 0 or 1", p.intra);
   o.intra = p.intra == 1;
   o.hashed = o.intra || o.subpel != 0 || o.deblock || o.rate;
+  if (o.partitions && o.qp < 1) return fail(VTS_E_INVALID, "partitions = 1 needs residual coding (qp >= 0)");
+  if (o.partitions && o.T < 0) return fail(VTS_E_INVALID, "partitions = 1 needs max_mb_sad >= 0 (inter macroblocks)");
+  if (o.partitions && !o.mvcost) return fail(VTS_E_INVALID, "partitions = 1 needs mvcost = 1 (a shape is chosen by rate)");
   if (o.intra4x4 && o.qp < 1) return fail(VTS_E_INVALID, "intra4x4 = 1 needs residual coding (qp >= 0)");
   if (o.intra4x4 && !o.intra) return fail(VTS_E_INVALID, "intra4x4 = 1 needs intra = 1");
   if (o.intra && o.qp < 1) return fail(VTS_E_INVALID, "intra = 1 needs residual coding (qp >= 0)");
@@ -210,6 +226,7 @@ struct Transcoder {
   int mbw = 0, mbh = 0, nmb = 0;
   int64_t cap = 0;           // staging slot per slice
   int64_t cmd_words = 0;     // n * nmb: the command (and Intra4x4PredModes) words of every macroblock
+  int64_t mv_words = 0;      // 4 n * nmb: the quadrant vectors of every macroblock
   int64_t max_chunk = 0;     // entries of the largest chunk
   hipStream_t s1 = nullptr, s2 = nullptr;
   double ms[4] = {0, 0, 0, 0}, mux_ms = 0;
@@ -230,6 +247,7 @@ struct Transcoder {
     uint32_t *cmd;      // [entry][mb], every frame: searches run ahead
     uint8_t *cbp;       // [entry][mb]
     uint64_t *i4;       // intra4x4: [entry][mb] mode words, ~0 where enc_intra<true> writes none
+    uint32_t *mv4;      // partitions: [entry][mb][4] quadrant vectors, every frame as cmd
     int16_t *coef;      // qp >= 1: residual levels, a ring of kRing levels
     uint8_t *stage, *out;        // [max_chunk slices][cap]; the packed chunk
     int64_t *total, *base, *fr;  // running output total; the total before the chunk; per frame: offset, size
@@ -260,12 +278,13 @@ struct Transcoder {
     uint32_t *cmd;
     uint8_t *cbp;
     uint64_t *i4;          // nullptr without intra4x4
+    uint32_t *mv4;         // nullptr without partitions
     int16_t *coef;         // the level's ring slot; nullptr without residual coding
   };
   Level level(int64_t j) const {
     const int64_t e0 = plan.lvl_off[j];
     return {e0, plan.lvl_off[j + 1] - e0, d.sent + e0, d.cmd + e0 * nmb, d.cbp + e0 * nmb,
-            d.i4 ? d.i4 + e0 * nmb : nullptr,
+            d.i4 ? d.i4 + e0 * nmb : nullptr, d.mv4 ? d.mv4 + e0 * nmb * 4 : nullptr,
             d.coef ? d.coef + (j % kRing) * plan.ngop * nmb * kCoefPerMb : nullptr};
   }
   SearchArgs search_args(int64_t j) const;
@@ -308,6 +327,12 @@ int Transcoder::check(vts_transcode_ext_info *xinfo) {
   if (opt.i4_out && opt.i4_cap < cmd_words)
     return fail(VTS_E_CAPACITY, "i4_cap %lld < %lld mode words", static_cast<long long>(opt.i4_cap),
                 static_cast<long long>(cmd_words));
+  // the four quadrant vectors of every macroblock, the same way
+  mv_words = 4 * cmd_words;
+  VTS_XINFO_PUT(vts_transcode_ext_info5, mv_words, mv_words);
+  if (opt.mv_out && opt.mv_cap < mv_words)
+    return fail(VTS_E_CAPACITY, "mv_cap %lld < %lld vector words", static_cast<long long>(opt.mv_cap),
+                static_cast<long long>(mv_words));
   return VTS_OK;
 }
 
@@ -335,6 +360,7 @@ int Transcoder::alloc() {
   VTS_TRY(bufs.get(&d.cmd, entries * nmb));
   VTS_TRY(bufs.get(&d.cbp, entries * nmb));
   if (opt.intra4x4) VTS_TRY(bufs.get(&d.i4, entries * nmb));
+  if (opt.partitions) VTS_TRY(bufs.get(&d.mv4, entries * nmb * 4));
   if (opt.qp >= 1) VTS_TRY(bufs.get(&d.coef, static_cast<size_t>(kRing * plan.ngop * nmb * kCoefPerMb)));
   VTS_TRY(bufs.get(&d.stage, static_cast<size_t>(max_chunk * mbh * cap)));
   VTS_TRY(bufs.get(&d.out, static_cast<size_t>(max_chunk * mbh * cap)));
@@ -361,6 +387,10 @@ int Transcoder::alloc() {
   HIP_TRY(hipMemset(d.stats, 0, kStCount * sizeof(unsigned long long)));
   HIP_TRY(hipMemsetAsync(d.err, 0, sizeof(uint32_t), s2));
   if (opt.intra4x4) HIP_TRY(hipMemsetAsync(d.i4, 0xff, entries * static_cast<size_t>(nmb) * sizeof(uint64_t), s1));
+  // no kernel writes the IDR level's vectors: they read as "no vector", as every intra macroblock's do
+  if (opt.partitions)
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d.mv4), static_cast<int>(kPcmCmdWord),
+                              entries * static_cast<size_t>(nmb) * 4, s1));
   return ev.create(plan.maxlen, n_chunks(plan));
 }
 
@@ -388,6 +418,8 @@ SearchArgs Transcoder::search_args(int64_t j) const {
     a.gop_pos = static_cast<int32_t>(j);
     a.lambda16 = search_lambda16(opt.qp, opt.mv_lambda16);
     a.es_stat = d.stats + kStEarlySkip;
+    a.mv4 = l.mv4;
+    a.mv4_prev = level(j - 1).mv4;
   }
   return a;
 }
@@ -429,6 +461,7 @@ DeblockArgs Transcoder::deblock_args(int64_t j) const {
   a.off_a = 2 * opt.dbk_alpha;
   a.off_b = 2 * opt.dbk_beta;
   a.count = d.stats + kStDeblocked;
+  a.mv4 = l.mv4;
   return a;
 }
 
@@ -468,6 +501,7 @@ WriteArgs Transcoder::write_args(int64_t ck) const {
   a.dbk_alpha = opt.dbk_alpha;
   a.dbk_beta = opt.dbk_beta;
   a.i4 = l.i4;
+  a.mv4 = l.mv4;
   return a;
 }
 
@@ -485,7 +519,7 @@ PackArgs Transcoder::pack_args(int64_t ck) const {
 // filtered): it is not deblocked, and it records no event.
 int Transcoder::enqueue_level(int64_t j) {
   const int64_t ne = level(j).ne;
-  if (j > 0) launch_enc_search(search_args(j), opt.subpel, opt.rate != 0, ne, s1);
+  if (j > 0) launch_enc_search(search_args(j), opt.subpel, opt.rate != 0, opt.partitions != 0, ne, s1);
   if (opt.intra) launch_enc_intra(intra_args(j), opt.intra4x4 != 0, ne, s1);
   if (opt.deblock && (j > 0 || opt.intra)) launch_enc_deblock(deblock_args(j), ne, s1);
   if (opt.hashed) launch_enc_hash(hash_args(j), ne, s1);
@@ -570,9 +604,29 @@ int Transcoder::encode() {
   return VTS_OK;
 }
 
-// cmd_out / i4_out: entry order -> frame order
+// cmd_out / i4_out / mv_out: entry order -> frame order
 int Transcoder::copy_words() {
   const size_t entries = plan.went.size(), per = static_cast<size_t>(nmb);
+  if (opt.mv_out) {
+    // without partitions a macroblock's vectors follow from its command word;
+    // a level the encoder writes no words for, and with partitions every IDR
+    // picture (no search ran on it), holds no vector
+    std::vector<uint32_t> words(entries * per * (opt.partitions ? 4 : 1));
+    HIP_TRY(hipMemcpy(words.data(), opt.partitions ? d.mv4 : d.cmd, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < entries; ++i) {
+      uint32_t *o = opt.mv_out + static_cast<int64_t>(plan.went[i].x) * nmb * 4;
+      if (plan.went[i].y == 0) {
+        std::fill(o, o + 4 * per, kPcmCmdWord);
+      } else if (opt.partitions) {
+        std::memcpy(o, words.data() + i * per * 4, per * 4 * sizeof(uint32_t));
+      } else {
+        for (size_t m = 0; m < per; ++m) {
+          const uint32_t w = words[i * per + m];
+          std::fill(o + 4 * m, o + 4 * m + 4, (w >> 16) == 0x8000u ? kPcmCmdWord : w);  // I_PCM and the intra words
+        }
+      }
+    }
+  }
   if (opt.cmd_out) {  // a level the encoder writes no words for (the I_PCM IDR pictures) is I_PCM
     std::vector<uint32_t> words(entries * per);
     HIP_TRY(hipMemcpy(words.data(), d.cmd, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -656,6 +710,9 @@ int Transcoder::finish(vts_transcode_info *info, vts_transcode_ext_info *xinfo) 
   VTS_XINFO_PUT(vts_transcode_ext_info2, deblock_mbs, on(opt.deblock, st[kStDeblocked]));
   VTS_XINFO_PUT(vts_transcode_ext_info3, early_skip_mbs, on(opt.early_skip, st[kStEarlySkip]));
   VTS_XINFO_PUT(vts_transcode_ext_info4, intra4x4_mbs, on(opt.intra4x4, st[kStI4]));
+  VTS_XINFO_PUT(vts_transcode_ext_info5, p16x8_mbs, on(opt.partitions, st[kStP16x8]));
+  VTS_XINFO_PUT(vts_transcode_ext_info5, p8x16_mbs, on(opt.partitions, st[kStP8x16]));
+  VTS_XINFO_PUT(vts_transcode_ext_info5, p8x8_mbs, on(opt.partitions, st[kStP8x8]));
   return VTS_OK;
 }
 

@@ -177,6 +177,19 @@ class TranscodeExtInfo4(C.Structure):
     _fields_ = [("base", TranscodeExtInfo3), ("intra4x4_mbs", C.c_int64), ("i4_words", C.c_int64)]
 
 
+class TranscodeExt6(C.Structure):
+    """vts_transcode_ext6 (inter partitions): begins with TranscodeExt5; passed by
+    pointer cast with base.base.base.base.base.struct_size = sizeof(TranscodeExt6)."""
+    _fields_ = [("base", TranscodeExt5), ("partitions", C.c_int32), ("_pad4", C.c_int32),
+                ("mv_out", C.POINTER(C.c_uint32)), ("mv_cap", C.c_int64)]
+
+
+class TranscodeExtInfo5(C.Structure):
+    """vts_transcode_ext_info5: begins with TranscodeExtInfo4; as TranscodeExt6."""
+    _fields_ = [("base", TranscodeExtInfo4), ("p16x8_mbs", C.c_int64), ("p8x16_mbs", C.c_int64),
+                ("p8x8_mbs", C.c_int64), ("mv_words", C.c_int64)]
+
+
 class ManifestArgs(C.Structure):
     _fields_ = [("video_id", C.c_char_p), ("segment_dir", C.c_char_p),
                 ("created_at", C.c_char_p), ("duration", C.c_double),

@@ -265,7 +265,8 @@ class VideoScorer:
                   subpel: int = 0, deblock: bool = False,
                   deblock_offsets: tuple[int, int] = (0, 0), mvcost: bool = False,
                   early_skip: bool = False, mv_lambda16: int = 0, want_commands: bool = False,
-                  cabac: bool = False, intra4x4: bool = False, want_intra4_modes: bool = False) -> dict:
+                  cabac: bool = False, intra4x4: bool = False, want_intra4_modes: bool = False,
+                  partitions: bool = False, want_vectors: bool = False) -> dict:
         """360p upload transcode of this video into `out_path`
         (vts_transcode_ex): decode + score + area downscale +
         device H.264 encode with a quantised residual at `qp` (<= 0: none, the
@@ -298,6 +299,15 @@ class VideoScorer:
         `want_intra4_modes`: the result also holds `intra4_modes`, a uint64
         array (n_frames, mbh, mbw): nibble k of an I_NxN macroblock's word is
         the Intra4x4PredMode of luma4x4BlkIdx k, every other word is ~0.
+        `partitions`: the motion search may give a P macroblock a top and a
+        bottom vector (16x8), a left and a right one (8x16) or one per 8x8
+        quadrant (P_8x8) instead of one, chosen by rate (DESIGN.md §11
+        "Partitions"); needs `mvcost` and `qp` > 0; off, every byte is as
+        before; the result then holds `p16x8_mbs`, `p8x16_mbs` and `p8x8_mbs`,
+        shares of `inter_mbs`.  `want_vectors`: the result also holds
+        `vectors`, a uint32 array (n_frames, mbh, mbw, 4): the quadrant vectors
+        of every inter macroblock as mvx | mvy << 16 (a 16x16 macroblock's
+        four times, P_Skip four 0), 0x80008000 for intra and I_PCM ones.
         Returns the facts (with `intra`, `subpel`, `deblock`, `mvcost`
         or `early_skip` also the encoder's `recon_hash`) and per-stage
         milliseconds; with one of the last four keywords also
@@ -313,20 +323,26 @@ class VideoScorer:
         prm.intra = 1 if intra else 0
         info = _lib.TranscodeInfo()
         # the Intra4x4 structs only with their keywords: without them the call is the one it was
+        # ... and the partition structs only with theirs
         i4 = bool(intra4x4 or want_intra4_modes)
-        ext5 = _lib.TranscodeExt5(_lib.TranscodeExt4(_lib.TranscodeExt3(
-            _lib.TranscodeExt2(_lib.TranscodeExt(C.sizeof(_lib.TranscodeExt5 if i4 else _lib.TranscodeExt4), subpel),
+        pt = bool(partitions or want_vectors)
+        ext_t = _lib.TranscodeExt6 if pt else (_lib.TranscodeExt5 if i4 else _lib.TranscodeExt4)
+        info_t = _lib.TranscodeExtInfo5 if pt else (_lib.TranscodeExtInfo4 if i4 else _lib.TranscodeExtInfo3)
+        ext6 = _lib.TranscodeExt6(_lib.TranscodeExt5(_lib.TranscodeExt4(_lib.TranscodeExt3(
+            _lib.TranscodeExt2(_lib.TranscodeExt(C.sizeof(ext_t), subpel),
                                1 if deblock else 0, int(deblock_offsets[0]), int(deblock_offsets[1])),
             1 if mvcost else 0, int(mv_lambda16), 1 if early_skip else 0), 1 if cabac else 0),
-            1 if intra4x4 else 0)
+            1 if intra4x4 else 0), 1 if partitions else 0)
+        ext5 = ext6.base
         ext = ext5.base.base
-        xinfo4 = _lib.TranscodeExtInfo4(_lib.TranscodeExtInfo3(_lib.TranscodeExtInfo2(
-            _lib.TranscodeExtInfo(C.sizeof(_lib.TranscodeExtInfo4 if i4 else _lib.TranscodeExtInfo3)))))
+        xinfo5 = _lib.TranscodeExtInfo5(_lib.TranscodeExtInfo4(_lib.TranscodeExtInfo3(_lib.TranscodeExtInfo2(
+            _lib.TranscodeExtInfo(C.sizeof(info_t))))))
+        xinfo4 = xinfo5.base
         xinfo3 = xinfo4.base
         xinfo2 = xinfo3.base
         xinfo = xinfo2.base
-        commands = modes = None
-        if want_commands or want_intra4_modes:
+        commands = modes = vectors = None
+        if want_commands or want_intra4_modes or want_vectors:
             # the coded macroblock grid of the output: width as ffmpeg's scale=-2, both 16-aligned
             w, h = int(self.info.width), int(self.info.height)
             sw = (height * w + h) // (2 * h) * 2
@@ -339,11 +355,21 @@ class VideoScorer:
             modes = np.zeros((int(self.info.n_frames), mbh, mbw), np.uint64)
             ext5.i4_out = modes.ctypes.data_as(C.POINTER(C.c_uint64))
             ext5.i4_cap = modes.size
+        if want_vectors:
+            vectors = np.zeros((int(self.info.n_frames), mbh, mbw, 4), np.uint32)
+            ext6.mv_out = vectors.ctypes.data_as(C.POINTER(C.c_uint32))
+            ext6.mv_cap = vectors.size
         _lib.check(self._lib.vts_transcode_ex(self._ctx, str(out_path).encode(), C.byref(prm),
-                                              C.cast(C.pointer(ext5), C.POINTER(_lib.TranscodeExt)),
+                                              C.cast(C.pointer(ext6), C.POINTER(_lib.TranscodeExt)),
                                               C.byref(info),
-                                              C.cast(C.pointer(xinfo4), C.POINTER(_lib.TranscodeExtInfo))))
+                                              C.cast(C.pointer(xinfo5), C.POINTER(_lib.TranscodeExtInfo))))
         extra = {}
+        if pt:
+            extra.update(p16x8_mbs=xinfo5.p16x8_mbs, p8x16_mbs=xinfo5.p8x16_mbs, p8x8_mbs=xinfo5.p8x8_mbs)
+        if want_vectors:
+            if xinfo5.mv_words != vectors.size:
+                raise RuntimeError(f"{xinfo5.mv_words} vector words, expected {vectors.size}")
+            extra["vectors"] = vectors
         if i4:
             extra["intra4x4_mbs"] = xinfo4.intra4x4_mbs
         if want_intra4_modes:

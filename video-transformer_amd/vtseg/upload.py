@@ -56,7 +56,7 @@ def compress_video_for_upload(video_path: Path, *, logger: logging.Logger | None
                               intra: bool = False, subpel: int = 0, deblock: bool = False,
                               deblock_offsets: tuple[int, int] = (0, 0), mvcost: bool = False,
                               early_skip: bool = False, cabac: bool = False,
-                              intra4x4: bool = False) -> Path:
+                              intra4x4: bool = False, partitions: bool = False) -> Path:
     """Same decisions and return values as the reference method: the input
     path when it is <= 30 MB, an existing non-empty compressed_<name> as is,
     otherwise the new compressed file, or the input path when compression
@@ -66,7 +66,8 @@ def compress_video_for_upload(video_path: Path, *, logger: logging.Logger | None
     deblocking filter with its two slice offsets; `mvcost` and `early_skip`
     are its rate-aware motion cost and early P_Skip decision, `cabac` its
     CABAC entropy coding (a Main profile stream), `intra4x4` its Intra_4x4
-    coding of intra macroblocks (needs `intra`)."""
+    coding of intra macroblocks (needs `intra`), `partitions` its 16x8 / 8x16 /
+    8x8 inter partitions (needs `mvcost`)."""
     log = logger or logging.getLogger(__name__)
     video_path = Path(video_path)
     file_size_mb = video_path.stat().st_size / (1024 * 1024)
@@ -85,7 +86,7 @@ def compress_video_for_upload(video_path: Path, *, logger: logging.Logger | None
         with VideoScorer(video_path, device=device) as v:
             facts = v.transcode(video_only, intra=intra, subpel=subpel, deblock=deblock,
                                 deblock_offsets=deblock_offsets, mvcost=mvcost, early_skip=early_skip,
-                                cabac=cabac, intra4x4=intra4x4)
+                                cabac=cabac, intra4x4=intra4x4, partitions=partitions)
         # the source's audio / other tracks, stream-copied beside the new video
         _lib.check(_lib.lib().vts_add_tracks(str(video_only).encode(),
                                              str(video_path).encode(), str(out).encode()))
