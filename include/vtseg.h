@@ -671,6 +671,64 @@ typedef struct vts_transcode_ext_info5 {
   int64_t mv_words;        /* 4 * n_frames * macroblocks per picture            */
 } vts_transcode_ext_info5;
 
+/* Per-picture QP and rate control, DESIGN.md §11 "Rate control".  As the
+ * structs above: begun with them, passed by pointer cast, struct_size = their
+ * own sizeof.  Read: bitrate_kbps when struct_size >= 116, qp_min at >= 120,
+ * qp_max at >= 124, frame_qp at >= 136, frame_qp_n at >= 144, qp_out at >= 152,
+ * bits_out at >= 160, frame_cap at >= 168 (a 112-byte vts_transcode_ext6 or
+ * anything smaller: off / NULL); written: qp_sum at >= 104, qp_lo at >= 108,
+ * qp_hi at >= 112, est_bits at >= 120, frame_words at >= 128.
+ * frame_qp: frame f is coded at frame_qp[f] by every stage (the quantiser and
+ * the reconstruction, the early P_Skip probe, lambda16 of the vector cost and
+ * of the Intra_4x4 modes unless mv_lambda16 is given, SliceQPY of the in-loop
+ * filter, slice_qp_delta = frame_qp[f] - 26 and the CABAC context
+ * initialisation); mb_qp_delta stays 0 and the parameter sets do not change.
+ * A constant frame_qp gives the bytes of the same call with that qp.
+ * bitrate_kbps: one controller per GOP sets the QPs on the device
+ * (csrc/enc_ratectl.h).  With B = bitrate_kbps * 1000 * frame duration (floor)
+ * and L the GOP's pictures: picture 0 is coded at clamp(qp), picture 1 at
+ * clamp(qp_0 + 3), picture j + 1 at the QP of picture j moved by at most 4 so
+ * that picture j's measure scaled by 2^(-step / 6) meets (B L - measure so
+ * far) / (L - j - 1); a picture that measured 0 leaves the QP, an overspent
+ * GOP raises it by 4; every QP is clamped to [qp_min, qp_max].  GOPs share no
+ * budget.  The measure of a picture, in bits: P_Skip 0; an inter macroblock
+ * the CAVLC bound of its residual (what the inter / I_PCM decision compares)
+ * plus the bits of its vectors against the search's predictor guess; an
+ * Intra16x16 / I_NxN macroblock its exact macroblock_layer() bits in CAVLC;
+ * I_PCM 3072.  It bounds inter residuals from above and leaves out slice and
+ * macroblock headers of P pictures; no hit tolerance is promised (DESIGN.md
+ * has the measured target / achieved ratios).
+ * qp_out / bits_out are filled with any settings: with both features off
+ * qp_out holds qp everywhere and bits_out 0.
+ * VTS_E_INVALID, the field named: bitrate_kbps outside 0 .. 1 000 000; qp_min
+ * or qp_max outside 1 .. 51 or qp_min > qp_max; either non-zero with both
+ * features off; frame_qp together with bitrate_kbps; frame_qp_n != n_frames;
+ * a frame_qp entry outside 1 .. 51; either feature with qp < 0, with
+ * max_mb_sad < 0 or without mvcost = 1.  VTS_E_CAPACITY before any encoding:
+ * qp_out or bits_out with frame_cap < n_frames.  recon_hash is filled
+ * (mvcost = 1 does that). */
+typedef struct vts_transcode_ext7 {
+  vts_transcode_ext6 base;
+  int32_t bitrate_kbps;    /* 0 off (every output byte as before); 1 .. 1 000 000 */
+  int32_t qp_min;          /* 0 = 10                                            */
+  int32_t qp_max;          /* 0 = 51                                            */
+  int32_t _pad5;
+  const uint8_t *frame_qp; /* NULL, or frame_qp_n QPs, each 1 .. 51             */
+  int64_t frame_qp_n;      /* must equal n_frames                               */
+  uint8_t *qp_out;         /* NULL, or frame_cap bytes: the QP of each frame    */
+  uint32_t *bits_out;      /* NULL, or frame_cap words: its rate measure        */
+  int64_t frame_cap;       /* entries each of the two holds                     */
+} vts_transcode_ext7;
+
+typedef struct vts_transcode_ext_info6 {
+  vts_transcode_ext_info5 base;
+  int64_t qp_sum;          /* sum of the frames' QPs                            */
+  int32_t qp_lo;           /* lowest QP used                                    */
+  int32_t qp_hi;           /* highest QP used                                   */
+  int64_t est_bits;        /* sum of the measure; 0 with both features off      */
+  int64_t frame_words;     /* n_frames                                          */
+} vts_transcode_ext_info6;
+
 /* vts_transcode with the settings of `ext` (NULL: none) and the further facts
  * in `ext_info` (NULL: not wanted).  vts_transcode(c, o, p, i) is
  * vts_transcode_ex(c, o, p, NULL, i, NULL). */

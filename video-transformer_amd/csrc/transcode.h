@@ -50,6 +50,11 @@ struct SearchArgs {
   // PT only (enc_part.h)
   uint32_t *mv4;                 // [entry][mb][4] the quadrant vectors, kNoMv four times where not inter
   const uint32_t *mv4_prev;      // the previous level's, as cmd_prev
+  // RC only (vts_transcode_ext7; NULL: off, and qp / lambda16 above hold)
+  const uint8_t *qp_f;           // [frame] the QP of each picture: read in place of qp, lambda16 follows it
+  uint32_t *est_f;               // [frame] the rate measure, bits: the final decisions of this kernel add into it
+  int32_t mv_lambda16;           // qp_f: the caller's lambda16 (> 0 replaces the table's at every QP)
+  int32_t pcm_bits;              // est_f: what a macroblock left as I_PCM adds (0 with intra: enc_intra decides it)
 };
 
 // ------------------------------------------------------ slice writer
@@ -74,6 +79,7 @@ struct WriteArgs {
   int32_t dbk_alpha, dbk_beta, _pad;  // enc_write<., true>: slice_alpha_c0_offset_div2, slice_beta_offset_div2
   const uint64_t *i4;   // [entry][mb] the Intra4x4PredModes of the I_NxN macroblocks (intra4x4; else unread)
   const uint32_t *mv4;  // [entry][mb][4] the quadrant vectors (partitions; else NULL and unread)
+  const uint8_t *qp_f;  // [frame] NULL, or the QP of each picture in place of qp (vts_transcode_ext7)
 };
 
 // ------------------------------------------------------ intra coding
@@ -90,6 +96,8 @@ struct IntraArgs {
   int32_t all;          // 1: every macroblock is a candidate and dst is unwritten (level 0, the IDR
                         // pictures); 0: the macroblocks enc_search left as kPcmCmd (dst holds the source)
   uint64_t *i4;         // enc_intra<true>: [entry][mb] the Intra4x4PredModes of an I_NxN macroblock, else ~0
+  const uint8_t *qp_f;  // [frame] NULL, or the QP of each picture in place of qp (vts_transcode_ext7)
+  uint32_t *est_f;      // [frame] NULL, or the rate measure: the bits of the macroblocks decided here are added
 };
 
 // ------------------------------------------------------ in-loop deblocking
@@ -104,6 +112,21 @@ struct DeblockArgs {
   int32_t qp, off_a, off_b, _pad;  // SliceQPY, FilterOffsetA, FilterOffsetB
   unsigned long long *count;       // macroblocks with a filtered line
   const uint32_t *mv4;             // [entry][mb][4] the quadrant vectors (partitions; else NULL and unread)
+  const uint8_t *qp_f;             // [frame] NULL, or the SliceQPY of each picture in place of qp (vts_transcode_ext7)
+};
+
+// ------------------------------------------------------ rate control
+// enc_rc (enc_ratectl.h) behind level j, one thread per entry of level j + 1:
+// the GOP's running sum takes picture j's measure, the next picture's QP is set
+struct RcArgs {
+  const int4 *ent;         // level j + 1's search entries: (frame, -, dst slot = 2 GOP + parity, -)
+  int32_t n_ent, gop_pos;  // its entries; j, the position of the pictures just coded
+  uint8_t *qp_f;           // [frame]
+  const uint32_t *est_f;   // [frame]
+  int64_t *spent;          // [GOP] the measure of the GOP's pictures so far
+  const int32_t *gop_len;  // [GOP] its pictures
+  int64_t frame_bits;      // B (enc_ratectl.h frame_budget)
+  int32_t qp_min, qp_max;
 };
 
 // ------------------------------------------------------ host-side only
@@ -140,6 +163,7 @@ struct PackArgs {
 void launch_enc_search(const SearchArgs &a, int subpel, bool rate_aware, bool partitions, int64_t entries, hipStream_t s);
 void launch_enc_intra(const IntraArgs &a, bool intra4x4, int64_t entries, hipStream_t s);
 void launch_enc_deblock(const DeblockArgs &a, int64_t entries, hipStream_t s);
+void launch_enc_rc(const RcArgs &a, hipStream_t s);
 void launch_enc_hash(const HashArgs &a, int64_t entries, hipStream_t s);
 void launch_enc_write(const WriteArgs &a, bool cabac, bool intra, bool deblock, hipStream_t s);  // a.n_slices slices
 void launch_enc_pack(const PackArgs &a, int64_t entries, int32_t nmb, hipStream_t s);
@@ -148,6 +172,7 @@ void launch_enc_pack(const PackArgs &a, int64_t entries, int32_t nmb, hipStream_
 // (transcode.hip asserts the two words against those headers)
 constexpr uint32_t kPcmCmdWord = 0x80008000u;  // the command word of an I_PCM macroblock (enc_deblock.h kPcmCmd)
 constexpr uint64_t kNoI4Modes = ~0ull;         // the mode word of a macroblock that is not I_NxN (enc_intra4.h kNoModes)
+constexpr int32_t kPcmMbBits = 3072;           // the rate measure of an I_PCM macroblock: its payload (kPcmBits)
 int64_t slice_slot_bytes(int mbw, bool cabac);    // staging slot of one slice (a macroblock row)
 int32_t search_lambda16(int qp, int mv_lambda16);  // SearchArgs.lambda16 (enc_rate.h lambda16)
 

@@ -28,6 +28,9 @@
 //      `enc_write_cabac` — one wave per slice writes it as CABAC through
 //      enc_cabac.h instead); `enc_scan` — device offsets;
 //      `enc_gather` + `enc_pcm` — packed output, one D2H copy per chunk;
+//      opt-in (vts_transcode_ext7): every stage reads a picture's QP from a
+//      per-frame array, and with a bitrate `enc_rc` — one thread per GOP
+//      between two levels sets the next picture's QP (enc_ratectl.h);
 //   4. host: MP4 mux (Mp4Writer) in display order.
 #include <hip/hip_runtime.h>
 
@@ -39,6 +42,7 @@
 #include "enc_deblock.h"
 #include "enc_part.h"
 #include "enc_rate.h"
+#include "enc_ratectl.h"
 #include "recon_full.h"
 #include "transcode.h"
 
@@ -678,6 +682,8 @@ struct MbOut {
   uint16_t pc, suv;
   uint32_t mvw;  // the vector's word, mvx | mvy << 16
   int frac;      // mvx | mvy
+  int frame;     // RC: the picture's frame number
+  int mvbits;    // RC: the bits of the vectors the macroblock codes, against the predictor guess
 };
 // the macroblock's words: inter with its vector, else I_PCM
 template <int SP>
@@ -701,7 +707,10 @@ __device__ __forceinline__ void finish_plain(const SearchArgs &a, int lane, cons
 // out, then lanes 16 / 17 the chroma DC levels and 24 / 25 their bits; inter
 // when the residual's CAVLC bound is within an I_PCM payload, else I_PCM;
 // returned: inter
-template <int SP>
+// RC: the macroblock's share of the picture's rate measure (a.est_f; NULL:
+// none) is added: P_Skip 0, inter the bound plus its vectors' bits, I_PCM
+// a.pcm_bits; false: the code is the epilogue's without it
+template <int SP, bool RC = false>
 __device__ __forceinline__ bool finish_residual(const SearchArgs &a, int lane, const MbOut &o, const uint32_t *srcy, MbPred &P) {
   __shared__ uint32_t recy[64];
   __shared__ uint8_t recc[2][64];
@@ -759,6 +768,12 @@ __device__ __forceinline__ bool finish_residual(const SearchArgs &a, int lane, c
     store_chroma_levels(cp, lane, lv, dcl);
   }
   if (lane == 0) write_words<SP>(a, o, inter, cbp);
+  if constexpr (RC) {
+    if (a.est_f && lane == 0) {
+      const int est = !inter ? a.pcm_bits : (cbp == 0 && o.mvw == 0 ? 0 : contrib + o.mvbits);
+      if (est) atomicAdd(a.est_f + o.frame, static_cast<uint32_t>(est));
+    }
+  }
   return inter;
 }
 
@@ -766,7 +781,9 @@ __device__ __forceinline__ bool finish_residual(const SearchArgs &a, int lane, c
 // SP: sub-sample refinement around the integer winner, 0 none (the code is
 // the integer-only kernel's), 1 half samples, 2 half then quarter samples.
 // RC: the rate-aware decisions of enc_rate.h, each switched by a bit of
-// a.rate (wave-uniform); false: the code is the kernel's without them.  Every
+// a.rate (wave-uniform), and with them the per-picture QP and the rate measure
+// of vts_transcode_ext7 (a.qp_f, a.est_f; NULL: off, a runtime test each);
+// false: the code is the kernel's without them.  Every
 // instance asks for 5 waves/SIMD: they fit (88 .. 90 VGPRs, no scratch), but
 // left to itself the register allocator settles at 98 .. 102 and 4 waves.
 // PT (with RC only): the inter partitions of enc_part.h.  The integer stage
@@ -799,6 +816,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT ? 4 
   srcy[lane] = *reinterpret_cast<const uint32_t *>(src + luma_off(a, lane, mx, my));
   SearchKey<RC> key;
   if constexpr (RC) {
+    o.frame = en.x;
+    o.mvbits = 0;
+    if (a.qp_f) {  // wave-uniform: the picture's own QP, and the lambda that follows it
+      a.qp = a.qp_f[en.x];
+      a.lambda16 = er::lambda16(a.qp, a.mv_lambda16);
+    }
     const bool coded = a.qp >= 1 && a.max_sad >= 0;
     if (coded && (a.rate & 2) && probe_skip(a, lane, o.mbi, mx, my, src, ref, o.dst, srcy, P)) {
       if constexpr (PT)
@@ -855,7 +878,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT ? 4 
     o.co = chroma_off(a, lane, mx, my);
     o.suv = *reinterpret_cast<const uint16_t *>(src + o.co);
     o.lo = luma_off(a, lane, mx, my);
-    const bool inter = finish_residual<SP>(a, lane, o, srcy, P);
+    if (a.est_f) {  // wave-uniform: the measure is on; the vectors the canonical shape codes
+      for (int i = 0; i < ep::shape_blocks(cshape); ++i) {
+        const int q = ep::part_quad(cshape, i);
+        const ep::Mv v = ep::mv_of_word(q == 0 ? qv[0] : (q == 1 ? qv[1] : (q == 2 ? qv[2] : qv[3])));
+        o.mvbits += er::mv_bits(v.x - key.p.x, v.y - key.p.y);
+      }
+    }
+    const bool inter = finish_residual<SP, true>(a, lane, o, srcy, P);
     if (lane < 4) a.mv4[o.mbi * 4 + lane] = !inter ? ep::kNoMv : (lane == 0 ? qv[0] : (lane == 1 ? qv[1] : (lane == 2 ? qv[2] : qv[3])));
     return;
   }
@@ -865,6 +895,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT ? 4 
   const int mvx = 4 * w.dx + cqx, mvy = 4 * w.dy + cqy;
   o.mvw = static_cast<uint32_t>(static_cast<uint16_t>(mvx)) | (static_cast<uint32_t>(static_cast<uint16_t>(mvy)) << 16);
   o.frac = mvx | mvy;
+  if constexpr (RC)
+    if (a.est_f) o.mvbits = er::mv_bits(mvx - key.p.x, mvy - key.p.y);  // wave-uniform: the measure is on
   // the macroblock's cost at that vector: luma and chroma SAD
   o.sy4 = srcy[lane];
   uint32_t cost = __builtin_amdgcn_sad_u8(o.py, o.sy4, 0);
@@ -877,7 +909,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT ? 4 
   for (int off = 32; off > 0; off >>= 1) cost += __shfl_xor(cost, off);
   o.lo = luma_off(a, lane, mx, my);
   if (a.qp < 1 || a.max_sad < 0) finish_plain<SP>(a, lane, o, cost);
-  else finish_residual<SP>(a, lane, o, srcy, P);
+  else finish_residual<SP, RC>(a, lane, o, srcy, P);
 }
 
 // ------------------------------------------------------ slice writer
@@ -929,8 +961,9 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
   const uint8_t *src = a.small + static_cast<int64_t>(en.x) * a.stride;
   uint8_t *dst = a.recon + static_cast<int64_t>(en.z) * a.stride;
   const int64_t mb0 = (static_cast<int64_t>(e) * a.mbh + my) * a.mbw;
-  const int qp = a.qp, qpc = kQpcTab[qp];
+  const int qp = a.qp_f ? a.qp_f[en.x] : a.qp, qpc = kQpcTab[qp];  // wave-uniform: the picture's own QP when given
   const int ly = lane >> 2, lx = 4 * (lane & 3), ci = lane & 7, cj = lane >> 3;
+  uint32_t row_bits = 0;  // the rate measure of the macroblocks this wave decides (a.est_f)
   if (lane < 4) lnz[lane] = -1;
   if (lane < 4) lnzc[lane >> 1][lane & 1] = -1;
   bool left_mine = false;  // the left macroblock was coded by this wave: its column is in left_y / left_c
@@ -1182,6 +1215,7 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
       __syncthreads();
     }
     const bool intra = contrib <= kPcmBits;  // wave-uniform
+    row_bits += static_cast<uint32_t>(intra ? contrib : kPcmBits);
     if constexpr (kI4) {
       if (intra && use4) {
         // I_NxN: luma is reconstructed (recy, above); chroma as Intra16x16; luma levels in the inter layout
@@ -1249,6 +1283,7 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
     left_mine = true;
     __syncthreads();
   }
+  if (a.est_f && lane == 0 && row_bits) atomicAdd(a.est_f + en.x, row_bits);
 }
 
 // ------------------------------------------------------ in-loop deblocking
@@ -1283,6 +1318,7 @@ __global__ void __launch_bounds__(64) enc_deblock(DeblockArgs a) {
   const int lane = threadIdx.x;
   const int e = blockIdx.x / a.mbh, my = blockIdx.x % a.mbh;
   const int4 en = a.ent[e];
+  const int qp = a.qp_f ? a.qp_f[en.x] : a.qp;  // SliceQPY; wave-uniform: the picture's own when given
   uint8_t *dst = a.recon + static_cast<int64_t>(en.z) * a.stride;
   const int64_t mb0 = (static_cast<int64_t>(e) * a.mbh + my) * a.mbw;
   // loads and stores: lane (r, q4) moves dword q4 of luma row r and, below 32, of chroma row r
@@ -1312,8 +1348,8 @@ __global__ void __launch_bounds__(64) enc_deblock(DeblockArgs a) {
   // indexA, alpha' and beta' of this lane's plane for the three qPav an edge can have (qP is 0 for
   // I_PCM and the slice QP otherwise), looked up once: both sides I_PCM, one side, neither
   const edb::Idx x_pcm = edb::indices(0, 0, a.off_a, a.off_b, chroma, 0);
-  const edb::Idx x_mix = edb::indices(0, a.qp, a.off_a, a.off_b, chroma, 0);
-  const edb::Idx x_qp = edb::indices(a.qp, a.qp, a.off_a, a.off_b, chroma, 0);
+  const edb::Idx x_mix = edb::indices(0, qp, a.off_a, a.off_b, chroma, 0);
+  const edb::Idx x_qp = edb::indices(qp, qp, a.off_a, a.off_b, chroma, 0);
   uint32_t carry = 0;  // lanes 0..23: the row's last dword of the macroblock to the left
   edb::Mb left = edb::mb_of_cmd(kPcmCmd, 0);
   bool prev_filtered = false;  // wave-uniform
@@ -1346,12 +1382,12 @@ __global__ void __launch_bounds__(64) enc_deblock(DeblockArgs a) {
         int bS, qpp;
         if constexpr (PT) {  // left or cur by name, not through p: the larger Mb then stays in registers
           bS = !mine ? 0 : (ed == 0 ? edb::line_bs<true>(left, cur, dir, ed, line) : edb::line_bs<true>(cur, cur, dir, ed, line));
-          qpp = ed == 0 ? edb::qp_of(left, a.qp) : edb::qp_of(cur, a.qp);
+          qpp = ed == 0 ? edb::qp_of(left, qp) : edb::qp_of(cur, qp);
         } else {
           bS = mine ? edb::line_bs<false>(p, cur, dir, ed, line) : 0;
-          qpp = edb::qp_of(p, a.qp);
+          qpp = edb::qp_of(p, qp);
         }
-        const int qpq = edb::qp_of(cur, a.qp);
+        const int qpq = edb::qp_of(cur, qp);
         const edb::Idx x = qpp != qpq ? x_mix : (qpp ? x_qp : x_pcm);
         const bool act = bS > 0 && x.alpha && x.beta;
         if (__ballot(act)) {  // wave-uniform
@@ -1458,10 +1494,11 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   const int e = s / a.mbh, row = s % a.mbh;
   const int4 en = a.ent[e];
   const bool idr = en.y == 0;  // GOP position 0
+  const int qp = a.qp_f ? a.qp_f[en.x] : a.qp;  // the picture's own QP when given
   uint8_t *slot = a.staging + static_cast<int64_t>(s) * a.cap;
   NalOut o = full::erbsp::word_sink(reinterpret_cast<uint32_t *>(slot + 4), a.cap - 4);
   // slice_qp_delta: SliceQPY = the residual's QP; every picture is a reference
-  full::erbsp::slice_header(o, false, idr, row * a.mbw, en.y, en.z, a.qp >= 1 ? a.qp - 26 : 0, kDbk, a.dbk_alpha, a.dbk_beta);
+  full::erbsp::slice_header(o, false, idr, row * a.mbw, en.y, en.z, qp >= 1 ? qp - 26 : 0, kDbk, a.dbk_alpha, a.dbk_beta);
   unsigned long long npcm = 0, ninter = 0, nskip = 0, nintra = 0, ni4 = 0;
   const uint32_t *cmd = a.cmd + static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw;
   const uint8_t *cbpr = a.cbp + static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw;
@@ -1561,7 +1598,8 @@ __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
   const int e = s / a.mbh, row = s % a.mbh;
   const int4 en = a.ent[e];
   const bool idr = en.y == 0;
-  for (int i = lane; i < ec::kNumCtx; i += 64) st[i] = ec::init_context(i, idr, a.qp);
+  const int qp = a.qp_f ? a.qp_f[en.x] : a.qp;  // SliceQPY; wave-uniform: the picture's own when given
+  for (int i = lane; i < ec::kNumCtx; i += 64) st[i] = ec::init_context(i, idr, qp);
   const uint32_t *cmd = a.cmd + static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw;
   const uint8_t *cbpr = a.cbp + static_cast<int64_t>(e) * a.mbw * a.mbh + static_cast<int64_t>(row) * a.mbw;
   const int16_t *coef_row =
@@ -1591,7 +1629,7 @@ __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
   [[maybe_unused]] unsigned long long n16x8 = 0, n8x16 = 0, n8x8 = 0;
   if (lane == 0) {
     if (njob) job += atomicAdd(a.n_jobs, njob);
-    ec::slice_header(o, idr, row * a.mbw, en.y, en.z, a.qp, kDbk, a.dbk_alpha, a.dbk_beta);
+    ec::slice_header(o, idr, row * a.mbw, en.y, en.z, qp, kDbk, a.dbk_alpha, a.dbk_beta);
   }
   const int16_t *lv = reinterpret_cast<const int16_t *>(lvw);
   for (int mx = 0; mx < a.mbw; ++mx) {
@@ -1751,6 +1789,22 @@ __global__ void __launch_bounds__(64) enc_pcm(const uint4 *jobs, const uint32_t 
   }
 }
 
+// The rate controllers (vts_transcode_ext7.bitrate_kbps; enc_ratectl.h), one
+// per GOP, behind level j on the search stream: thread t takes entry t of
+// level j + 1, whose previous picture is frame - 1 of the same GOP.  A GOP's
+// state is touched by its own thread alone; stream order is all the ordering.
+__global__ void __launch_bounds__(64) enc_rc(RcArgs a) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= a.n_ent) return;
+  const int4 en = a.ent[t];
+  const int g = en.z >> 1;
+  const int64_t bits = a.est_f[en.x - 1];
+  const int64_t spent = a.spent[g] + bits;
+  a.spent[g] = spent;
+  a.qp_f[en.x] = static_cast<uint8_t>(
+      full::erc::next_qp(a.frame_bits, a.gop_len[g], a.gop_pos, spent, bits, a.qp_f[en.x - 1], a.qp_min, a.qp_max));
+}
+
 
 // f(std::integral_constant<int, V>{}) for the V that equals v; the last V
 // stands for every other value.  The launch functions below pick their
@@ -1769,6 +1823,7 @@ void with_const(int v, F &&f) {
 
 // ------------------------------------------------------------ launches
 static_assert(kPcmCmdWord == kPcmCmd && kNoI4Modes == ei4::kNoModes, "transcode.h restates the kernels' two words");
+static_assert(kPcmMbBits == kPcmBits, "... and the I_PCM payload's bits");
 
 // An I_PCM macroblock is < 400 bytes, and so is an inter one (its residual is
 // coded only under a 3072-bit bound); the rest is headroom for emulation
@@ -1811,6 +1866,10 @@ void launch_enc_deblock(const DeblockArgs &a, int64_t entries, hipStream_t s) {
   with_const<1, 0>(a.mv4 != nullptr, [&](auto pt) {
     hipLaunchKernelGGL(enc_deblock<pt() != 0>, dim3(static_cast<unsigned>(entries * a.mbh)), dim3(64), 0, s, a);
   });
+}
+
+void launch_enc_rc(const RcArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(enc_rc, dim3(static_cast<unsigned>((a.n_ent + 63) / 64)), dim3(64), 0, s, a);
 }
 
 // up to 64 workgroups share a picture, 4096 bytes each

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "enc_plan.h"
+#include "enc_ratectl.h"
 #include "mp4.h"
 #include "session.h"
 #include "transcode.h"
@@ -57,6 +58,16 @@ static_assert(VTS_END_OF(vts_transcode_ext, subpel) == 8 && VTS_END_OF(vts_trans
               VTS_END_OF(vts_transcode_ext6, mv_out) == 104 && VTS_END_OF(vts_transcode_ext6, mv_cap) == 112 &&
               sizeof(vts_transcode_ext6) == 112,
               "vts_transcode_ext .. ext6: struct_size >= 8, 12, 16, 20, 28, 32, 36, 48, 56, 60, 68, 80, 88, 92, 104, 112");
+static_assert(VTS_END_OF(vts_transcode_ext7, bitrate_kbps) == 116 && VTS_END_OF(vts_transcode_ext7, qp_min) == 120 &&
+              VTS_END_OF(vts_transcode_ext7, qp_max) == 124 && VTS_END_OF(vts_transcode_ext7, frame_qp) == 136 &&
+              VTS_END_OF(vts_transcode_ext7, frame_qp_n) == 144 && VTS_END_OF(vts_transcode_ext7, qp_out) == 152 &&
+              VTS_END_OF(vts_transcode_ext7, bits_out) == 160 && VTS_END_OF(vts_transcode_ext7, frame_cap) == 168 &&
+              sizeof(vts_transcode_ext7) == 168,
+              "vts_transcode_ext7: struct_size >= 116, 120, 124, 136, 144, 152, 160, 168");
+static_assert(VTS_END_OF(vts_transcode_ext_info6, qp_sum) == 104 && VTS_END_OF(vts_transcode_ext_info6, qp_lo) == 108 &&
+              VTS_END_OF(vts_transcode_ext_info6, qp_hi) == 112 && VTS_END_OF(vts_transcode_ext_info6, est_bits) == 120 &&
+              VTS_END_OF(vts_transcode_ext_info6, frame_words) == 128 && sizeof(vts_transcode_ext_info6) == 128,
+              "vts_transcode_ext_info6: struct_size >= 104, 108, 112, 120, 128");
 static_assert(VTS_END_OF(vts_transcode_ext_info, _pad) == 8 && VTS_END_OF(vts_transcode_ext_info, subpel_mbs) == 16 &&
               VTS_END_OF(vts_transcode_ext_info, qpel_mbs) == 24 && VTS_END_OF(vts_transcode_ext_info2, deblock_mbs) == 32 &&
               VTS_END_OF(vts_transcode_ext_info3, early_skip_mbs) == 40 &&
@@ -80,6 +91,13 @@ struct TranscodeOpts {
   int partitions = 0;
   uint32_t *mv_out = nullptr;
   int64_t mv_cap = 0;
+  int bitrate_kbps = 0, qp_min = 0, qp_max = 0;  // rate control (enc_ratectl.h); the bounds with their defaults applied
+  const uint8_t *frame_qp = nullptr;             // the caller's QP of each frame
+  int64_t frame_qp_n = 0;
+  uint8_t *qp_out = nullptr;
+  uint32_t *bits_out = nullptr;
+  int64_t frame_cap = 0;
+  bool per_frame = false;  // frame_qp or bitrate_kbps: the kernels read a QP per picture and measure its rate
   int rate = 0;         // SearchArgs.rate: mvcost | early_skip << 1
   int sh = 0, R = 0, T = 0, qp = 0, keyint = 0;  // output height, search range, max SAD, residual QP (0: none)
   bool intra = false, idr_at_cuts = false;
@@ -128,6 +146,36 @@ int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_trans
     VTS_EXT_GET(o.mv_out, vts_transcode_ext6, mv_out);
     VTS_EXT_GET(o.mv_cap, vts_transcode_ext6, mv_cap);
     if (o.partitions != 0 && o.partitions != 1) return fail(VTS_E_INVALID, "partitions %d: 0 or 1", o.partitions);
+    // vts_transcode_ext7, the same way
+    VTS_EXT_GET(o.bitrate_kbps, vts_transcode_ext7, bitrate_kbps);
+    VTS_EXT_GET(o.qp_min, vts_transcode_ext7, qp_min);
+    VTS_EXT_GET(o.qp_max, vts_transcode_ext7, qp_max);
+    VTS_EXT_GET(o.frame_qp, vts_transcode_ext7, frame_qp);
+    VTS_EXT_GET(o.frame_qp_n, vts_transcode_ext7, frame_qp_n);
+    VTS_EXT_GET(o.qp_out, vts_transcode_ext7, qp_out);
+    VTS_EXT_GET(o.bits_out, vts_transcode_ext7, bits_out);
+    VTS_EXT_GET(o.frame_cap, vts_transcode_ext7, frame_cap);
+    if (o.bitrate_kbps < 0 || o.bitrate_kbps > full::erc::kMaxKbps)
+      return fail(VTS_E_INVALID, "bitrate_kbps %d: 0 .. %d", o.bitrate_kbps, full::erc::kMaxKbps);
+    if (o.qp_min < 0 || o.qp_min > 51) return fail(VTS_E_INVALID, "qp_min %d: 0 (default) or 1 .. 51", o.qp_min);
+    if (o.qp_max < 0 || o.qp_max > 51) return fail(VTS_E_INVALID, "qp_max %d: 0 (default) or 1 .. 51", o.qp_max);
+    o.per_frame = o.bitrate_kbps != 0 || o.frame_qp != nullptr;
+    if (!o.per_frame && o.qp_min) return fail(VTS_E_INVALID, "qp_min %d without bitrate_kbps or frame_qp", o.qp_min);
+    if (!o.per_frame && o.qp_max) return fail(VTS_E_INVALID, "qp_max %d without bitrate_kbps or frame_qp", o.qp_max);
+    if (o.per_frame) {
+      if (!o.qp_min) o.qp_min = full::erc::kQpMinDefault;
+      if (!o.qp_max) o.qp_max = full::erc::kQpMaxDefault;
+      if (o.qp_min > o.qp_max) return fail(VTS_E_INVALID, "qp_min %d > qp_max %d", o.qp_min, o.qp_max);
+    }
+    if (o.frame_qp && o.bitrate_kbps) return fail(VTS_E_INVALID, "frame_qp together with bitrate_kbps %d", o.bitrate_kbps);
+    if (o.frame_qp) {
+      if (o.frame_qp_n != c->n_frames)
+        return fail(VTS_E_INVALID, "frame_qp_n %lld: the video has %lld frames", static_cast<long long>(o.frame_qp_n),
+                    static_cast<long long>(c->n_frames));
+      for (int64_t f = 0; f < o.frame_qp_n; ++f)
+        if (o.frame_qp[f] < 1 || o.frame_qp[f] > 51)
+          return fail(VTS_E_INVALID, "frame_qp[%lld] %d: 1 .. 51", static_cast<long long>(f), o.frame_qp[f]);
+    }
   }
   o.rate = o.mvcost | (o.early_skip << 1);
   if (xinfo && xinfo->struct_size < VTS_END_OF(vts_transcode_ext_info, _pad))
@@ -145,6 +193,10 @@ int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_trans
   if (o.partitions && o.qp < 1) return fail(VTS_E_INVALID, "partitions = 1 needs residual coding (qp >= 0)");
   if (o.partitions && o.T < 0) return fail(VTS_E_INVALID, "partitions = 1 needs max_mb_sad >= 0 (inter macroblocks)");
   if (o.partitions && !o.mvcost) return fail(VTS_E_INVALID, "partitions = 1 needs mvcost = 1 (a shape is chosen by rate)");
+  const char *pf = o.bitrate_kbps ? "bitrate_kbps" : "frame_qp";
+  if (o.per_frame && o.qp < 1) return fail(VTS_E_INVALID, "%s needs residual coding (qp >= 0)", pf);
+  if (o.per_frame && o.T < 0) return fail(VTS_E_INVALID, "%s needs max_mb_sad >= 0 (inter macroblocks)", pf);
+  if (o.per_frame && !o.mvcost) return fail(VTS_E_INVALID, "%s needs mvcost = 1", pf);
   if (o.intra4x4 && o.qp < 1) return fail(VTS_E_INVALID, "intra4x4 = 1 needs residual coding (qp >= 0)");
   if (o.intra4x4 && !o.intra) return fail(VTS_E_INVALID, "intra4x4 = 1 needs intra = 1");
   if (o.intra && o.qp < 1) return fail(VTS_E_INVALID, "intra = 1 needs residual coding (qp >= 0)");
@@ -257,6 +309,10 @@ struct Transcoder {
     uint32_t *err;
     uint4 *jobs;                 // I_PCM payload jobs of a chunk
     uint32_t *njobs;
+    uint8_t *qp_f;               // per_frame: [frame] the QP each picture is coded at
+    uint32_t *est_f;             // per_frame: [frame] the rate measure
+    int64_t *rc_spent;           // bitrate_kbps: [GOP] the measure of its pictures so far
+    int32_t *rc_len;             // bitrate_kbps: [GOP] its pictures
   } d{};
   Events ev;  // destroyed before `bufs` drains and frees
   int64_t next_search = 1;
@@ -268,6 +324,7 @@ struct Transcoder {
   int check(vts_transcode_ext_info *xinfo);
   int decode();
   int alloc();
+  int alloc_rate();
   int encode();
   int finish(vts_transcode_info *info, vts_transcode_ext_info *xinfo);
 
@@ -333,6 +390,14 @@ int Transcoder::check(vts_transcode_ext_info *xinfo) {
   if (opt.mv_out && opt.mv_cap < mv_words)
     return fail(VTS_E_CAPACITY, "mv_cap %lld < %lld vector words", static_cast<long long>(opt.mv_cap),
                 static_cast<long long>(mv_words));
+  // the QP and the rate measure of every frame, the same way
+  VTS_XINFO_PUT(vts_transcode_ext_info6, frame_words, n);
+  if (opt.qp_out && opt.frame_cap < n)
+    return fail(VTS_E_CAPACITY, "frame_cap %lld < %lld frames (qp_out)", static_cast<long long>(opt.frame_cap),
+                static_cast<long long>(n));
+  if (opt.bits_out && opt.frame_cap < n)
+    return fail(VTS_E_CAPACITY, "frame_cap %lld < %lld frames (bits_out)", static_cast<long long>(opt.frame_cap),
+                static_cast<long long>(n));
   return VTS_OK;
 }
 
@@ -388,10 +453,39 @@ int Transcoder::alloc() {
   HIP_TRY(hipMemsetAsync(d.err, 0, sizeof(uint32_t), s2));
   if (opt.intra4x4) HIP_TRY(hipMemsetAsync(d.i4, 0xff, entries * static_cast<size_t>(nmb) * sizeof(uint64_t), s1));
   // no kernel writes the IDR level's vectors: they read as "no vector", as every intra macroblock's do
+  if (opt.per_frame) VTS_TRY(alloc_rate());
   if (opt.partitions)
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d.mv4), static_cast<int>(kPcmCmdWord),
                               entries * static_cast<size_t>(nmb) * 4, s1));
   return ev.create(plan.maxlen, n_chunks(plan));
+}
+
+// The per-picture QPs and the rate measure (vts_transcode_ext7).  frame_qp:
+// the caller's QPs; bitrate_kbps: every picture starts at picture 0's QP and
+// enc_rc sets the others as their GOP goes.  A picture no kernel codes (an IDR
+// picture without intra) measures as all I_PCM from the start.
+int Transcoder::alloc_rate() {
+  const size_t nf = static_cast<size_t>(n);
+  VTS_TRY(bufs.get(&d.qp_f, nf));
+  VTS_TRY(bufs.get(&d.est_f, nf));
+  std::vector<uint8_t> qps(nf, static_cast<uint8_t>(full::erc::first_qp(opt.qp, opt.qp_min, opt.qp_max)));
+  if (opt.frame_qp) qps.assign(opt.frame_qp, opt.frame_qp + nf);
+  std::vector<uint32_t> est(nf, 0);
+  if (!opt.intra)
+    for (int64_t f : plan.gop_start) est[f] = static_cast<uint32_t>(kPcmMbBits) * static_cast<uint32_t>(nmb);
+  HIP_TRY(hipMemcpy(d.qp_f, qps.data(), nf, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d.est_f, est.data(), nf * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (opt.bitrate_kbps) {
+    std::vector<int32_t> len(static_cast<size_t>(plan.ngop));
+    for (int64_t k = 0; k < plan.ngop; ++k)
+      len[k] = static_cast<int32_t>((k + 1 < plan.ngop ? plan.gop_start[k + 1] : n) - plan.gop_start[k]);
+    const std::vector<int64_t> none(len.size(), 0);
+    VTS_TRY(bufs.get(&d.rc_spent, len.size()));
+    VTS_TRY(bufs.get(&d.rc_len, len.size()));
+    HIP_TRY(hipMemcpy(d.rc_spent, none.data(), none.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.rc_len, len.data(), len.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  return VTS_OK;
 }
 
 SearchArgs Transcoder::search_args(int64_t j) const {
@@ -420,6 +514,10 @@ SearchArgs Transcoder::search_args(int64_t j) const {
     a.es_stat = d.stats + kStEarlySkip;
     a.mv4 = l.mv4;
     a.mv4_prev = level(j - 1).mv4;
+    a.qp_f = d.qp_f;
+    a.est_f = d.est_f;
+    a.mv_lambda16 = opt.mv_lambda16;
+    a.pcm_bits = opt.intra ? 0 : kPcmMbBits;
   }
   return a;
 }
@@ -441,6 +539,8 @@ IntraArgs Transcoder::intra_args(int64_t j) const {
   a.qp = opt.qp;
   a.all = j == 0;
   a.i4 = l.i4;
+  a.qp_f = d.qp_f;
+  a.est_f = d.est_f;
   return a;
 }
 
@@ -462,6 +562,7 @@ DeblockArgs Transcoder::deblock_args(int64_t j) const {
   a.off_b = 2 * opt.dbk_beta;
   a.count = d.stats + kStDeblocked;
   a.mv4 = l.mv4;
+  a.qp_f = d.qp_f;
   return a;
 }
 
@@ -502,6 +603,7 @@ WriteArgs Transcoder::write_args(int64_t ck) const {
   a.dbk_beta = opt.dbk_beta;
   a.i4 = l.i4;
   a.mv4 = l.mv4;
+  a.qp_f = d.qp_f;
   return a;
 }
 
@@ -523,6 +625,22 @@ int Transcoder::enqueue_level(int64_t j) {
   if (opt.intra) launch_enc_intra(intra_args(j), opt.intra4x4 != 0, ne, s1);
   if (opt.deblock && (j > 0 || opt.intra)) launch_enc_deblock(deblock_args(j), ne, s1);
   if (opt.hashed) launch_enc_hash(hash_args(j), ne, s1);
+  // bitrate_kbps: the GOPs' controllers take this level's measure and set the next level's QPs, in stream order
+  if (opt.bitrate_kbps && j + 1 < plan.maxlen) {
+    const Level nx = level(j + 1);
+    RcArgs r{};
+    r.ent = nx.ent;
+    r.n_ent = static_cast<int32_t>(nx.ne);
+    r.gop_pos = static_cast<int32_t>(j);
+    r.qp_f = d.qp_f;
+    r.est_f = d.est_f;
+    r.spent = d.rc_spent;
+    r.gop_len = d.rc_len;
+    r.frame_bits = full::erc::frame_budget(opt.bitrate_kbps, delta, c->info.track_timescale);
+    r.qp_min = opt.qp_min;
+    r.qp_max = opt.qp_max;
+    launch_enc_rc(r, s1);
+  }
   if (j > 0 || opt.intra) HIP_TRY(hipEventRecord(ev.level_done[j], s1));
   return VTS_OK;
 }
@@ -669,6 +787,24 @@ int Transcoder::finish(vts_transcode_info *info, vts_transcode_ext_info *xinfo) 
   HIP_TRY(hipMemcpy(st, d.stats, sizeof st, hipMemcpyDeviceToHost));
   if (err) return fail(VTS_E_CAPACITY, "a slice exceeded its %lld-byte staging slot", static_cast<long long>(cap));
   VTS_TRY(copy_words());
+  // the QP and the measure of every frame: the device's with a per-picture QP, else the call's QP and no measure
+  std::vector<uint8_t> qps(static_cast<size_t>(n), static_cast<uint8_t>(opt.qp));
+  std::vector<uint32_t> est(static_cast<size_t>(n), 0);
+  if (opt.per_frame) {
+    HIP_TRY(hipMemcpy(qps.data(), d.qp_f, qps.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(est.data(), d.est_f, est.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  if (opt.qp_out) std::copy(qps.begin(), qps.end(), opt.qp_out);
+  if (opt.bits_out) std::copy(est.begin(), est.end(), opt.bits_out);
+  int64_t qp_sum = 0, est_bits = 0;
+  for (int64_t f = 0; f < n; ++f) {
+    qp_sum += qps[f];
+    est_bits += est[f];
+  }
+  VTS_XINFO_PUT(vts_transcode_ext_info6, qp_sum, qp_sum);
+  VTS_XINFO_PUT(vts_transcode_ext_info6, qp_lo, n ? *std::min_element(qps.begin(), qps.end()) : 0);
+  VTS_XINFO_PUT(vts_transcode_ext_info6, qp_hi, n ? *std::max_element(qps.begin(), qps.end()) : 0);
+  VTS_XINFO_PUT(vts_transcode_ext_info6, est_bits, est_bits);
 
   const auto t0 = clk::now();
   std::vector<uint8_t> sps, pps;

@@ -190,6 +190,22 @@ class TranscodeExtInfo5(C.Structure):
                 ("p8x8_mbs", C.c_int64), ("mv_words", C.c_int64)]
 
 
+class TranscodeExt7(C.Structure):
+    """vts_transcode_ext7 (per-picture QP, rate control): begins with TranscodeExt6;
+    passed by pointer cast with the innermost struct_size = sizeof(TranscodeExt7)."""
+    _fields_ = [("base", TranscodeExt6), ("bitrate_kbps", C.c_int32), ("qp_min", C.c_int32),
+                ("qp_max", C.c_int32), ("_pad5", C.c_int32),
+                ("frame_qp", C.POINTER(C.c_uint8)), ("frame_qp_n", C.c_int64),
+                ("qp_out", C.POINTER(C.c_uint8)), ("bits_out", C.POINTER(C.c_uint32)),
+                ("frame_cap", C.c_int64)]
+
+
+class TranscodeExtInfo6(C.Structure):
+    """vts_transcode_ext_info6: begins with TranscodeExtInfo5; as TranscodeExt7."""
+    _fields_ = [("base", TranscodeExtInfo5), ("qp_sum", C.c_int64), ("qp_lo", C.c_int32),
+                ("qp_hi", C.c_int32), ("est_bits", C.c_int64), ("frame_words", C.c_int64)]
+
+
 class ManifestArgs(C.Structure):
     _fields_ = [("video_id", C.c_char_p), ("segment_dir", C.c_char_p),
                 ("created_at", C.c_char_p), ("duration", C.c_double),

@@ -266,7 +266,9 @@ class VideoScorer:
                   deblock_offsets: tuple[int, int] = (0, 0), mvcost: bool = False,
                   early_skip: bool = False, mv_lambda16: int = 0, want_commands: bool = False,
                   cabac: bool = False, intra4x4: bool = False, want_intra4_modes: bool = False,
-                  partitions: bool = False, want_vectors: bool = False) -> dict:
+                  partitions: bool = False, want_vectors: bool = False,
+                  bitrate_kbps: int = 0, qp_range: tuple[int, int] = (0, 0),
+                  frame_qp=None, want_rate: bool = False) -> dict:
         """360p upload transcode of this video into `out_path`
         (vts_transcode_ex): decode + score + area downscale +
         device H.264 encode with a quantised residual at `qp` (<= 0: none, the
@@ -308,6 +310,19 @@ class VideoScorer:
         `vectors`, a uint32 array (n_frames, mbh, mbw, 4): the quadrant vectors
         of every inter macroblock as mvx | mvy << 16 (a 16x16 macroblock's
         four times, P_Skip four 0), 0x80008000 for intra and I_PCM ones.
+        `frame_qp`: one QP (1..51) per frame, in frame order; every stage
+        codes frame f at frame_qp[f] (slice_qp_delta, no per-macroblock QP); a
+        constant one gives the bytes of the same call with that `qp`.
+        `bitrate_kbps`: one controller per GOP sets the QPs on the device from
+        a per-picture rate measure so that each GOP meets its share of the
+        bitrate (DESIGN.md §11 "Rate control" has the measured target /
+        achieved ratios; no hit tolerance is promised),
+        starting every GOP at `qp` and staying inside `qp_range` = (qp_min,
+        qp_max), 0 = the default 10 / 51.  Both need `mvcost` and `qp` > 0 and
+        exclude each other.  With one of them or `want_rate` the result also
+        holds `frame_qp` (uint8 array, the QP each frame was coded at),
+        `frame_bits` (uint32 array, its rate measure: all 0 with both off),
+        `qp_lo`, `qp_hi`, `qp_mean` and `est_bits`.
         Returns the facts (with `intra`, `subpel`, `deblock`, `mvcost`
         or `early_skip` also the encoder's `recon_hash`) and per-stage
         milliseconds; with one of the last four keywords also
@@ -326,17 +341,24 @@ class VideoScorer:
         # ... and the partition structs only with theirs
         i4 = bool(intra4x4 or want_intra4_modes)
         pt = bool(partitions or want_vectors)
-        ext_t = _lib.TranscodeExt6 if pt else (_lib.TranscodeExt5 if i4 else _lib.TranscodeExt4)
-        info_t = _lib.TranscodeExtInfo5 if pt else (_lib.TranscodeExtInfo4 if i4 else _lib.TranscodeExtInfo3)
-        ext6 = _lib.TranscodeExt6(_lib.TranscodeExt5(_lib.TranscodeExt4(_lib.TranscodeExt3(
+        # ... and the rate structs only with theirs
+        rc = bool(bitrate_kbps or tuple(qp_range) != (0, 0) or frame_qp is not None or want_rate)
+        ext_t = _lib.TranscodeExt7 if rc else (
+            _lib.TranscodeExt6 if pt else (_lib.TranscodeExt5 if i4 else _lib.TranscodeExt4))
+        info_t = _lib.TranscodeExtInfo6 if rc else (
+            _lib.TranscodeExtInfo5 if pt else (_lib.TranscodeExtInfo4 if i4 else _lib.TranscodeExtInfo3))
+        ext7 = _lib.TranscodeExt7(_lib.TranscodeExt6(_lib.TranscodeExt5(_lib.TranscodeExt4(_lib.TranscodeExt3(
             _lib.TranscodeExt2(_lib.TranscodeExt(C.sizeof(ext_t), subpel),
                                1 if deblock else 0, int(deblock_offsets[0]), int(deblock_offsets[1])),
             1 if mvcost else 0, int(mv_lambda16), 1 if early_skip else 0), 1 if cabac else 0),
-            1 if intra4x4 else 0), 1 if partitions else 0)
+            1 if intra4x4 else 0), 1 if partitions else 0),
+            int(bitrate_kbps), int(qp_range[0]), int(qp_range[1]))
+        ext6 = ext7.base
         ext5 = ext6.base
         ext = ext5.base.base
-        xinfo5 = _lib.TranscodeExtInfo5(_lib.TranscodeExtInfo4(_lib.TranscodeExtInfo3(_lib.TranscodeExtInfo2(
-            _lib.TranscodeExtInfo(C.sizeof(info_t))))))
+        xinfo6 = _lib.TranscodeExtInfo6(_lib.TranscodeExtInfo5(_lib.TranscodeExtInfo4(_lib.TranscodeExtInfo3(
+            _lib.TranscodeExtInfo2(_lib.TranscodeExtInfo(C.sizeof(info_t)))))))
+        xinfo5 = xinfo6.base
         xinfo4 = xinfo5.base
         xinfo3 = xinfo4.base
         xinfo2 = xinfo3.base
@@ -359,11 +381,33 @@ class VideoScorer:
             vectors = np.zeros((int(self.info.n_frames), mbh, mbw, 4), np.uint32)
             ext6.mv_out = vectors.ctypes.data_as(C.POINTER(C.c_uint32))
             ext6.mv_cap = vectors.size
+        qps_in = qps = bits = None
+        if rc:
+            nf = int(self.info.n_frames)
+            if frame_qp is not None:
+                wide = np.asarray(frame_qp, dtype=np.int64).reshape(-1)
+                # what a byte cannot hold would wrap in the cast (300 to 44) and get past the library's 1..51
+                # check; 0 and 52..255 reach the library, which names the entry
+                if wide.size and (wide.min() < 0 or wide.max() > 255):
+                    raise ValueError(f"frame_qp: every QP is 1..51, got {int(wide.min())}..{int(wide.max())}")
+                qps_in = np.ascontiguousarray(wide, dtype=np.uint8)
+                ext7.frame_qp = qps_in.ctypes.data_as(C.POINTER(C.c_uint8))
+                ext7.frame_qp_n = qps_in.size
+            qps = np.zeros(nf, np.uint8)
+            bits = np.zeros(nf, np.uint32)
+            ext7.qp_out = qps.ctypes.data_as(C.POINTER(C.c_uint8))
+            ext7.bits_out = bits.ctypes.data_as(C.POINTER(C.c_uint32))
+            ext7.frame_cap = nf
         _lib.check(self._lib.vts_transcode_ex(self._ctx, str(out_path).encode(), C.byref(prm),
-                                              C.cast(C.pointer(ext6), C.POINTER(_lib.TranscodeExt)),
+                                              C.cast(C.pointer(ext7), C.POINTER(_lib.TranscodeExt)),
                                               C.byref(info),
-                                              C.cast(C.pointer(xinfo5), C.POINTER(_lib.TranscodeExtInfo))))
+                                              C.cast(C.pointer(xinfo6), C.POINTER(_lib.TranscodeExtInfo))))
         extra = {}
+        if rc:
+            if xinfo6.frame_words != qps.size:
+                raise RuntimeError(f"{xinfo6.frame_words} frames reported, expected {qps.size}")
+            extra.update(frame_qp=qps, frame_bits=bits, qp_lo=xinfo6.qp_lo, qp_hi=xinfo6.qp_hi,
+                         qp_mean=xinfo6.qp_sum / max(1, qps.size), est_bits=xinfo6.est_bits)
         if pt:
             extra.update(p16x8_mbs=xinfo5.p16x8_mbs, p8x16_mbs=xinfo5.p8x16_mbs, p8x8_mbs=xinfo5.p8x8_mbs)
         if want_vectors:
