@@ -17,6 +17,8 @@
  *   vts_probe_info         utils/video_utils.py:7-38        (same probe, all stream facts)
  *   vts_extract_segment    utils/video_segmenter.py:86-154  extract_segment (ffmpeg -c copy)
  *   vts_add_tracks         analyzer/content_analyzer.py:206-209 (audio kept in the upload copy)
+ *   vts_add_tracks_range   utils/video_segmenter.py:86-154  extract_segment (the re-encode branch's
+ *                          audio, beside a vts_transcode_ex of a frame range; a stream copy)
  *   vts_boundary_frames*   (no reference code; video_segmenter.py:157-159 snap_to_keyframe
  *                          is the identity stub this feeds)  segment time -> frame index
  *   vts_open/vts_score/... (no reference code; north_star)   decode + NV12 scene scoring
@@ -188,6 +190,16 @@ int vts_extract_segment(const char *in_path, double start, double end,
  * upload transcode keeps the source's audio with it, as the reference keeps
  * audio (content_analyzer.py:206-209, -c:a aac -b:a 64k; here a stream copy). */
 int vts_add_tracks(const char *video_path, const char *src_path, const char *out_path);
+
+/* As vts_add_tracks, with every non-video track of src_path cut to
+ * [start, end) by vts_extract_segment's rule: samples from the sync sample at
+ * or before `start` to the last one presented before `end`, an edit list that
+ * begins presentation at `start`.  Every track of video_path is copied whole
+ * (the device re-encode of the same span: its file starts at its first
+ * frame); a track of src_path with nothing in range is dropped; moov first.
+ * VTS_E_INVALID when end - start <= 0. */
+int vts_add_tracks_range(const char *video_path, const char *src_path, double start,
+                         double end, const char *out_path);
 
 /* ------------------------------------------------- device scoring kernel */
 
@@ -728,6 +740,39 @@ typedef struct vts_transcode_ext_info6 {
   int64_t est_bits;        /* sum of the measure; 0 with both features off      */
   int64_t frame_words;     /* n_frames                                          */
 } vts_transcode_ext_info6;
+
+/* A frame range, DESIGN.md §11 "Segment re-encode".  As the structs above:
+ * begun with them, passed by pointer cast, struct_size = their own sizeof.
+ * Read: frame_first when struct_size >= 176, frame_count at >= 184 (a 168-byte
+ * vts_transcode_ext7 or anything smaller: 0, the whole video); written:
+ * frame_first at >= 136, frame_count at >= 144 (the range applied).
+ * Frames are counted in presentation order, as every result and
+ * vts_boundary_frames count them.  The output is what the same call would
+ * write for a video made of the frames [frame_first, frame_first +
+ * frame_count) alone: frame frame_first is an IDR picture, keyint, the rate
+ * controller's GOPs, idr_pic_id and frame_num start there, idr_at_cuts reads
+ * the session's scores of the frames after it, recon_hash weighs a frame by
+ * its index inside the range, and sample i of the file has the time i * the
+ * frame duration.  vts_transcode_info.n_frames, cmd_words, i4_words, mv_words,
+ * frame_words, frame_qp_n and the capacities checked for cmd_out, i4_out,
+ * mv_out, qp_out and bits_out count the range's frames; the constant frame
+ * duration is asked of the range only.  Every window of the video is still
+ * decoded and scored (the session's scores stay whole); only the range's
+ * frames are kept for the encoder.
+ * VTS_E_INVALID, the field named: frame_first < 0 or >= the video's frames,
+ * frame_count < 0 or frame_first + frame_count > the video's frames.
+ * frame_first = 0 and frame_count = 0 is the call as it was, byte for byte. */
+typedef struct vts_transcode_ext8 {
+  vts_transcode_ext7 base;
+  int64_t frame_first;     /* first frame of the range                          */
+  int64_t frame_count;     /* its frames; 0 = through the last frame            */
+} vts_transcode_ext8;
+
+typedef struct vts_transcode_ext_info7 {
+  vts_transcode_ext_info6 base;
+  int64_t frame_first;     /* the range applied                                 */
+  int64_t frame_count;
+} vts_transcode_ext_info7;
 
 /* vts_transcode with the settings of `ext` (NULL: none) and the further facts
  * in `ext_info` (NULL: not wanted).  vts_transcode(c, o, p, i) is

@@ -1,5 +1,6 @@
-// downscale.hip — the small store: every decoded frame downscaled (area
-// filter, NV12 -> NV12 at (w, height), coded 16-aligned) into a whole-video
+// downscale.hip — the small store: every decoded frame of the transcoded
+// range (the whole video by default) downscaled (area filter, NV12 -> NV12 at
+// (w, height), coded 16-aligned; at ratio 1 copied by ingest_nv12) into one
 // store while it sits in the decode ring.  The decode sessions call
 // setup_small and small_window (session.h); the device encoder
 // (transcode.hip, transcode_driver.cpp) reads the store.
@@ -8,6 +9,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "pixel_clamp.h"
 #include "session.h"
 
 namespace vts {
@@ -128,6 +130,64 @@ __global__ void __launch_bounds__(256) downscale_nv12(DsArgs a) {
   }
 }
 
+// ------------------------------------------------------------- ingest
+// Ratio 1 (output size = source display size): the store's frame is the
+// source's with every sample max(s, 1) and the coded padding rebuilt from the
+// display edge (the surface's own padding holds whatever the stream coded in
+// the cropped area).  One lane makes 16 bytes of one row, luma rows then the
+// NV12 chroma rows: one 16-byte load and one 16-byte store where the group
+// lies inside the display, the edge rule byte by byte where it crosses the
+// display width or the row is a padded one.  small_window checks the 16-byte
+// alignment of both sides.
+struct IngestArgs {
+  const uint8_t *src;  // ring surface of the first frame
+  int64_t src_stride;
+  int32_t pitch, uv_rows;
+  int32_t sw, sh;      // display size (even)
+  uint8_t *dst;        // small store, the first frame's slot
+  int64_t dst_stride;
+  int32_t cw, ch;      // coded size
+};
+
+__global__ void __launch_bounds__(256) ingest_nv12(IngestArgs a) {
+  const int groups = a.cw / 16;
+  const int rows = a.ch + a.ch / 2;
+  const int64_t t = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+  if (t >= static_cast<int64_t>(groups) * rows) return;
+  const int64_t f = blockIdx.y;
+  const int g = static_cast<int>(t % groups), row = static_cast<int>(t / groups);
+  const bool chroma = row >= a.ch;
+  const int y = chroma ? row - a.ch : row;        // row of its plane
+  const int ny = chroma ? a.sh / 2 : a.sh;        // display rows of the plane
+  const uint8_t *plane = a.src + f * a.src_stride + (chroma ? static_cast<int64_t>(a.pitch) * a.uv_rows : 0);
+  uint4 *out = reinterpret_cast<uint4 *>(a.dst + f * a.dst_stride + static_cast<int64_t>(row) * a.cw + 16 * g);
+  uint4 v;
+  if (y < ny && 16 * g + 16 <= a.sw) {
+    v = *reinterpret_cast<const uint4 *>(plane + static_cast<int64_t>(y) * a.pitch + 16 * g);
+  } else {
+    // columns >= sw repeat the last display column (chroma: the last U, V pair), rows >= ny the last display row
+    const uint8_t *r = plane + static_cast<int64_t>(min(y, ny - 1)) * a.pitch;
+    uint32_t w[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      uint32_t d = 0;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int x = 16 * g + 4 * q + b;
+        const int sx = chroma ? 2 * min(x >> 1, a.sw / 2 - 1) + (x & 1) : min(x, a.sw - 1);
+        d |= static_cast<uint32_t>(r[sx]) << (8 * b);
+      }
+      w[q] = d;
+    }
+    v = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+  v.x = clamp_min1_x4(v.x);
+  v.y = clamp_min1_x4(v.y);
+  v.z = clamp_min1_x4(v.z);
+  v.w = clamp_min1_x4(v.w);
+  *out = v;
+}
+
 // ------------------------------------------------------------ host
 int64_t gcd64(int64_t a, int64_t b) {
   while (b) {
@@ -165,17 +225,23 @@ std::vector<int32_t> area_taps(int64_t n, int64_t m, int coded, int *k_out, int3
 
 }  // namespace
 
-int setup_small(vts_ctx *c, int sh) {
+int setup_small(vts_ctx *c, int sh, int64_t f0, int64_t f1) {
   SmallStore &S = c->small;
   const int W = c->width, H = c->height;
   const int sw = static_cast<int>((static_cast<int64_t>(sh) * W + H) / (2 * static_cast<int64_t>(H))) * 2;
   if (sw < 2) return fail(VTS_E_INVALID, "output width %d from %dx%d at height %d", sw, W, H, sh);
-  if (S.d && S.w == sw && S.h == sh) return VTS_OK;
+  if (S.d && S.w == sw && S.h == sh && S.cap >= f1 - f0) {  // the same geometry and room for the range
+    S.f0 = f0;
+    S.f1 = f1;
+    return VTS_OK;
+  }
   if (S.d) vts::dfree(S.d);
   if (S.d_taps) vts::dfree(S.d_taps);
   S = SmallStore{};
   S.w = sw;
   S.h = sh;
+  S.f0 = f0;
+  S.f1 = f1;
   S.cw = (sw + 15) & ~15;
   S.ch = (sh + 15) & ~15;
   S.stride = (static_cast<int64_t>(S.cw) * S.ch * 3 / 2 + 255) & ~int64_t(255);
@@ -202,25 +268,33 @@ int setup_small(vts_ctx *c, int sh) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(vts::dmalloc(&S.d_taps, all.size() * sizeof(int32_t)));
   HIP_TRY(hipMemcpy(S.d_taps, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  const size_t bytes = static_cast<size_t>(S.stride * c->n_frames + 256);
+  const size_t bytes = static_cast<size_t>(S.stride * (f1 - f0) + 256);
   if (vts::dmalloc(&S.d, bytes) != hipSuccess) {
     (void)hipGetLastError();
     S.d = nullptr;
     return fail(VTS_E_HIP, "cannot allocate %.1f GiB for the %dx%d frames", bytes / 1073741824.0, sw, sh);
   }
+  S.cap = f1 - f0;
   return VTS_OK;
 }
 
-int small_window(vts_ctx *c, int ring, int64_t f0, int64_t f1, hipStream_t s) {
+int small_window(vts_ctx *c, int ring, int64_t wf0, int64_t wf1, hipStream_t s) {
   const SmallStore &S = c->small;
+  // the window's frames the store holds (none: nothing to do); frame f of the
+  // window is ring surface f - wf0 and goes to the store's slot f - S.f0
+  const int64_t f0 = std::max(wf0, S.f0), f1 = std::min(wf1, S.f1);
+  if (f1 <= f0) return VTS_OK;
+  if (f0 < S.f0 || f1 - S.f0 > S.cap)  // never: setup_small gave the range its slots
+    return fail(VTS_E_HIP, "small store of %lld slots from frame %lld: frames %lld .. %lld", static_cast<long long>(S.cap),
+                static_cast<long long>(S.f0), static_cast<long long>(f0), static_cast<long long>(f1 - 1));
   DsArgs a{};
-  a.src = c->d_surf[ring];
+  a.src = c->d_surf[ring] + (f0 - wf0) * c->frame_stride;
   a.src_stride = c->frame_stride;
   a.pitch = c->pitch;
   a.uv_rows = c->coded_h;
   a.sw = c->width;
   a.sh = c->height;
-  a.dst = S.d + f0 * S.stride;
+  a.dst = S.d + (f0 - S.f0) * S.stride;
   a.dst_stride = S.stride;
   a.cw = S.cw;
   a.ch = S.ch;
@@ -239,11 +313,24 @@ int small_window(vts_ctx *c, int ring, int64_t f0, int64_t f1, hipStream_t s) {
   // integer ratio on both axes (equal): the dword box path; else the tap tables
   const int W = c->width, H = c->height;
   const int k = (W % S.w == 0 && H % S.h == 0 && W / S.w == H / S.h) ? W / S.w : 0;
+  // ratio 1: 16-byte groups, when both sides are 16-byte aligned (they are: the pitch is the coded width,
+  // frame_stride and stride are multiples of 256 and the allocations' bases of more; else the tap tables)
+  const auto al16 = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+  const bool ingest = k == 1 && al16(a.src) && al16(a.dst) && a.pitch % 16 == 0 && a.src_stride % 16 == 0 &&
+                      a.cw % 16 == 0 && a.dst_stride % 16 == 0 &&
+                      (static_cast<int64_t>(a.pitch) * a.uv_rows) % 16 == 0;
+  const int64_t groups16 = static_cast<int64_t>(S.cw / 16) * (S.ch + S.ch / 2);
   for (int64_t g0 = 0; g0 < f1 - f0; g0 += 65535) {  // grid.y <= 65535 frames per launch
     DsArgs b = a;
     b.src = a.src + g0 * a.src_stride;
     b.dst = a.dst + g0 * a.dst_stride;
     b.n_frames = std::min<int64_t>(65535, f1 - f0 - g0);
+    if (ingest) {
+      const IngestArgs ia{b.src, b.src_stride, b.pitch, b.uv_rows, b.sw, b.sh, b.dst, b.dst_stride, b.cw, b.ch};
+      hipLaunchKernelGGL(ingest_nv12, dim3(static_cast<unsigned>((groups16 + 255) / 256), static_cast<unsigned>(b.n_frames)),
+                         dim3(256), 0, s, ia);
+      continue;
+    }
     const dim3 grid(static_cast<unsigned>((threads + 255) / 256), static_cast<unsigned>(b.n_frames));
     switch (k) {
       case 2: hipLaunchKernelGGL(downscale_nv12<2>, grid, dim3(256), 0, s, b); break;

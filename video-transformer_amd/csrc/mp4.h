@@ -81,6 +81,10 @@ std::string mp4_remux_segment(const char *in_path, double start, double end,
 // upload transcode keeps the source's audio this way (content_analyzer.py:
 // 206-209 keeps it with -c:a aac).  "" = ok, else the reason.
 std::string mp4_add_tracks(const char *video_path, const char *src_path, const char *out_path);
+// ... with the tracks of src_path cut to [start, end) as mp4_remux_segment
+// cuts them (one with nothing in range is dropped); video_path's stay whole
+std::string mp4_add_tracks_range(const char *video_path, const char *src_path, double start, double end,
+                                 const char *out_path);
 
 // Streaming MP4 writer: ftyp, mdat (64-bit size), moov at the end.
 class Mp4Writer {

@@ -360,29 +360,43 @@ std::string write_cuts(std::vector<Cut> &cuts, const char *const *srcs, int n_sr
 
 }  // namespace
 
-std::string mp4_add_tracks(const char *video_path, const char *src_path, const char *out_path) {
+namespace {
+constexpr double kWhole = 1e300;  // finite: ceil_ticks saturates it (frexp of inf is not a number)
+
+// every track of video_path whole, every non-video track of src_path cut to [start, end)
+std::string add_tracks(const char *video_path, const char *src_path, double start, double end,
+                       const char *out_path) {
   Mp4Info a, b;
   std::string e = mp4_parse_file(video_path, &a);
   if (!e.empty()) return e;
   e = mp4_parse_file(src_path, &b);
   if (!e.empty()) return e;
-  const double inf = 1e300;  // finite: ceil_ticks saturates it (frexp of inf is not a number)
   std::vector<Cut> cuts;
   for (const Mp4VideoTrack &t : a.tracks) {
     Cut c;
-    e = plan_cut(t, 0.0, inf, &c);
+    e = plan_cut(t, 0.0, kWhole, &c);
     if (!e.empty()) return e;
     cuts.push_back(std::move(c));
   }
   for (const Mp4VideoTrack &t : b.tracks) {
     if (t.handler == 0x76696465u) continue;  // 'vide': the new video replaces it
     Cut c;
-    if (!plan_cut(t, 0.0, inf, &c).empty()) continue;  // an empty track is dropped
+    if (!plan_cut(t, start, end, &c).empty()) continue;  // a track with nothing in range is dropped
     c.src = 1;
     cuts.push_back(std::move(c));
   }
   const char *srcs[2] = {video_path, src_path};
   return write_cuts(cuts, srcs, 2, out_path);
+}
+}  // namespace
+
+std::string mp4_add_tracks(const char *video_path, const char *src_path, const char *out_path) {
+  return add_tracks(video_path, src_path, 0.0, kWhole, out_path);
+}
+
+std::string mp4_add_tracks_range(const char *video_path, const char *src_path, double start, double end,
+                                 const char *out_path) {
+  return add_tracks(video_path, src_path, start, end, out_path);
 }
 
 std::string mp4_remux_segment(const char *in_path, double start, double end,
@@ -422,6 +436,16 @@ extern "C" int vts_add_tracks(const char *video_path, const char *src_path, cons
   vts::clear_error();
   if (!video_path || !src_path || !out_path) return vts::fail(VTS_E_INVALID, "NULL path");
   const std::string e = vts::mp4_add_tracks(video_path, src_path, out_path);
+  if (!e.empty()) return vts::fail(VTS_E_FORMAT, "%s", e.c_str());
+  return VTS_OK;
+}
+
+extern "C" int vts_add_tracks_range(const char *video_path, const char *src_path, double start, double end,
+                                    const char *out_path) {
+  vts::clear_error();
+  if (!video_path || !src_path || !out_path) return vts::fail(VTS_E_INVALID, "NULL path");
+  if (!(end - start > 0)) return vts::fail(VTS_E_INVALID, "empty time range: start %g, end %g", start, end);
+  const std::string e = vts::mp4_add_tracks_range(video_path, src_path, start, end, out_path);
   if (!e.empty()) return vts::fail(VTS_E_FORMAT, "%s", e.c_str());
   return VTS_OK;
 }

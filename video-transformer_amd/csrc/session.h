@@ -55,14 +55,16 @@ struct Window {
   std::vector<int32_t> dlv_early;
 };
 
-// Downscaled copy of every decoded frame (downscale.hip), filled by run_all
-// after each window's reconstruction when `on`.
+// Downscaled copy of the decoded frames [f0, f1) (downscale.hip), filled by
+// run_all after each window's reconstruction when `on`.
 struct SmallStore {
   bool on = false;
   int w = 0, h = 0;             // display size (even)
   int cw = 0, ch = 0;           // coded size (16-aligned); NV12, pitch cw, UV at cw * ch
   int64_t stride = 0;           // bytes per frame
-  uint8_t *d = nullptr;         // [frame]
+  int64_t f0 = 0, f1 = 0;       // the frames it holds: frame f at slot f - f0
+  int64_t cap = 0;              // slots allocated (>= f1 - f0)
+  uint8_t *d = nullptr;         // [slot]
   int32_t *d_taps = nullptr;    // area-filter tap tables (downscale.hip area_taps)
   int64_t off[4] = {0, 0, 0, 0};  // luma x, luma y, chroma x, chroma y tables in d_taps
   int taps_x = 0, taps_y = 0, taps_cx = 0, taps_cy = 0;  // taps per output sample
@@ -268,7 +270,9 @@ bool general_by_headers(const vts_ctx *c);
 bool wants_general(const vts_ctx *c, const uint8_t *es, const std::vector<int64_t> &es_off,
                    const std::vector<uint32_t> &sizes, int nal_length_size);
 // the small store (downscale.hip): sized and allocated for output height sh
-// (kept when it already has that size); downscale the window's frames into it
-int setup_small(vts_ctx *c, int sh);
+// and the frames [f0, f1) (kept when it already has that size and as many
+// slots); downscale the window's frames [f0, f1) into it, those of them the
+// store holds (none: nothing is launched)
+int setup_small(vts_ctx *c, int sh, int64_t f0, int64_t f1);
 int small_window(vts_ctx *c, int ring, int64_t f0, int64_t f1, hipStream_t s);
 }  // namespace vts

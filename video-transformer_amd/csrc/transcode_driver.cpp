@@ -68,6 +68,10 @@ static_assert(VTS_END_OF(vts_transcode_ext_info6, qp_sum) == 104 && VTS_END_OF(v
               VTS_END_OF(vts_transcode_ext_info6, qp_hi) == 112 && VTS_END_OF(vts_transcode_ext_info6, est_bits) == 120 &&
               VTS_END_OF(vts_transcode_ext_info6, frame_words) == 128 && sizeof(vts_transcode_ext_info6) == 128,
               "vts_transcode_ext_info6: struct_size >= 104, 108, 112, 120, 128");
+static_assert(VTS_END_OF(vts_transcode_ext8, frame_first) == 176 && VTS_END_OF(vts_transcode_ext8, frame_count) == 184 &&
+              sizeof(vts_transcode_ext8) == 184 && VTS_END_OF(vts_transcode_ext_info7, frame_first) == 136 &&
+              VTS_END_OF(vts_transcode_ext_info7, frame_count) == 144 && sizeof(vts_transcode_ext_info7) == 144,
+              "vts_transcode_ext8: struct_size >= 176, 184; vts_transcode_ext_info7: >= 136, 144");
 static_assert(VTS_END_OF(vts_transcode_ext_info, _pad) == 8 && VTS_END_OF(vts_transcode_ext_info, subpel_mbs) == 16 &&
               VTS_END_OF(vts_transcode_ext_info, qpel_mbs) == 24 && VTS_END_OF(vts_transcode_ext_info2, deblock_mbs) == 32 &&
               VTS_END_OF(vts_transcode_ext_info3, early_skip_mbs) == 40 &&
@@ -97,6 +101,7 @@ struct TranscodeOpts {
   uint8_t *qp_out = nullptr;
   uint32_t *bits_out = nullptr;
   int64_t frame_cap = 0;
+  int64_t f0 = 0, n = 0;   // the frames [f0, f0 + n) of the video are transcoded (vts_transcode_ext8; all by default)
   bool per_frame = false;  // frame_qp or bitrate_kbps: the kernels read a QP per picture and measure its rate
   int rate = 0;         // SearchArgs.rate: mvcost | early_skip << 1
   int sh = 0, R = 0, T = 0, qp = 0, keyint = 0;  // output height, search range, max SAD, residual QP (0: none)
@@ -109,6 +114,7 @@ struct TranscodeOpts {
 int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_transcode_ext *ext,
               const vts_transcode_ext_info *xinfo, TranscodeOpts *out) {
   TranscodeOpts &o = *out;
+  o.n = c->n_frames;
   if (ext) {
     if (ext->struct_size < VTS_END_OF(vts_transcode_ext, subpel))
       return fail(VTS_E_INVALID, "vts_transcode_ext.struct_size %u < 8", ext->struct_size);
@@ -155,6 +161,17 @@ int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_trans
     VTS_EXT_GET(o.qp_out, vts_transcode_ext7, qp_out);
     VTS_EXT_GET(o.bits_out, vts_transcode_ext7, bits_out);
     VTS_EXT_GET(o.frame_cap, vts_transcode_ext7, frame_cap);
+    // vts_transcode_ext8, the same way: the range, before what is counted in its frames
+    int64_t count = 0;
+    VTS_EXT_GET(o.f0, vts_transcode_ext8, frame_first);
+    VTS_EXT_GET(count, vts_transcode_ext8, frame_count);
+    if (o.f0 < 0 || (o.f0 >= c->n_frames && (o.f0 || count)))  // 0, 0 on an empty video is the call as it was
+      return fail(VTS_E_INVALID, "frame_first %lld: 0 .. %lld", static_cast<long long>(o.f0),
+                  static_cast<long long>(c->n_frames - 1));
+    if (count < 0 || count > c->n_frames - o.f0)
+      return fail(VTS_E_INVALID, "frame_count %lld: 0 .. %lld from frame_first %lld", static_cast<long long>(count),
+                  static_cast<long long>(c->n_frames - o.f0), static_cast<long long>(o.f0));
+    o.n = count ? count : c->n_frames - o.f0;
     if (o.bitrate_kbps < 0 || o.bitrate_kbps > full::erc::kMaxKbps)
       return fail(VTS_E_INVALID, "bitrate_kbps %d: 0 .. %d", o.bitrate_kbps, full::erc::kMaxKbps);
     if (o.qp_min < 0 || o.qp_min > 51) return fail(VTS_E_INVALID, "qp_min %d: 0 (default) or 1 .. 51", o.qp_min);
@@ -169,9 +186,9 @@ int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_trans
     }
     if (o.frame_qp && o.bitrate_kbps) return fail(VTS_E_INVALID, "frame_qp together with bitrate_kbps %d", o.bitrate_kbps);
     if (o.frame_qp) {
-      if (o.frame_qp_n != c->n_frames)
-        return fail(VTS_E_INVALID, "frame_qp_n %lld: the video has %lld frames", static_cast<long long>(o.frame_qp_n),
-                    static_cast<long long>(c->n_frames));
+      if (o.frame_qp_n != o.n)
+        return fail(VTS_E_INVALID, "frame_qp_n %lld: the %s has %lld frames", static_cast<long long>(o.frame_qp_n),
+                    o.n == c->n_frames ? "video" : "range", static_cast<long long>(o.n));
       for (int64_t f = 0; f < o.frame_qp_n; ++f)
         if (o.frame_qp[f] < 1 || o.frame_qp[f] > 51)
           return fail(VTS_E_INVALID, "frame_qp[%lld] %d: 1 .. 51", static_cast<long long>(f), o.frame_qp[f]);
@@ -275,6 +292,7 @@ struct Transcoder {
   GopPlan plan;
   // geometry
   int64_t n = 0, delta = 0;  // frames; their constant duration (track timescale)
+  int64_t f0 = 0;            // the video's frame that is frame 0 here (the small store's slot 0)
   int mbw = 0, mbh = 0, nmb = 0;
   int64_t cap = 0;           // staging slot per slice
   int64_t cmd_words = 0;     // n * nmb: the command (and Intra4x4PredModes) words of every macroblock
@@ -361,20 +379,24 @@ struct Transcoder {
 // 0. what can be refused before any device work: a variable frame rate (the
 // writer's stts is one entry), the output size, word buffers too small
 int Transcoder::check(vts_transcode_ext_info *xinfo) {
-  n = c->n_frames;
-  delta = n > 1 ? c->pts[1] - c->pts[0] : std::max<int64_t>(1, c->info.track_timescale / 30);
+  n = opt.n;
+  f0 = opt.f0;
+  const int64_t *pts = c->pts.data() + f0;  // of the range's frames
+  delta = n > 1 ? pts[1] - pts[0] : std::max<int64_t>(1, c->info.track_timescale / 30);
   for (int64_t i = 1; i < n; ++i)
-    if (c->pts[i] - c->pts[i - 1] != delta)
+    if (pts[i] - pts[i - 1] != delta)
       return fail(VTS_E_UNSUPPORTED, "variable frame rate (frame %lld) is not transcoded",
-                  static_cast<long long>(i));
+                  static_cast<long long>(f0 + i));
+  VTS_XINFO_PUT(vts_transcode_ext_info7, frame_first, f0);
+  VTS_XINFO_PUT(vts_transcode_ext_info7, frame_count, n);
   HIP_TRY(hipSetDevice(c->device));
-  VTS_TRY(setup_small(c, opt.sh));
+  VTS_TRY(setup_small(c, opt.sh, f0, f0 + n));
   mbw = S().cw / 16;
   mbh = S().ch / 16;
   nmb = mbw * mbh;
   cap = slice_slot_bytes(mbw, opt.cabac != 0);
   // the command words of every macroblock, [frame][my][mx]: reported always, copied out when asked
-  cmd_words = c->n_frames * nmb;
+  cmd_words = n * nmb;
   VTS_XINFO_PUT(vts_transcode_ext_info3, cmd_words, cmd_words);
   if (opt.cmd_out && opt.cmd_cap < cmd_words)
     return fail(VTS_E_CAPACITY, "cmd_cap %lld < %lld command words", static_cast<long long>(opt.cmd_cap),
@@ -871,7 +893,9 @@ extern "C" int vts_transcode_ex(vts_ctx *c, const char *out_path, const vts_tran
   VTS_TRY(read_opts(c, pin, ext, xinfo, &t.opt));
   VTS_TRY(t.check(xinfo));
   VTS_TRY(t.decode());
-  t.plan = plan_gops(t.n, c->host_scores, t.opt.keyint, t.opt.idr_at_cuts, t.opt.thr, t.opt.intra, t.opt.rate);
+  // the range's own scores: frame t.f0 + i is frame i of the plan and of everything after it
+  const std::vector<float> scores(c->host_scores.begin() + t.f0, c->host_scores.begin() + t.f0 + t.n);
+  t.plan = plan_gops(t.n, scores, t.opt.keyint, t.opt.idr_at_cuts, t.opt.thr, t.opt.intra, t.opt.rate);
   VTS_TRY(t.alloc());
   VTS_TRY(t.encode());
   return t.finish(info, xinfo);

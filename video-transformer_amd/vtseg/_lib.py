@@ -206,6 +206,17 @@ class TranscodeExtInfo6(C.Structure):
                 ("qp_hi", C.c_int32), ("est_bits", C.c_int64), ("frame_words", C.c_int64)]
 
 
+class TranscodeExt8(C.Structure):
+    """vts_transcode_ext8 (a frame range): begins with TranscodeExt7; passed by
+    pointer cast with the innermost struct_size = sizeof(TranscodeExt8)."""
+    _fields_ = [("base", TranscodeExt7), ("frame_first", C.c_int64), ("frame_count", C.c_int64)]
+
+
+class TranscodeExtInfo7(C.Structure):
+    """vts_transcode_ext_info7: begins with TranscodeExtInfo6; as TranscodeExt8."""
+    _fields_ = [("base", TranscodeExtInfo6), ("frame_first", C.c_int64), ("frame_count", C.c_int64)]
+
+
 class ManifestArgs(C.Structure):
     _fields_ = [("video_id", C.c_char_p), ("segment_dir", C.c_char_p),
                 ("created_at", C.c_char_p), ("duration", C.c_double),
@@ -239,6 +250,7 @@ SIGNATURES: dict[str, tuple] = {
     "vts_probe_info": (C.c_int, [C.c_char_p, _P(VideoInfo)]),
     "vts_extract_segment": (C.c_int, [C.c_char_p, C.c_double, C.c_double, C.c_char_p]),
     "vts_add_tracks": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p]),
+    "vts_add_tracks_range": (C.c_int, [C.c_char_p, C.c_char_p, C.c_double, C.c_double, C.c_char_p]),
     "vts_score_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
     "vts_score_nv12_dev": (C.c_int, [_P(ScoreDesc), C.c_void_p]),
     "vts_open": (C.c_int, [C.c_int, C.c_char_p, _P(Params), _P(C.c_void_p)]),

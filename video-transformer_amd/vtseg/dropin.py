@@ -34,13 +34,29 @@ ANALYZER_NAMES = {
 }
 
 
-def install(upload_transcode: bool = False) -> list[str]:
+_extract_segment = video_segmenter.extract_segment
+
+
+def _segment_reencode_extract(input_path, start, end, output_path, stream_copy=True):
+    """extract_segment under the reference's signature with the device
+    re-encode before ffmpeg's (install(segment_reencode=True))."""
+    return _extract_segment(input_path, start, end, output_path, stream_copy, device_reencode=True)
+
+
+def install(upload_transcode: bool = False, segment_reencode: bool = False) -> list[str]:
     """Bind vtseg under the reference's names; returns what was bound.
 
     upload_transcode: also replace ContentAnalyzer._compress_video_for_upload
     (content_analyzer.py:167-236) with the GPU transcode (vtseg.upload;
-    opt-in: its bytes differ from x264's)."""
+    opt-in: its bytes differ from x264's).
+    segment_reencode: ``extract_segment`` under the reference's names
+    (``utils.video_segmenter.extract_segment`` and the name content_analyzer
+    imported) runs with ``device_reencode=True``: the frame-accurate device
+    re-encode before the ffmpeg one (opt-in for the same reason; False binds
+    the plain one again)."""
     done = []
+    extract = _segment_reencode_extract if segment_reencode else _extract_segment
+    video_segmenter.extract_segment = extract
     for name, mod in MODULES.items():
         sys.modules[name] = mod
         done.append(name)
@@ -52,7 +68,7 @@ def install(upload_transcode: bool = False) -> list[str]:
     if ca is not None:
         for attr, obj in ANALYZER_NAMES.items():
             if hasattr(ca, attr):
-                setattr(ca, attr, obj)
+                setattr(ca, attr, extract if attr == "extract_segment" else obj)
                 done.append(f"analyzer.content_analyzer.{attr}")
         if upload_transcode and hasattr(ca, "ContentAnalyzer"):
             from . import upload

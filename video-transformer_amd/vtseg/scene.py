@@ -122,6 +122,7 @@ class VideoScorer:
         prm.keep_frames = 1 if keep_frames else 0
         prm.decoder = {"auto": 0, "subset": 1, "general": 2}[decoder]
         self._threshold = cut_threshold
+        self._path = Path(path)   # transcode_segment copies the other tracks from it
         ctx = C.c_void_p()
         _lib.check(self._lib.vts_open(int(device), str(path).encode(), C.byref(prm),
                                       C.byref(ctx)))
@@ -268,7 +269,8 @@ class VideoScorer:
                   cabac: bool = False, intra4x4: bool = False, want_intra4_modes: bool = False,
                   partitions: bool = False, want_vectors: bool = False,
                   bitrate_kbps: int = 0, qp_range: tuple[int, int] = (0, 0),
-                  frame_qp=None, want_rate: bool = False) -> dict:
+                  frame_qp=None, want_rate: bool = False,
+                  frames: tuple[int, int] | None = None) -> dict:
         """360p upload transcode of this video into `out_path`
         (vts_transcode_ex): decode + score + area downscale +
         device H.264 encode with a quantised residual at `qp` (<= 0: none, the
@@ -323,6 +325,15 @@ class VideoScorer:
         holds `frame_qp` (uint8 array, the QP each frame was coded at),
         `frame_bits` (uint32 array, its rate measure: all 0 with both off),
         `qp_lo`, `qp_hi`, `qp_mean` and `est_bits`.
+        `frames` = (f0, f1): only the frames [f0, f1) (presentation order, as
+        `boundary_frames` counts them) are transcoded, into the file the same
+        call would write for a video made of those frames alone: it starts
+        with an IDR picture at time 0, `keyint`, the GOPs of `bitrate_kbps`
+        and `recon_hash` count from f0, `frame_qp` and every per-frame array
+        of the result have f1 - f0 entries, and the result also holds
+        `frame_first` and `frame_count`.  The whole video is still decoded and
+        scored; only the range is kept for the encoder (DESIGN.md §11
+        "Segment re-encode").  None: the whole video, every byte as before.
         Returns the facts (with `intra`, `subpel`, `deblock`, `mvcost`
         or `early_skip` also the encoder's `recon_hash`) and per-stage
         milliseconds; with one of the last four keywords also
@@ -343,21 +354,33 @@ class VideoScorer:
         pt = bool(partitions or want_vectors)
         # ... and the rate structs only with theirs
         rc = bool(bitrate_kbps or tuple(qp_range) != (0, 0) or frame_qp is not None or want_rate)
-        ext_t = _lib.TranscodeExt7 if rc else (
+        # ... and the range structs only with `frames`; nf: the frames every per-frame array holds
+        nf = int(self.info.n_frames)
+        if frames is not None:
+            f0, f1 = int(frames[0]), int(frames[1])
+            if f1 == f0 and 0 <= f0 < nf:   # a count of 0 means "through the last frame" to the library
+                raise _lib.VtsegError(_lib.VTS_E_INVALID, f"frame_count 0: frames=({f0}, {f1}) is empty")
+            nf = max(f1 - f0, 0)
+        ext_t = _lib.TranscodeExt8 if frames is not None else _lib.TranscodeExt7 if rc else (
             _lib.TranscodeExt6 if pt else (_lib.TranscodeExt5 if i4 else _lib.TranscodeExt4))
-        info_t = _lib.TranscodeExtInfo6 if rc else (
+        info_t = _lib.TranscodeExtInfo7 if frames is not None else _lib.TranscodeExtInfo6 if rc else (
             _lib.TranscodeExtInfo5 if pt else (_lib.TranscodeExtInfo4 if i4 else _lib.TranscodeExtInfo3))
-        ext7 = _lib.TranscodeExt7(_lib.TranscodeExt6(_lib.TranscodeExt5(_lib.TranscodeExt4(_lib.TranscodeExt3(
-            _lib.TranscodeExt2(_lib.TranscodeExt(C.sizeof(ext_t), subpel),
-                               1 if deblock else 0, int(deblock_offsets[0]), int(deblock_offsets[1])),
-            1 if mvcost else 0, int(mv_lambda16), 1 if early_skip else 0), 1 if cabac else 0),
+        ext8 = _lib.TranscodeExt8(_lib.TranscodeExt7(_lib.TranscodeExt6(_lib.TranscodeExt5(_lib.TranscodeExt4(
+            _lib.TranscodeExt3(
+                _lib.TranscodeExt2(_lib.TranscodeExt(C.sizeof(ext_t), subpel),
+                                   1 if deblock else 0, int(deblock_offsets[0]), int(deblock_offsets[1])),
+                1 if mvcost else 0, int(mv_lambda16), 1 if early_skip else 0), 1 if cabac else 0),
             1 if intra4x4 else 0), 1 if partitions else 0),
-            int(bitrate_kbps), int(qp_range[0]), int(qp_range[1]))
+            int(bitrate_kbps), int(qp_range[0]), int(qp_range[1])))
+        if frames is not None:
+            ext8.frame_first, ext8.frame_count = f0, f1 - f0
+        ext7 = ext8.base
         ext6 = ext7.base
         ext5 = ext6.base
         ext = ext5.base.base
-        xinfo6 = _lib.TranscodeExtInfo6(_lib.TranscodeExtInfo5(_lib.TranscodeExtInfo4(_lib.TranscodeExtInfo3(
-            _lib.TranscodeExtInfo2(_lib.TranscodeExtInfo(C.sizeof(info_t)))))))
+        xinfo7 = _lib.TranscodeExtInfo7(_lib.TranscodeExtInfo6(_lib.TranscodeExtInfo5(_lib.TranscodeExtInfo4(
+            _lib.TranscodeExtInfo3(_lib.TranscodeExtInfo2(_lib.TranscodeExtInfo(C.sizeof(info_t))))))))
+        xinfo6 = xinfo7.base
         xinfo5 = xinfo6.base
         xinfo4 = xinfo5.base
         xinfo3 = xinfo4.base
@@ -370,20 +393,19 @@ class VideoScorer:
             sw = (height * w + h) // (2 * h) * 2
             mbw, mbh = (sw + 15) // 16, (height + 15) // 16
         if want_commands:
-            commands = np.zeros((int(self.info.n_frames), mbh, mbw), np.uint32)
+            commands = np.zeros((nf, mbh, mbw), np.uint32)
             ext.cmd_out = commands.ctypes.data_as(C.POINTER(C.c_uint32))
             ext.cmd_cap = commands.size
         if want_intra4_modes:
-            modes = np.zeros((int(self.info.n_frames), mbh, mbw), np.uint64)
+            modes = np.zeros((nf, mbh, mbw), np.uint64)
             ext5.i4_out = modes.ctypes.data_as(C.POINTER(C.c_uint64))
             ext5.i4_cap = modes.size
         if want_vectors:
-            vectors = np.zeros((int(self.info.n_frames), mbh, mbw, 4), np.uint32)
+            vectors = np.zeros((nf, mbh, mbw, 4), np.uint32)
             ext6.mv_out = vectors.ctypes.data_as(C.POINTER(C.c_uint32))
             ext6.mv_cap = vectors.size
         qps_in = qps = bits = None
         if rc:
-            nf = int(self.info.n_frames)
             if frame_qp is not None:
                 wide = np.asarray(frame_qp, dtype=np.int64).reshape(-1)
                 # what a byte cannot hold would wrap in the cast (300 to 44) and get past the library's 1..51
@@ -399,10 +421,12 @@ class VideoScorer:
             ext7.bits_out = bits.ctypes.data_as(C.POINTER(C.c_uint32))
             ext7.frame_cap = nf
         _lib.check(self._lib.vts_transcode_ex(self._ctx, str(out_path).encode(), C.byref(prm),
-                                              C.cast(C.pointer(ext7), C.POINTER(_lib.TranscodeExt)),
+                                              C.cast(C.pointer(ext8), C.POINTER(_lib.TranscodeExt)),
                                               C.byref(info),
-                                              C.cast(C.pointer(xinfo6), C.POINTER(_lib.TranscodeExtInfo))))
+                                              C.cast(C.pointer(xinfo7), C.POINTER(_lib.TranscodeExtInfo))))
         extra = {}
+        if frames is not None:
+            extra.update(frame_first=int(xinfo7.frame_first), frame_count=int(xinfo7.frame_count))
         if rc:
             if xinfo6.frame_words != qps.size:
                 raise RuntimeError(f"{xinfo6.frame_words} frames reported, expected {qps.size}")
@@ -434,6 +458,39 @@ class VideoScorer:
                 "recon_hash": int(info.recon_hash), "bytes_written": info.bytes_written,
                 "decode_ms": info.ms[0], "search_ms": info.ms[1], "write_ms": info.ms[2],
                 "mux_ms": info.ms[3]}
+
+    def transcode_segment(self, out_path: str | Path, start: float, end: float, *, height: int = 0,
+                          **encoder) -> dict:
+        """Frame-accurate re-encode of [start, end) seconds into `out_path`
+        (the reference's extract_segment re-encode branch, DESIGN.md §11
+        "Segment re-encode"): the frames from the first one presented at or
+        after `start` through the last one presented before `end` (ffmpeg's
+        accurate seek; `boundary_frames`), transcoded at `height` lines (0: the
+        source's) with `encoder` = transcode's keywords, and every other track
+        of the source stream-copied beside them, cut to the kept frames'
+        presentation span so that both start at 0 (vts_add_tracks_range).
+        Raises VtsegError when no frame lies in the range.  Returns
+        transcode's facts with `bytes_written` of the final file and
+        `start` / `end`, the span of the kept frames in seconds."""
+        out_path = Path(out_path)
+        f0, f1 = self.boundary_frames([start, end])
+        if f1 <= f0:
+            raise _lib.VtsegError(_lib.VTS_E_INVALID, f"no frame is presented in [{start}, {end})")
+        pts, ts, n = self.frame_pts(), int(self.info.track_timescale), self.n_frames
+        if f0 + 1 < n:
+            delta = int(pts[f0 + 1] - pts[f0])
+        else:
+            delta = int(pts[f0] - pts[f0 - 1]) if f0 > 0 else max(1, ts // 30)
+        t0, t1 = int(pts[f0]) / ts, (int(pts[f1 - 1]) + delta) / ts
+        video_only = out_path.with_name(out_path.name + ".video.tmp")
+        try:
+            facts = self.transcode(video_only, height=height or int(self.info.height), frames=(f0, f1), **encoder)
+            _lib.check(self._lib.vts_add_tracks_range(str(video_only).encode(), str(self._path).encode(),
+                                                      t0, t1, str(out_path).encode()))
+        finally:
+            if video_only.exists():
+                video_only.unlink()
+        return {**facts, "bytes_written": out_path.stat().st_size, "start": t0, "end": t1}
 
     def close(self) -> None:
         if getattr(self, "_ctx", None):

@@ -113,12 +113,45 @@ def plan_segments(
     return out
 
 
+# The device re-encode's settings (extract_segment(device_reencode=True)): qp 23
+# is the reference's `-crf 23`; the rest turns on what the device encoder has
+# (VideoScorer.transcode's keywords).  `encoder=` overrides entries.
+SEGMENT_ENCODER = dict(qp=23, intra=True, intra4x4=True, subpel=2, deblock=True, mvcost=True,
+                       early_skip=True, cabac=True)
+
+
+def _device_reencode(input_path: Path, start: float, end: float, output_path: Path, device: int,
+                     encoder: dict | None) -> bool:
+    """extract_segment's device re-encode: True when output_path holds the
+    segment; on any failure nothing of it (nor its temporary file) is left."""
+    tmp = output_path.with_name(output_path.name + ".video.tmp")
+    try:
+        from .scene import VideoScorer
+        with VideoScorer(input_path, device=device) as v:
+            v.transcode_segment(output_path, float(start), float(end), **{**SEGMENT_ENCODER, **(encoder or {})})
+        if output_path.exists() and output_path.stat().st_size > 0:
+            return True
+    except Exception:   # the contract: never raises (no library, no device, a stream the decoder refuses ...)
+        pass
+    for p in (output_path, tmp):
+        try:
+            if p.exists():
+                p.unlink()
+        except OSError:
+            pass
+    return False
+
+
 def extract_segment(
     input_path: str | Path,
     start: float,
     end: float,
     output_path: str | Path,
     stream_copy: bool = True,
+    *,
+    device_reencode: bool = False,
+    device: int = 0,
+    encoder: dict | None = None,
 ) -> bool:
     """Cut [start, end] into output_path (video_segmenter.py:86-154).
 
@@ -129,6 +162,13 @@ def extract_segment(
     -t D -movflags +faststart -c copy``); other containers, a failed native
     copy and the re-encode fallback run the reference's ffmpeg commands
     (``%.3f`` timestamps, 120 s timeout).
+
+    Opt-in, ``device_reencode=True`` with ISO-BMFF input: before the ffmpeg
+    re-encode (after the copies when ``stream_copy``, first when not) the
+    segment is re-encoded on GPU ``device`` (``VideoScorer.transcode_segment``:
+    frame-accurate, the file starts at the first frame at or after ``start``;
+    the other tracks are stream-copied, cut to the same span) with
+    ``SEGMENT_ENCODER``'s settings, ``encoder`` overriding entries.
     """
     duration = end - start
     if duration <= 0:
@@ -166,6 +206,9 @@ def extract_segment(
             return True
         if output_path.exists():
             output_path.unlink()
+    if device_reencode and _is_isobmff(input_path):
+        if _device_reencode(input_path, start, end, output_path, device, encoder):
+            return True
     return run(head + ["-c:v", "libx264", "-preset", "veryfast", "-crf", "23",
                        "-c:a", "aac", "-b:a", "128k", str(output_path)])
 
