@@ -774,6 +774,54 @@ typedef struct vts_transcode_ext_info7 {
   int64_t frame_count;
 } vts_transcode_ext_info7;
 
+/* Adaptive quantisation, DESIGN.md §11 "Adaptive quantisation".  As the
+ * structs above: begun with them, passed by pointer cast, struct_size = their
+ * own sizeof.  Read: aq_strength_q8 when struct_size >= 188, aq_max at >= 192,
+ * mbqp_out at >= 200, mbqp_cap at >= 208 (a 184-byte vts_transcode_ext8 or
+ * anything smaller: off / NULL); written: mbqp_words at >= 152, aq_lo at >=
+ * 156, aq_hi at >= 160, aq_mbs at >= 168.
+ * aq_strength_q8 > 0: every macroblock of every picture gets a QP offset from
+ * the samples of the encoder's input picture alone (csrc/enc_aq.h, after
+ * x264's aq-mode 1): with E the sum over the macroblock's luma and two chroma
+ * blocks of (sum of squares - (sum)^2 / samples) and L = log2(max(E, 1)) in
+ * Q8, offset = clamp(round(aq_strength_q8 (L - 3693) / 65536), -aq_max,
+ * aq_max): flat macroblocks below the picture's QP, busy ones above.  The
+ * macroblock is coded at clamp(QP + offset, lo, hi), QP being qp, frame_qp[f]
+ * or the rate controller's, lo = qp_min where the caller gave one and 1
+ * where it is 0, hi = qp_max or 51 (not the controller's default 10: a
+ * macroblock with offset 0 keeps a frame_qp below 10; a frame_qp outside a
+ * given range is brought into it): the quantiser and the reconstruction, the
+ * early P_Skip probe, lambda16 of the vector cost and of the Intra_4x4 modes
+ * unless mv_lambda16 is given, and the in-loop filter's indices (from QP_Y of
+ * the two macroblocks at an edge) follow it.  The slices carry mb_qp_delta
+ * against the running QP of 7.4.5, which starts at SliceQPY (the picture's QP)
+ * in every slice; the parameter sets do not change.  The offsets are computed
+ * before the first level and do not depend on the rate controller, whose
+ * measure counts the true mb_qp_delta bits of intra macroblocks.
+ * mbqp_out: the QP of every macroblock, [frame][my][mx], as the offset and the
+ * picture's QP give it (a macroblock that sends no mb_qp_delta is decoded at
+ * the running QP; nothing of it depends on a QP); filled with any settings.
+ * VTS_E_INVALID, the field named: aq_strength_q8 outside 0 .. 768; aq_max
+ * outside 0 .. 10 or given without aq_strength_q8; aq_strength_q8 with qp < 0,
+ * with max_mb_sad < 0 or without mvcost = 1.  VTS_E_CAPACITY before any
+ * encoding: mbqp_out with mbqp_cap < n_frames * macroblocks.
+ * aq_strength_q8 = 0 is the call as it was, byte for byte. */
+typedef struct vts_transcode_ext9 {
+  vts_transcode_ext8 base;
+  int32_t aq_strength_q8;  /* 0 off; 1 .. 768 (256 = x264's strength 1.0)      */
+  int32_t aq_max;          /* largest |offset|: 0 = 8; 1 .. 10                  */
+  uint8_t *mbqp_out;       /* NULL, or mbqp_cap bytes: the QP of each macroblock */
+  int64_t mbqp_cap;
+} vts_transcode_ext9;
+
+typedef struct vts_transcode_ext_info8 {
+  vts_transcode_ext_info7 base;
+  int64_t mbqp_words;      /* n_frames * macroblocks                            */
+  int32_t aq_lo;           /* lowest offset used (0 with aq off)                */
+  int32_t aq_hi;           /* highest offset used                               */
+  int64_t aq_mbs;          /* macroblocks with a non-zero offset                */
+} vts_transcode_ext_info8;
+
 /* vts_transcode with the settings of `ext` (NULL: none) and the further facts
  * in `ext_info` (NULL: not wanted).  vts_transcode(c, o, p, i) is
  * vts_transcode_ex(c, o, p, NULL, i, NULL). */

@@ -75,6 +75,9 @@ constexpr int kNumCtx = 277;  // ctxIdx 0 .. 276: the frame-coded 4x4 syntax and
 //   32 bits): 28 + 6 x 95 = 598 bits over the inter macroblock's 45791 of the
 //   arithmetic just given, 46389 bits = 5799 bytes, 8699 with emulation
 //   prevention.  9024 bounds it.
+//   With adaptive quantisation (enc_aq.h) mb_qp_delta is up to 41 bins (|v| <=
+//   20) where 1 is counted above: 40 x 7 = 280 bits more, 46669 bits = 5834
+//   bytes, 8751 with emulation prevention.  9024 bounds it.
 constexpr int kMbBytes = 9024;
 
 #if defined(__HIPCC__)
@@ -277,6 +280,7 @@ struct Left {        // the macroblock to the left in the slice (mx = 0: kNone)
   uint32_t cbf;
   uint64_t i4 = ei4::kNoModes;  // I_NxN: its Intra4x4PredModes (enc_intra4.h), else ~0
   int bmvd[2] = {0, 0};         // |mvd_l0| of its quadrant 3 (amvd: of its quadrant 1; partitions, else unread)
+  bool dq = false;              // it sent a non-zero mb_qp_delta (adaptive quantisation; every `l = Left{..}` clears it)
 };
 VTS_HD VTS_INLINE Left left_none() { return Left{kNone, 0, 0, {0, 0}, 0, ei4::kNoModes}; }
 
@@ -389,6 +393,18 @@ template <class E>
 VTS_HD VTS_INLINE void mb_qp_delta0(E &e) {
   e.decision(60, 0);
 }
+// mb_qp_delta of any value (adaptive quantisation, enc_aq.h): the unary code of
+// the mapped value (9.3.2.7: 2 v - 1 for v > 0, else -2 v), bin 0 at ctxIdx 60 +
+// inc (inc: the previous macroblock of the slice sent a non-zero delta,
+// 9.3.3.1.1.5), bin 1 at 62, every later bin at 63.  |v| <= 20: at most 41 bins.
+template <class E>
+VTS_HD inline void mb_qp_delta(E &e, int inc, int v) {
+  const int m = v > 0 ? 2 * v - 1 : -2 * v;
+  e.decision(60 + inc, m > 0);
+  if (!m) return;
+  e.decision(62, m > 1);
+  for (int i = 2; i <= m; ++i) e.decision(63, i < m);
+}
 // residual_block_cabac (7.3.5.3.3) of lv[0 .. n) in scan order, ctxBlockCat
 // cat: 0 Intra16x16DCLevel, 1 Intra16x16ACLevel, 2 LumaLevel4x4, 3 chroma DC,
 // 4 chroma AC.  inc: transBlockA + 2 transBlockB of coded_block_flag.
@@ -435,6 +451,13 @@ VTS_HD inline int residual_block(E &e, int cat, int inc, const int16_t *lv, int 
 }
 
 // ------------------------------------------------------- macroblocks
+// mb_qp_delta = dqp of a macroblock whose left neighbour in the slice is l;
+// the mb_* functions below note a non-zero one in the Left they leave
+template <class E>
+VTS_HD VTS_INLINE void send_qp_delta(E &e, const Left &l, int dqp) {
+  if (dqp == 0 && !l.dq) mb_qp_delta0(e);
+  else mb_qp_delta(e, l.dq ? 1 : 0, dqp);
+}
 // condTermFlagN of coded_block_flag for a block outside the macroblock
 // (9.3.3.1.1.9): A by the left macroblock's bit, an absent macroblock by the
 // current one being intra
@@ -480,13 +503,13 @@ VTS_HD inline void mb_skip(E &e, Left &l, bool last) {
 // intra_chroma_pred_mode, 4..9 coded_block_pattern) and levels (DC at 0, the
 // 16 AC blocks of 15 at 16, chroma)
 template <class E>
-VTS_HD inline void mb_intra16(E &e, bool islice, Left &l, uint32_t cmd, const int16_t *cp, bool last) {
+VTS_HD inline void mb_intra16(E &e, bool islice, Left &l, uint32_t cmd, const int16_t *cp, bool last, int dqp = 0) {
   const int cbp = static_cast<int>(cmd >> 4) & 63, cmode = static_cast<int>(cmd >> 2) & 3;
   e.block_begin();
   if (!islice) mb_skip_flag(e, l, 0);
   mb_type_intra(e, islice, l, false, static_cast<int>(cmd & 3u), cbp >> 4, (cbp & 15) != 0);
   intra_chroma_pred_mode(e, l, cmode);
-  mb_qp_delta0(e);
+  send_qp_delta(e, l, dqp);
   uint32_t cbf = static_cast<uint32_t>(residual_block(e, 0, cbf_left(l, 0, true) + 2, cp, 16));
   if (cbp & 15)
     for (int k = 0; k < 16; ++k)
@@ -495,6 +518,7 @@ VTS_HD inline void mb_intra16(E &e, bool islice, Left &l, uint32_t cmd, const in
   cbf = chroma_residual(e, l, cp, cbp >> 4, true, cbf);
   e.terminate(last);
   l = Left{kI16, cbp, cmode, {0, 0}, cbf};
+  l.dq = dqp != 0;
 }
 // I_NxN (Intra_4x4) from its command word (bits 2..3 intra_chroma_pred_mode,
 // 4..9 coded_block_pattern), its Intra4x4PredModes and levels (the inter
@@ -503,7 +527,8 @@ VTS_HD inline void mb_intra16(E &e, bool islice, Left &l, uint32_t cmd, const in
 // coded_block_flag takes condTermFlag 1 for a neighbour outside the slice
 // (intra: cbf_inc_luma), mb_qp_delta is sent only with a pattern.
 template <class E>
-VTS_HD inline void mb_intra4(E &e, bool islice, Left &l, uint32_t cmd, uint64_t modes, const int16_t *cp, bool last) {
+VTS_HD inline void mb_intra4(E &e, bool islice, Left &l, uint32_t cmd, uint64_t modes, const int16_t *cp, bool last,
+                             int dqp = 0) {
   const int cbp = static_cast<int>(cmd >> 4) & 63, cmode = static_cast<int>(cmd >> 2) & 3;
   e.block_begin();
   if (!islice) mb_skip_flag(e, l, 0);
@@ -514,7 +539,7 @@ VTS_HD inline void mb_intra4(E &e, bool islice, Left &l, uint32_t cmd, uint64_t 
   coded_block_pattern(e, l, cbp);
   uint32_t cbf = 0;
   if (cbp) {
-    mb_qp_delta0(e);
+    send_qp_delta(e, l, dqp);
     for (int k = 0; k < 16; ++k)
       if ((cbp >> (k >> 2)) & 1)
         cbf |= static_cast<uint32_t>(residual_block(e, 2, cbf_inc_luma(l, cbf, k, true), cp + 16 * k, 16))
@@ -523,11 +548,12 @@ VTS_HD inline void mb_intra4(E &e, bool islice, Left &l, uint32_t cmd, uint64_t 
   }
   e.terminate(last);
   l = Left{kI4, cbp, cmode, {0, 0}, cbf, modes};
+  l.dq = cbp && dqp != 0;
 }
 // P_L0_16x16 with the vector difference (dx, dy), coded_block_pattern cbp and
 // levels (16 per luma block by luma4x4BlkIdx, chroma)
 template <class E>
-VTS_HD inline void mb_inter(E &e, Left &l, int dx, int dy, int cbp, const int16_t *cp, bool last) {
+VTS_HD inline void mb_inter(E &e, Left &l, int dx, int dy, int cbp, const int16_t *cp, bool last, int dqp = 0) {
   e.block_begin();
   mb_skip_flag(e, l, 0);
   mb_type_p16x16(e);
@@ -536,7 +562,7 @@ VTS_HD inline void mb_inter(E &e, Left &l, int dx, int dy, int cbp, const int16_
   coded_block_pattern(e, l, cbp);
   uint32_t cbf = 0;
   if (cbp) {
-    mb_qp_delta0(e);
+    send_qp_delta(e, l, dqp);
     for (int k = 0; k < 16; ++k)
       if ((cbp >> (k >> 2)) & 1)
         cbf |= static_cast<uint32_t>(residual_block(e, 2, cbf_inc_luma(l, cbf, k, false), cp + 16 * k, 16))
@@ -548,6 +574,7 @@ VTS_HD inline void mb_inter(E &e, Left &l, int dx, int dy, int cbp, const int16_
   l = Left{kInter, cbp, 0, {ax < 33 ? ax : 33, ay < 33 ? ay : 33}, cbf};
   l.bmvd[0] = l.amvd[0];
   l.bmvd[1] = l.amvd[1];
+  l.dq = cbp && dqp != 0;
 }
 // mb_type of the partitioned P macroblocks (Table 9-37): P_L0_L0_16x8 (1) bins
 // 0 1 1 at ctxIdx 14, 15, 17; P_L0_L0_8x16 (2) 0 1 0; P_8x8 (3) 0 0 1 at 14,
@@ -573,7 +600,7 @@ VTS_HD VTS_INLINE void mb_type_p_part(E &e, int shape) {
 // left inside the macroblock.
 template <class E>
 VTS_HD inline void mb_p_part(E &e, Left &l, int shape, const uint32_t *mv4, const epart::Left &lmv, int cbp,
-                             const int16_t *cp, bool last) {
+                             const int16_t *cp, bool last, int dqp = 0) {
   epart::Mv q[4];
   for (int i = 0; i < 4; ++i) q[i] = epart::mv_of_word(mv4[i]);
   e.block_begin();
@@ -601,7 +628,7 @@ VTS_HD inline void mb_p_part(E &e, Left &l, int shape, const uint32_t *mv4, cons
   coded_block_pattern(e, l, cbp);
   uint32_t cbf = 0;
   if (cbp) {
-    mb_qp_delta0(e);
+    send_qp_delta(e, l, dqp);
     for (int k = 0; k < 16; ++k)
       if ((cbp >> (k >> 2)) & 1)
         cbf |= static_cast<uint32_t>(residual_block(e, 2, cbf_inc_luma(l, cbf, k, false), cp + 16 * k, 16))
@@ -612,6 +639,7 @@ VTS_HD inline void mb_p_part(E &e, Left &l, int shape, const uint32_t *mv4, cons
   l = Left{kInter, cbp, 0, {cur[1][0], cur[1][1]}, cbf};
   l.bmvd[0] = cur[3][0];
   l.bmvd[1] = cur[3][1];
+  l.dq = cbp && dqp != 0;
 }
 // I_PCM up to the samples: mb_type through the terminate bin and the flush.
 // The caller writes pcm_alignment_zero_bits and the 384 samples (or leaves

@@ -12,7 +12,10 @@
 //   mb_*            macroblock_layer() of each kind from what a level holds
 //                   about it (command word, coded_block_pattern, levels, mode
 //                   word), from mb_skip_run on, leaving the Row as the
-//                   macroblock to the right finds it.
+//                   macroblock to the right finds it.  dqp is the mb_qp_delta
+//                   a macroblock sends when its syntax has one (enc_aq.h's
+//                   running-QP rule is the caller's; 0 without adaptive
+//                   quantisation).
 //
 // A slice is one macroblock row: neighbour B (above) is never available
 // across macroblocks, and A (left) is the previous macroblock of the slice.
@@ -291,7 +294,7 @@ VTS_EV VTS_INLINE void mb_skip(Row &z) {
 // P_L0_16x16 from its command word (the vector, mvx | mvy << 16),
 // coded_block_pattern and levels
 template <class Sink>
-VTS_EV void mb_inter(Sink &o, Row &z, uint32_t cmd, int cbp, const int16_t *cp) {
+VTS_EV void mb_inter(Sink &o, Row &z, uint32_t cmd, int cbp, const int16_t *cp, int dqp = 0) {
   const int mvx = static_cast<int16_t>(cmd & 0xffffu), mvy = static_cast<int16_t>(cmd >> 16);
   skip_run(o, false, z);
   o.ue(0);  // mb_type
@@ -300,7 +303,7 @@ VTS_EV void mb_inter(Sink &o, Row &z, uint32_t cmd, int cbp, const int16_t *cp) 
   o.ue(cbp_inter_code(cbp));
   z.clear();
   if (cbp) {
-    o.se(0);  // mb_qp_delta
+    o.se(dqp);  // mb_qp_delta
     luma_residual(o, cp, cbp, z);
     chroma_residual(o, cp, cbp >> 4, z);
   }
@@ -313,7 +316,7 @@ VTS_EV void mb_inter(Sink &o, Row &z, uint32_t cmd, int cbp, const int16_t *cp) 
 // the sub_mb_types, the mvds in syntax order against epart::pred_block (one
 // reference picture: no ref_idx_l0), then as mb_inter
 template <class Sink>
-VTS_EV void mb_p_part(Sink &o, Row &z, uint32_t cmd, const uint32_t *mv4, int cbp, const int16_t *cp) {
+VTS_EV void mb_p_part(Sink &o, Row &z, uint32_t cmd, const uint32_t *mv4, int cbp, const int16_t *cp, int dqp = 0) {
   const int shape = epart::part_shape(cmd);
   epart::Mv q[4];
   for (int i = 0; i < 4; ++i) q[i] = epart::mv_of_word(mv4[i]);
@@ -330,7 +333,7 @@ VTS_EV void mb_p_part(Sink &o, Row &z, uint32_t cmd, const uint32_t *mv4, int cb
   o.ue(cbp_inter_code(cbp));
   z.clear();
   if (cbp) {
-    o.se(0);  // mb_qp_delta
+    o.se(dqp);  // mb_qp_delta
     luma_residual(o, cp, cbp, z);
     chroma_residual(o, cp, cbp >> 4, z);
   }
@@ -343,12 +346,12 @@ VTS_EV void mb_p_part(Sink &o, Row &z, uint32_t cmd, const uint32_t *mv4, int cb
 // slice), from its command word (bits 0..1 Intra16x16PredMode, 2..3
 // intra_chroma_pred_mode, 4..9 coded_block_pattern) and levels
 template <class Sink>
-VTS_EV void intra16_layer(Sink &o, bool islice, Row &z, uint32_t cmd, const int16_t *cp) {
+VTS_EV void intra16_layer(Sink &o, bool islice, Row &z, uint32_t cmd, const int16_t *cp, int dqp = 0) {
   const int cbp = static_cast<int>(cmd >> 4) & 63;
   const uint32_t mbt = 1 + (cmd & 3u) + 4 * static_cast<uint32_t>(cbp >> 4) + ((cbp & 15) ? 12 : 0);
   o.ue(islice ? mbt : 5 + mbt);
   o.ue((cmd >> 2) & 3u);  // intra_chroma_pred_mode
-  o.se(0);                // mb_qp_delta
+  o.se(dqp);              // mb_qp_delta
   z.clear();
   luma16_residual(o, cp, cbp, z);
   chroma_residual(o, cp, cbp >> 4, z);
@@ -360,7 +363,7 @@ VTS_EV void intra16_layer(Sink &o, bool islice, Row &z, uint32_t cmd, const int1
 // its Intra4x4PredModes and levels (the inter layout).  There is no
 // transform_size_8x8_flag: the PPS has no 8x8 transform.
 template <class Sink>
-VTS_EV void intra4_layer(Sink &o, bool islice, Row &z, uint32_t cmd, uint64_t modes, const int16_t *cp) {
+VTS_EV void intra4_layer(Sink &o, bool islice, Row &z, uint32_t cmd, uint64_t modes, const int16_t *cp, int dqp = 0) {
   const int cbp = static_cast<int>(cmd >> 4) & 63;
   o.ue(islice ? 0 : 5);
   for (int k = 0; k < 16; ++k) {
@@ -372,7 +375,7 @@ VTS_EV void intra4_layer(Sink &o, bool islice, Row &z, uint32_t cmd, uint64_t mo
   o.ue(cbp_intra_code(cbp));
   z.clear();
   if (cbp) {
-    o.se(0);  // mb_qp_delta
+    o.se(dqp);  // mb_qp_delta
     luma_residual(o, cp, cbp, z);
     chroma_residual(o, cp, cbp >> 4, z);
   }
@@ -380,14 +383,14 @@ VTS_EV void intra4_layer(Sink &o, bool islice, Row &z, uint32_t cmd, uint64_t mo
   z.left_is(modes, false, 0, 0);
 }
 template <class Sink>
-VTS_EV void mb_intra16(Sink &o, bool islice, Row &z, uint32_t cmd, const int16_t *cp) {
+VTS_EV void mb_intra16(Sink &o, bool islice, Row &z, uint32_t cmd, const int16_t *cp, int dqp = 0) {
   skip_run(o, islice, z);
-  intra16_layer(o, islice, z, cmd, cp);
+  intra16_layer(o, islice, z, cmd, cp, dqp);
 }
 template <class Sink>
-VTS_EV void mb_intra4(Sink &o, bool islice, Row &z, uint32_t cmd, uint64_t modes, const int16_t *cp) {
+VTS_EV void mb_intra4(Sink &o, bool islice, Row &z, uint32_t cmd, uint64_t modes, const int16_t *cp, int dqp = 0) {
   skip_run(o, islice, z);
-  intra4_layer(o, islice, z, cmd, modes, cp);
+  intra4_layer(o, islice, z, cmd, modes, cp, dqp);
 }
 // I_PCM up to the samples: mb_skip_run and mb_type.  The caller writes
 // pcm_alignment_zero_bits and the 384 samples, or leaves their gap.

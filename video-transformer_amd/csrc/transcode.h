@@ -55,6 +55,9 @@ struct SearchArgs {
   uint32_t *est_f;               // [frame] the rate measure, bits: the final decisions of this kernel add into it
   int32_t mv_lambda16;           // qp_f: the caller's lambda16 (> 0 replaces the table's at every QP)
   int32_t pcm_bits;              // est_f: what a macroblock left as I_PCM adds (0 with intra: enc_intra decides it)
+  // RC only (vts_transcode_ext9, enc_aq.h; NULL: off)
+  const int8_t *aq_off;          // [frame][mb] the macroblock's QP offset: it is coded at clamp(QP + offset, aq_lo, aq_hi)
+  int32_t aq_lo, aq_hi;
 };
 
 // ------------------------------------------------------ slice writer
@@ -80,6 +83,8 @@ struct WriteArgs {
   const uint64_t *i4;   // [entry][mb] the Intra4x4PredModes of the I_NxN macroblocks (intra4x4; else unread)
   const uint32_t *mv4;  // [entry][mb][4] the quadrant vectors (partitions; else NULL and unread)
   const uint8_t *qp_f;  // [frame] NULL, or the QP of each picture in place of qp (vts_transcode_ext7)
+  const int8_t *aq_off; // [frame][mb] NULL, or the macroblocks' QP offsets (vts_transcode_ext9): mb_qp_delta is written
+  int32_t aq_lo, aq_hi; // ... a macroblock's QP is clamp(QP + offset, aq_lo, aq_hi)
 };
 
 // ------------------------------------------------------ intra coding
@@ -98,6 +103,8 @@ struct IntraArgs {
   uint64_t *i4;         // enc_intra<true>: [entry][mb] the Intra4x4PredModes of an I_NxN macroblock, else ~0
   const uint8_t *qp_f;  // [frame] NULL, or the QP of each picture in place of qp (vts_transcode_ext7)
   uint32_t *est_f;      // [frame] NULL, or the rate measure: the bits of the macroblocks decided here are added
+  const int8_t *aq_off; // [frame][mb] NULL, or the macroblocks' QP offsets (vts_transcode_ext9)
+  int32_t aq_lo, aq_hi; // ... a macroblock's QP is clamp(QP + offset, aq_lo, aq_hi)
 };
 
 // ------------------------------------------------------ in-loop deblocking
@@ -113,6 +120,19 @@ struct DeblockArgs {
   unsigned long long *count;       // macroblocks with a filtered line
   const uint32_t *mv4;             // [entry][mb][4] the quadrant vectors (partitions; else NULL and unread)
   const uint8_t *qp_f;             // [frame] NULL, or the SliceQPY of each picture in place of qp (vts_transcode_ext7)
+  const int8_t *aq_off;            // [frame][mb] NULL, or the macroblocks' QP offsets (vts_transcode_ext9): an edge's
+  int32_t aq_lo, aq_hi;            // indices come from the QP_Y of the macroblocks on its two sides
+};
+
+// ------------------------------------------------------ adaptive quantisation
+// enc_aq (enc_aq.h) once per call, ahead of level 0: the offset of every
+// macroblock of every frame from the encoder's input pictures
+struct AqArgs {
+  const uint8_t *small;  // [frame] the encoder's input pictures (NV12, cw x ch)
+  int64_t stride;
+  int32_t cw, ch, mbw, mbh;
+  int32_t strength_q8, aq_max;
+  int8_t *aq_off;        // [frame][mb]
 };
 
 // ------------------------------------------------------ rate control
@@ -164,6 +184,7 @@ void launch_enc_search(const SearchArgs &a, int subpel, bool rate_aware, bool pa
 void launch_enc_intra(const IntraArgs &a, bool intra4x4, int64_t entries, hipStream_t s);
 void launch_enc_deblock(const DeblockArgs &a, int64_t entries, hipStream_t s);
 void launch_enc_rc(const RcArgs &a, hipStream_t s);
+void launch_enc_aq(const AqArgs &a, int64_t frames, hipStream_t s);
 void launch_enc_hash(const HashArgs &a, int64_t entries, hipStream_t s);
 void launch_enc_write(const WriteArgs &a, bool cabac, bool intra, bool deblock, hipStream_t s);  // a.n_slices slices
 void launch_enc_pack(const PackArgs &a, int64_t entries, int32_t nmb, hipStream_t s);
@@ -173,7 +194,7 @@ void launch_enc_pack(const PackArgs &a, int64_t entries, int32_t nmb, hipStream_
 constexpr uint32_t kPcmCmdWord = 0x80008000u;  // the command word of an I_PCM macroblock (enc_deblock.h kPcmCmd)
 constexpr uint64_t kNoI4Modes = ~0ull;         // the mode word of a macroblock that is not I_NxN (enc_intra4.h kNoModes)
 constexpr int32_t kPcmMbBits = 3072;           // the rate measure of an I_PCM macroblock: its payload (kPcmBits)
-int64_t slice_slot_bytes(int mbw, bool cabac);    // staging slot of one slice (a macroblock row)
+int64_t slice_slot_bytes(int mbw, bool cabac, bool aq = false);  // staging slot of one slice (a macroblock row)
 int32_t search_lambda16(int qp, int mv_lambda16);  // SearchArgs.lambda16 (enc_rate.h lambda16)
 
 }  // namespace vts

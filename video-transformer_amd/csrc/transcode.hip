@@ -31,12 +31,17 @@
 //      opt-in (vts_transcode_ext7): every stage reads a picture's QP from a
 //      per-frame array, and with a bitrate `enc_rc` — one thread per GOP
 //      between two levels sets the next picture's QP (enc_ratectl.h);
+//      opt-in (vts_transcode_ext9): `enc_aq` — ahead of level 0, four
+//      macroblocks a wave — gives every macroblock a QP offset from its
+//      source samples (enc_aq.h), every stage codes it at its own QP and the
+//      writers send mb_qp_delta;
 //   4. host: MP4 mux (Mp4Writer) in display order.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <type_traits>
 
+#include "enc_aq.h"
 #include "enc_cabac.h"
 #include "enc_cavlc.h"
 #include "enc_deblock.h"
@@ -77,6 +82,7 @@ namespace eres = full::eres;  // the transform, the quantiser and the reconstruc
 namespace ei4 = full::ei4;    // the Intra_4x4 decisions (enc_intra4.h)
 namespace ecav = full::ecav;  // the CAVLC slice writer and its bit counts (enc_cavlc.h)
 namespace ep = full::epart;   // the inter partitions (enc_part.h)
+namespace eaq = full::eaq;    // adaptive quantisation: the law and the running-QP rule (enc_aq.h)
 
 // ------------------------------------------------------ motion search
 __device__ __forceinline__ uint32_t u32_at(const uint8_t *lds_row, int off) {  // 4 bytes at any offset
@@ -782,7 +788,8 @@ __device__ __forceinline__ bool finish_residual(const SearchArgs &a, int lane, c
 // the integer-only kernel's), 1 half samples, 2 half then quarter samples.
 // RC: the rate-aware decisions of enc_rate.h, each switched by a bit of
 // a.rate (wave-uniform), and with them the per-picture QP and the rate measure
-// of vts_transcode_ext7 (a.qp_f, a.est_f; NULL: off, a runtime test each);
+// of vts_transcode_ext7 (a.qp_f, a.est_f; NULL: off, a runtime test each) and
+// the macroblock's QP offset of vts_transcode_ext9 (a.aq_off, the same way);
 // false: the code is the kernel's without them.  Every
 // instance asks for 5 waves/SIMD: they fit (88 .. 90 VGPRs, no scratch), but
 // left to itself the register allocator settles at 98 .. 102 and 4 waves.
@@ -820,6 +827,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT ? 4 
     o.mvbits = 0;
     if (a.qp_f) {  // wave-uniform: the picture's own QP, and the lambda that follows it
       a.qp = a.qp_f[en.x];
+      a.lambda16 = er::lambda16(a.qp, a.mv_lambda16);
+    }
+    if (a.aq_off) {  // wave-uniform: the macroblock's own QP (enc_aq.h), and the lambda that follows it
+      a.qp = eaq::qp_mb(a.qp, a.aq_off[static_cast<int64_t>(en.x) * a.nmb + mb], a.aq_lo, a.aq_hi);
       a.lambda16 = er::lambda16(a.qp, a.mv_lambda16);
     }
     const bool coded = a.qp >= 1 && a.max_sad >= 0;
@@ -944,7 +955,10 @@ using full::edb::is_intra_cmd;
 // the block into the tile.  The levels wait in LDS for the bit count, which
 // lanes 0..15 then take a block each as the Intra16x16 candidate's.
 // false: the code is the kernel's without it.
-template <bool kI4>
+// kAq (vts_transcode_ext9, enc_aq.h): a macroblock's QP is its own, from
+// a.aq_off; false: the code is the kernel's without it (a runtime test of the
+// pointer costs enc_intra<true> scratch).
+template <bool kI4, bool kAq>
 __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
   __shared__ __attribute__((aligned(16))) uint32_t srcy[64], recy[64];
   __shared__ uint16_t srcc[64];
@@ -961,7 +975,13 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
   const uint8_t *src = a.small + static_cast<int64_t>(en.x) * a.stride;
   uint8_t *dst = a.recon + static_cast<int64_t>(en.z) * a.stride;
   const int64_t mb0 = (static_cast<int64_t>(e) * a.mbh + my) * a.mbw;
-  const int qp = a.qp_f ? a.qp_f[en.x] : a.qp, qpc = kQpcTab[qp];  // wave-uniform: the picture's own QP when given
+  const int qp_pic = a.qp_f ? a.qp_f[en.x] : a.qp, qpc_pic = kQpcTab[qp_pic];  // wave-uniform: the picture's own QP when given
+  // kAq: every macroblock has its own QP, and the bits of its mb_qp_delta
+  // follow the slice's running QP (enc_aq.h), which the walk keeps over the
+  // macroblocks it does not code too
+  const int8_t *aqr = kAq ? a.aq_off + (static_cast<int64_t>(en.x) * a.mbh + my) * a.mbw : nullptr;
+  eaq::RunQp rq;
+  rq.start(qp_pic);
   const int ly = lane >> 2, lx = 4 * (lane & 3), ci = lane & 7, cj = lane >> 3;
   uint32_t row_bits = 0;  // the rate measure of the macroblocks this wave decides (a.est_f)
   if (lane < 4) lnz[lane] = -1;
@@ -969,7 +989,9 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
   bool left_mine = false;  // the left macroblock was coded by this wave: its column is in left_y / left_c
   [[maybe_unused]] uint64_t left_modes = ei4::kNoModes;  // kI4: the left macroblock's Intra4x4PredModes when it is I_NxN
   for (int mx = 0; mx < a.mbw; ++mx) {
+    const int qp = kAq ? eaq::qp_mb(qp_pic, aqr[mx], a.aq_lo, a.aq_hi) : qp_pic, qpc = kAq ? kQpcTab[qp] : qpc_pic;  // wave-uniform
     if (!a.all && a.cmd[mb0 + mx] != kPcmCmd) {  // wave-uniform
+      if constexpr (kAq) rq.step(a.cbp[mb0 + mx] != 0, qp);  // enc_search's: inter, its delta sent with a pattern
       left_mine = false;
       if constexpr (kI4) left_modes = ei4::kNoModes;
       continue;
@@ -1112,6 +1134,10 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
       contrib = ecav::ue_bits(static_cast<uint32_t>(a.all ? mbt : 5 + mbt)) + ecav::ue_bits(static_cast<uint32_t>(cmode)) + 1 +
                 ecav::count_block(dlv, 16, ecav::nc_luma(0, tcy, lnz));
     }
+    // mb_qp_delta of either candidate against the running QP: se(0) is the one bit counted above
+    const int dq_extra = kAq ? eaq::se_bits(qp - rq.pred) - 1 : 0;
+    if constexpr (kAq)
+      if (lane == 26) contrib += dq_extra;
     [[maybe_unused]] int own = 0;  // kI4: lanes 16..25 hold the chroma bits, the same for both candidates
     if constexpr (kI4) own = contrib;
 #pragma unroll
@@ -1202,7 +1228,7 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
         c4 = own;
       } else if (lane == 26) {  // mb_type, the sixteen modes, intra_chroma_pred_mode, coded_block_pattern, mb_qp_delta
         c4 = ecav::ue_bits(a.all ? 0u : 5u) + mbits + ecav::ue_bits(static_cast<uint32_t>(cmode)) +
-             ecav::ue_bits(ecav::cbp_intra_code(cbp4)) + (cbp4 ? 1 : 0);
+             ecav::ue_bits(ecav::cbp_intra_code(cbp4)) + (cbp4 ? 1 + dq_extra : 0);
       }
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) c4 += __shfl_xor(c4, off);
@@ -1216,6 +1242,7 @@ __global__ void __launch_bounds__(64) enc_intra(IntraArgs a) {
     }
     const bool intra = contrib <= kPcmBits;  // wave-uniform
     row_bits += static_cast<uint32_t>(intra ? contrib : kPcmBits);
+    if constexpr (kAq) rq.step(intra && (!(kI4 && use4) || cbp4 != 0), qp);  // Intra16x16 always sends its delta, I_NxN with a pattern
     if constexpr (kI4) {
       if (intra && use4) {
         // I_NxN: luma is reconstructed (recy, above); chroma as Intra16x16; luma levels in the inter layout
@@ -1350,6 +1377,12 @@ __global__ void __launch_bounds__(64) enc_deblock(DeblockArgs a) {
   const edb::Idx x_pcm = edb::indices(0, 0, a.off_a, a.off_b, chroma, 0);
   const edb::Idx x_mix = edb::indices(0, qp, a.off_a, a.off_b, chroma, 0);
   const edb::Idx x_qp = edb::indices(qp, qp, a.off_a, a.off_b, chroma, 0);
+  // a.aq_off: the macroblocks have their own QPs (enc_aq.h).  QP_Y of one that sent no mb_qp_delta is the
+  // slice's running QP, which this walk keeps; an edge's indices are looked up from its two sides' QP_Y
+  const int8_t *aqr = a.aq_off ? a.aq_off + (static_cast<int64_t>(en.x) * a.mbh + my) * a.mbw : nullptr;
+  eaq::RunQp rq;
+  rq.start(qp);
+  int qy_left = 0, qy_cur = 0;  // aqr: QP_Y of the left and of this macroblock as the filter reads them (I_PCM 0)
   uint32_t carry = 0;  // lanes 0..23: the row's last dword of the macroblock to the left
   edb::Mb left = edb::mb_of_cmd(kPcmCmd, 0);
   bool prev_filtered = false;  // wave-uniform
@@ -1358,6 +1391,11 @@ __global__ void __launch_bounds__(64) enc_deblock(DeblockArgs a) {
     if (lane < 32) *reinterpret_cast<uint32_t *>(tc + 4) = pf_c;
     if (lane < 24) *reinterpret_cast<uint32_t *>(T + lane * kDbPitch) = carry;
     const uint32_t cmd = n_cmd;
+    if (aqr) {  // wave-uniform
+      const bool pcm = cmd == kPcmCmd;
+      rq.step(eaq::sends_delta(pcm, is_intra_cmd(cmd) && !ei4::is_i4_cmd(cmd), n_cbp), eaq::qp_mb(qp, aqr[mx], a.aq_lo, a.aq_hi));
+      qy_cur = rq.filter_qp(pcm);
+    }
     const bool nzb = lane < 16 && edb::blk_nz(n_lv.s, n_cbp, lane);
     [[maybe_unused]] const uint4 mv = n_mv;
     if (mx + 1 < a.mbw) {
@@ -1388,7 +1426,8 @@ __global__ void __launch_bounds__(64) enc_deblock(DeblockArgs a) {
           qpp = edb::qp_of(p, qp);
         }
         const int qpq = edb::qp_of(cur, qp);
-        const edb::Idx x = qpp != qpq ? x_mix : (qpp ? x_qp : x_pcm);
+        edb::Idx x = qpp != qpq ? x_mix : (qpp ? x_qp : x_pcm);
+        if (aqr) x = edb::indices(ed == 0 ? qy_left : qy_cur, qy_cur, a.off_a, a.off_b, chroma, 0);
         const bool act = bS > 0 && x.alpha && x.beta;
         if (__ballot(act)) {  // wave-uniform
           if (act) {
@@ -1419,6 +1458,7 @@ __global__ void __launch_bounds__(64) enc_deblock(DeblockArgs a) {
     if (wave_filtered && lane == 0) atomicAdd(a.count, 1ull);
     prev_filtered = wave_filtered;
     left = cur;
+    qy_left = qy_cur;
   }
   if (prev_filtered && lane < 24) {  // the last macroblock's columns 12..15
     uint8_t *g = lane < 16 ? dst + static_cast<int64_t>(my * 16 + lane) * a.cw
@@ -1487,7 +1527,10 @@ __device__ void pcm_gap(NalOut &o, uint4 *job, int s, int mx) {
 // ran on the reconstruction); false: the header, and the code, without it.
 // kPart: a command may be a partitioned macroblock's (enc_part.h), its vectors
 // in a.mv4; false: the code is the kernel's without partitions
-template <bool kIntra, bool kDbk, bool kPart>
+// kAq: the macroblocks have their own QPs (a.aq_off, enc_aq.h) and send
+// mb_qp_delta; false: the code is the kernel's without it (a runtime test of
+// the pointer costs both writers registers, and some instances a wave)
+template <bool kIntra, bool kDbk, bool kPart, bool kAq>
 __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= a.n_slices) return;
@@ -1519,32 +1562,40 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
   uint4 *job = a.jobs + (njob ? atomicAdd(a.n_jobs, njob) : 0u);
   ecav::Row z;
   z.start();
+  // kAq: the macroblocks' own QPs; mb_qp_delta by the slice's running QP (enc_aq.h), else 0 as ever
+  const int8_t *aqr = kAq ? a.aq_off + (static_cast<int64_t>(en.x) * a.mbh + row) * a.mbw : nullptr;
+  eaq::RunQp rq;
+  rq.start(qp);
   for (int mx = 0; mx < a.mbw; ++mx) {
     const uint32_t c = all_pcm ? kPcmCmd : cmd[mx];
     const int16_t *cp = coef_row + static_cast<int64_t>(mx) * kCoefPerMb;
+    int dqp = 0;
+    if (aqr)
+      dqp = rq.step(eaq::sends_delta(c == kPcmCmd, is_intra_cmd(c) && !ei4::is_i4_cmd(c), cbpr[mx]),
+                    eaq::qp_mb(qp, aqr[mx], a.aq_lo, a.aq_hi));
     if (c == kPcmCmd) {
       ecav::mb_pcm_head(o, idr, z);
       pcm_gap(o, job++, s, mx);
       ++npcm;
     } else if (kIntra && ei4::is_i4_cmd(c)) {
-      ecav::mb_intra4(o, idr, z, c, i4r[mx], cp);
+      ecav::mb_intra4(o, idr, z, c, i4r[mx], cp, dqp);
       ++nintra;
       ++ni4;
     } else if (kIntra && is_intra_cmd(c)) {
-      ecav::mb_intra16(o, idr, z, c, cp);
+      ecav::mb_intra16(o, idr, z, c, cp, dqp);
       ++nintra;
     } else if (c == 0 && cbpr[mx] == 0) {  // P_Skip: vector (0, 0), nothing coded
       ecav::mb_skip(z);
       ++nskip;
     } else if (kPart && ep::is_part_cmd(c)) {
-      ecav::mb_p_part(o, z, c, mv4r + 4 * mx, cbpr[mx], cp);
+      ecav::mb_p_part(o, z, c, mv4r + 4 * mx, cbpr[mx], cp, dqp);
       ++ninter;
       const int shape = ep::part_shape(c);
       n16x8 += shape == ep::k16x8;
       n8x16 += shape == ep::k8x16;
       n8x8 += shape == ep::k8x8;
     } else {
-      ecav::mb_inter(o, z, c, cbpr[mx], cp);
+      ecav::mb_inter(o, z, c, cbpr[mx], cp, dqp);
       ++ninter;
     }
   }
@@ -1588,7 +1639,7 @@ __global__ void __launch_bounds__(64) enc_write(WriteArgs a) {
 // (downscale clamp), and pcm_gap's argument holds as it does for CAVLC: no
 // emulation prevention byte falls in or next to the samples and the zero run
 // after them is 0.  The encoder restarts behind them (9.3.1.2).
-template <bool kIntra, bool kDbk, bool kPart>
+template <bool kIntra, bool kDbk, bool kPart, bool kAq>
 __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
   namespace ec = full::ecab;
   __shared__ uint8_t st[320];             // ec::kNumCtx context variables
@@ -1632,10 +1683,18 @@ __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
     ec::slice_header(o, idr, row * a.mbw, en.y, en.z, qp, kDbk, a.dbk_alpha, a.dbk_beta);
   }
   const int16_t *lv = reinterpret_cast<const int16_t *>(lvw);
+  // kAq: as in enc_write; ctxIdxInc of the delta's first bin travels in ec::Left
+  const int8_t *aqr = kAq ? a.aq_off + (static_cast<int64_t>(en.x) * a.mbh + row) * a.mbw : nullptr;
+  eaq::RunQp rq;
+  rq.start(qp);
   for (int mx = 0; mx < a.mbw; ++mx) {
     const uint32_t c = all_pcm ? kPcmCmd : cmd[mx];  // wave-uniform
     const bool intra = kIntra && is_intra_cmd(c);
     const int cbp = (c == kPcmCmd || intra) ? 0 : cbpr[mx];
+    int dqp = 0;
+    if (aqr)  // an I_NxN macroblock's pattern is in its command word
+      dqp = rq.step(eaq::sends_delta(c == kPcmCmd, intra && !ei4::is_i4_cmd(c), intra ? static_cast<int>(c >> 4) & 63 : cbp),
+                    eaq::qp_mb(qp, aqr[mx], a.aq_lo, a.aq_hi));
     __syncthreads();  // lane 0 is done with the previous macroblock's levels (and, first, the contexts are set)
     if (intra || cbp) {
       const uint32_t *src = reinterpret_cast<const uint32_t *>(coef_row + static_cast<int64_t>(mx) * kCoefPerMb);
@@ -1651,18 +1710,18 @@ __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
       a_ok = false;
       ++npcm;
     } else if (intra && ei4::is_i4_cmd(c)) {
-      ec::mb_intra4(enc, idr, left, c, i4r[mx], lv, last);
+      ec::mb_intra4(enc, idr, left, c, i4r[mx], lv, last, dqp);
       a_ok = false;
       ++nintra;
       ++ni4;
     } else if (intra) {
-      ec::mb_intra16(enc, idr, left, c, lv, last);
+      ec::mb_intra16(enc, idr, left, c, lv, last, dqp);
       a_ok = false;
       ++nintra;
     } else if (kPart && ep::is_part_cmd(c)) {
       const uint32_t *v = mv4r + 4 * mx;
       const int shape = ep::part_shape(c);
-      ec::mb_p_part(enc, left, shape, v, ep::Left{a_ok, {amx, amy}, {a3x, a3y}}, cbp, lv, last);
+      ec::mb_p_part(enc, left, shape, v, ep::Left{a_ok, {amx, amy}, {a3x, a3y}}, cbp, lv, last, dqp);
       ++ninter;
       n16x8 += shape == ep::k16x8;
       n8x16 += shape == ep::k8x16;
@@ -1678,7 +1737,7 @@ __global__ void __launch_bounds__(64) enc_write_cabac(WriteArgs a) {
         ec::mb_skip(enc, left, last);
         ++nskip;
       } else {
-        ec::mb_inter(enc, left, mvx - (a_ok ? amx : 0), mvy - (a_ok ? amy : 0), cbp, lv, last);  // 8.4.1.3, A alone
+        ec::mb_inter(enc, left, mvx - (a_ok ? amx : 0), mvy - (a_ok ? amy : 0), cbp, lv, last, dqp);  // 8.4.1.3, A alone
         ++ninter;
       }
       a_ok = true;
@@ -1789,6 +1848,60 @@ __global__ void __launch_bounds__(64) enc_pcm(const uint4 *jobs, const uint32_t 
   }
 }
 
+// The macroblocks' QP offsets (vts_transcode_ext9; enc_aq.h), once per call
+// ahead of level 0.  Pure streaming, one read of the input pictures: a wave
+// takes four macroblocks side by side.  Lane (r, m) = (lane / 4, lane % 4)
+// loads the 16 bytes of luma row r of macroblock m, so the four lanes of a row
+// read 64 contiguous bytes, and below lane 32 the 16 bytes (8 Cb|Cr pairs) of
+// its chroma row r.  A dword gives S1 by a SAD against 0 and S2 by a dot
+// product with itself; the sixteen lanes of a macroblock are summed by
+// butterflies over lane bits 2..5.  No LDS.  The grid covers whole groups of
+// four: a lane whose macroblock lies past the picture's width loads nothing.
+__global__ void __launch_bounds__(64) enc_aq(AqArgs a) {
+  const int lane = threadIdx.x, r = lane >> 2, m = lane & 3;
+  const int groups = (a.mbw + 3) >> 2;
+  const int g = blockIdx.x % groups, my = (blockIdx.x / groups) % a.mbh;
+  const int64_t f = blockIdx.x / (groups * a.mbh);
+  const int mx = 4 * g + m;
+  const bool in = mx < a.mbw;
+  const uint8_t *pic = a.small + f * a.stride;
+  uint32_t s1y = 0, s2y = 0, s1u = 0, s2u = 0, s1v = 0, s2v = 0;
+  if (in) {
+    const uint4 y = *reinterpret_cast<const uint4 *>(pic + static_cast<int64_t>(my * 16 + r) * a.cw + mx * 16);
+    const uint32_t yw[4] = {y.x, y.y, y.z, y.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      s1y = __builtin_amdgcn_sad_u8(yw[k], 0u, s1y);
+      s2y = __builtin_amdgcn_udot4(yw[k], yw[k], s2y, false);
+    }
+    if (r < 8) {
+      const uint4 c = *reinterpret_cast<const uint4 *>(pic + static_cast<int64_t>(a.cw) * a.ch +
+                                                       static_cast<int64_t>(my * 8 + r) * a.cw + mx * 16);
+      const uint32_t cw4[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t u = cw4[k] & 0x00ff00ffu, v = (cw4[k] >> 8) & 0x00ff00ffu;
+        s1u = __builtin_amdgcn_sad_u8(u, 0u, s1u);
+        s2u = __builtin_amdgcn_udot4(u, u, s2u, false);
+        s1v = __builtin_amdgcn_sad_u8(v, 0u, s1v);
+        s2v = __builtin_amdgcn_udot4(v, v, s2v, false);
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 4; off < 64; off <<= 1) {
+    s1y += __shfl_xor(s1y, off);
+    s2y += __shfl_xor(s2y, off);
+    s1u += __shfl_xor(s1u, off);
+    s2u += __shfl_xor(s2u, off);
+    s1v += __shfl_xor(s1v, off);
+    s2v += __shfl_xor(s2v, off);
+  }
+  if (in && r == 0)
+    a.aq_off[(f * a.mbh + my) * a.mbw + mx] =
+        static_cast<int8_t>(eaq::offset_of_energy(eaq::energy(s1y, s2y, s1u, s2u, s1v, s2v), a.strength_q8, a.aq_max));
+}
+
 // The rate controllers (vts_transcode_ext7.bitrate_kbps; enc_ratectl.h), one
 // per GOP, behind level j on the search stream: thread t takes entry t of
 // level j + 1, whose previous picture is frame - 1 of the same GOP.  A GOP's
@@ -1831,8 +1944,13 @@ static_assert(kPcmMbBits == kPcmBits, "... and the I_PCM payload's bits");
 // bounded in CAVLC bits, which bounds no CABAC length: the slot holds the
 // worst case of the bins themselves (full::ecab::kMbBytes, derived there; the
 // larger of the two bounds)
-int64_t slice_slot_bytes(int mbw, bool cabac) {
-  return ((64 + static_cast<int64_t>(mbw) * (cabac ? std::max(600, full::ecab::kMbBytes) : 600)) + 255) & ~int64_t(255);
+// aq: mb_qp_delta is se(v) of up to 11 bits where 1 was counted, 2 bytes more a
+// macroblock in CAVLC; in CABAC up to 41 bins where 1 was, 40 x 7 bits = 35
+// bytes, 53 with emulation prevention, on top of the 8628 / 8699 that
+// enc_cabac.h derives: kMbBytes still bounds it
+int64_t slice_slot_bytes(int mbw, bool cabac, bool aq) {
+  const int cavlc = aq ? 602 : 600;
+  return ((64 + static_cast<int64_t>(mbw) * (cabac ? std::max(cavlc, full::ecab::kMbBytes) : cavlc)) + 255) & ~int64_t(255);
 }
 
 int32_t search_lambda16(int qp, int mv_lambda16) { return er::lambda16(qp, mv_lambda16); }
@@ -1858,7 +1976,9 @@ void launch_enc_search(const SearchArgs &a, int subpel, bool rate_aware, bool pa
 // one wave per (entry, macroblock row)
 void launch_enc_intra(const IntraArgs &a, bool intra4x4, int64_t entries, hipStream_t s) {
   with_const<1, 0>(intra4x4, [&](auto i4) {
-    hipLaunchKernelGGL(enc_intra<i4() != 0>, dim3(static_cast<unsigned>(entries * a.mbh)), dim3(64), 0, s, a);
+    with_const<1, 0>(a.aq_off != nullptr, [&](auto aq) {
+      hipLaunchKernelGGL((enc_intra<i4() != 0, aq() != 0>), dim3(static_cast<unsigned>(entries * a.mbh)), dim3(64), 0, s, a);
+    });
   });
 }
 
@@ -1866,6 +1986,12 @@ void launch_enc_deblock(const DeblockArgs &a, int64_t entries, hipStream_t s) {
   with_const<1, 0>(a.mv4 != nullptr, [&](auto pt) {
     hipLaunchKernelGGL(enc_deblock<pt() != 0>, dim3(static_cast<unsigned>(entries * a.mbh)), dim3(64), 0, s, a);
   });
+}
+
+// one wave per four macroblocks of a row
+void launch_enc_aq(const AqArgs &a, int64_t frames, hipStream_t s) {
+  if (frames <= 0) return;
+  hipLaunchKernelGGL(enc_aq, dim3(static_cast<unsigned>(frames * a.mbh * ((a.mbw + 3) / 4))), dim3(64), 0, s, a);
 }
 
 void launch_enc_rc(const RcArgs &a, hipStream_t s) {
@@ -1885,8 +2011,12 @@ void launch_enc_write(const WriteArgs &a, bool cabac, bool intra, bool deblock, 
   with_const<1, 0>(intra, [&](auto in) {
     with_const<1, 0>(deblock, [&](auto db) {
       with_const<1, 0>(a.mv4 != nullptr, [&](auto pt) {  // partitions: the level has quadrant vectors
-        if (cabac) hipLaunchKernelGGL((enc_write_cabac<in() != 0, db() != 0, pt() != 0>), dim3(ns), dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((enc_write<in() != 0, db() != 0, pt() != 0>), dim3((ns + 63) / 64), dim3(64), 0, s, a);
+        with_const<1, 0>(a.aq_off != nullptr, [&](auto aq) {  // adaptive quantisation: the call has offsets
+          if (cabac)
+            hipLaunchKernelGGL((enc_write_cabac<in() != 0, db() != 0, pt() != 0, aq() != 0>), dim3(ns), dim3(64), 0, s, a);
+          else
+            hipLaunchKernelGGL((enc_write<in() != 0, db() != 0, pt() != 0, aq() != 0>), dim3((ns + 63) / 64), dim3(64), 0, s, a);
+        });
       });
     });
   });

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "enc_aq.h"
 #include "enc_plan.h"
 #include "enc_ratectl.h"
 #include "mp4.h"
@@ -72,6 +73,12 @@ static_assert(VTS_END_OF(vts_transcode_ext8, frame_first) == 176 && VTS_END_OF(v
               sizeof(vts_transcode_ext8) == 184 && VTS_END_OF(vts_transcode_ext_info7, frame_first) == 136 &&
               VTS_END_OF(vts_transcode_ext_info7, frame_count) == 144 && sizeof(vts_transcode_ext_info7) == 144,
               "vts_transcode_ext8: struct_size >= 176, 184; vts_transcode_ext_info7: >= 136, 144");
+static_assert(VTS_END_OF(vts_transcode_ext9, aq_strength_q8) == 188 && VTS_END_OF(vts_transcode_ext9, aq_max) == 192 &&
+              VTS_END_OF(vts_transcode_ext9, mbqp_out) == 200 && VTS_END_OF(vts_transcode_ext9, mbqp_cap) == 208 &&
+              sizeof(vts_transcode_ext9) == 208 && VTS_END_OF(vts_transcode_ext_info8, mbqp_words) == 152 &&
+              VTS_END_OF(vts_transcode_ext_info8, aq_lo) == 156 && VTS_END_OF(vts_transcode_ext_info8, aq_hi) == 160 &&
+              VTS_END_OF(vts_transcode_ext_info8, aq_mbs) == 168 && sizeof(vts_transcode_ext_info8) == 168,
+              "vts_transcode_ext9: struct_size >= 188, 192, 200, 208; vts_transcode_ext_info8: >= 152, 156, 160, 168");
 static_assert(VTS_END_OF(vts_transcode_ext_info, _pad) == 8 && VTS_END_OF(vts_transcode_ext_info, subpel_mbs) == 16 &&
               VTS_END_OF(vts_transcode_ext_info, qpel_mbs) == 24 && VTS_END_OF(vts_transcode_ext_info2, deblock_mbs) == 32 &&
               VTS_END_OF(vts_transcode_ext_info3, early_skip_mbs) == 40 &&
@@ -102,6 +109,10 @@ struct TranscodeOpts {
   uint32_t *bits_out = nullptr;
   int64_t frame_cap = 0;
   int64_t f0 = 0, n = 0;   // the frames [f0, f0 + n) of the video are transcoded (vts_transcode_ext8; all by default)
+  int aq_strength_q8 = 0, aq_max = 0;  // adaptive quantisation (enc_aq.h); aq_max with its default applied
+  int aq_lo = 1, aq_hi = 51;           // ... a macroblock's QP is clamped to them: the caller's qp_min / qp_max where given
+  uint8_t *mbqp_out = nullptr;
+  int64_t mbqp_cap = 0;
   bool per_frame = false;  // frame_qp or bitrate_kbps: the kernels read a QP per picture and measure its rate
   int rate = 0;         // SearchArgs.rate: mvcost | early_skip << 1
   int sh = 0, R = 0, T = 0, qp = 0, keyint = 0;  // output height, search range, max SAD, residual QP (0: none)
@@ -172,6 +183,17 @@ int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_trans
       return fail(VTS_E_INVALID, "frame_count %lld: 0 .. %lld from frame_first %lld", static_cast<long long>(count),
                   static_cast<long long>(c->n_frames - o.f0), static_cast<long long>(o.f0));
     o.n = count ? count : c->n_frames - o.f0;
+    // vts_transcode_ext9, the same way
+    VTS_EXT_GET(o.aq_strength_q8, vts_transcode_ext9, aq_strength_q8);
+    VTS_EXT_GET(o.aq_max, vts_transcode_ext9, aq_max);
+    VTS_EXT_GET(o.mbqp_out, vts_transcode_ext9, mbqp_out);
+    VTS_EXT_GET(o.mbqp_cap, vts_transcode_ext9, mbqp_cap);
+    if (o.aq_strength_q8 < 0 || o.aq_strength_q8 > full::eaq::kStrengthMaxQ8)
+      return fail(VTS_E_INVALID, "aq_strength_q8 %d: 0 .. %d", o.aq_strength_q8, full::eaq::kStrengthMaxQ8);
+    if (o.aq_max < 0 || o.aq_max > full::eaq::kMaxLimit)
+      return fail(VTS_E_INVALID, "aq_max %d: 0 (default) or 1 .. %d", o.aq_max, full::eaq::kMaxLimit);
+    if (!o.aq_strength_q8 && o.aq_max) return fail(VTS_E_INVALID, "aq_max %d without aq_strength_q8", o.aq_max);
+    if (o.aq_strength_q8 && !o.aq_max) o.aq_max = full::eaq::kMaxDefault;
     if (o.bitrate_kbps < 0 || o.bitrate_kbps > full::erc::kMaxKbps)
       return fail(VTS_E_INVALID, "bitrate_kbps %d: 0 .. %d", o.bitrate_kbps, full::erc::kMaxKbps);
     if (o.qp_min < 0 || o.qp_min > 51) return fail(VTS_E_INVALID, "qp_min %d: 0 (default) or 1 .. 51", o.qp_min);
@@ -179,6 +201,10 @@ int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_trans
     o.per_frame = o.bitrate_kbps != 0 || o.frame_qp != nullptr;
     if (!o.per_frame && o.qp_min) return fail(VTS_E_INVALID, "qp_min %d without bitrate_kbps or frame_qp", o.qp_min);
     if (!o.per_frame && o.qp_max) return fail(VTS_E_INVALID, "qp_max %d without bitrate_kbps or frame_qp", o.qp_max);
+    // a macroblock's QP stays inside the bounds the caller gave; a bound left at 0 is 1 or 51 for it, not the
+    // controller's default: a frame_qp below 10 must not move a macroblock whose offset is 0
+    if (o.qp_min) o.aq_lo = o.qp_min;
+    if (o.qp_max) o.aq_hi = o.qp_max;
     if (o.per_frame) {
       if (!o.qp_min) o.qp_min = full::erc::kQpMinDefault;
       if (!o.qp_max) o.qp_max = full::erc::kQpMaxDefault;
@@ -214,6 +240,9 @@ int read_opts(const vts_ctx *c, const vts_transcode_params *pin, const vts_trans
   if (o.per_frame && o.qp < 1) return fail(VTS_E_INVALID, "%s needs residual coding (qp >= 0)", pf);
   if (o.per_frame && o.T < 0) return fail(VTS_E_INVALID, "%s needs max_mb_sad >= 0 (inter macroblocks)", pf);
   if (o.per_frame && !o.mvcost) return fail(VTS_E_INVALID, "%s needs mvcost = 1", pf);
+  if (o.aq_strength_q8 && o.qp < 1) return fail(VTS_E_INVALID, "aq_strength_q8 needs residual coding (qp >= 0)");
+  if (o.aq_strength_q8 && o.T < 0) return fail(VTS_E_INVALID, "aq_strength_q8 needs max_mb_sad >= 0 (inter macroblocks)");
+  if (o.aq_strength_q8 && !o.mvcost) return fail(VTS_E_INVALID, "aq_strength_q8 needs mvcost = 1");
   if (o.intra4x4 && o.qp < 1) return fail(VTS_E_INVALID, "intra4x4 = 1 needs residual coding (qp >= 0)");
   if (o.intra4x4 && !o.intra) return fail(VTS_E_INVALID, "intra4x4 = 1 needs intra = 1");
   if (o.intra && o.qp < 1) return fail(VTS_E_INVALID, "intra = 1 needs residual coding (qp >= 0)");
@@ -331,6 +360,7 @@ struct Transcoder {
     uint32_t *est_f;             // per_frame: [frame] the rate measure
     int64_t *rc_spent;           // bitrate_kbps: [GOP] the measure of its pictures so far
     int32_t *rc_len;             // bitrate_kbps: [GOP] its pictures
+    int8_t *aq_off;              // aq_strength_q8: [frame][mb] the macroblocks' QP offsets
   } d{};
   Events ev;  // destroyed before `bufs` drains and frees
   int64_t next_search = 1;
@@ -394,7 +424,7 @@ int Transcoder::check(vts_transcode_ext_info *xinfo) {
   mbw = S().cw / 16;
   mbh = S().ch / 16;
   nmb = mbw * mbh;
-  cap = slice_slot_bytes(mbw, opt.cabac != 0);
+  cap = slice_slot_bytes(mbw, opt.cabac != 0, opt.aq_strength_q8 != 0);
   // the command words of every macroblock, [frame][my][mx]: reported always, copied out when asked
   cmd_words = n * nmb;
   VTS_XINFO_PUT(vts_transcode_ext_info3, cmd_words, cmd_words);
@@ -412,6 +442,11 @@ int Transcoder::check(vts_transcode_ext_info *xinfo) {
   if (opt.mv_out && opt.mv_cap < mv_words)
     return fail(VTS_E_CAPACITY, "mv_cap %lld < %lld vector words", static_cast<long long>(opt.mv_cap),
                 static_cast<long long>(mv_words));
+  // the QP of every macroblock, the same way
+  VTS_XINFO_PUT(vts_transcode_ext_info8, mbqp_words, cmd_words);
+  if (opt.mbqp_out && opt.mbqp_cap < cmd_words)
+    return fail(VTS_E_CAPACITY, "mbqp_cap %lld < %lld macroblocks", static_cast<long long>(opt.mbqp_cap),
+                static_cast<long long>(cmd_words));
   // the QP and the rate measure of every frame, the same way
   VTS_XINFO_PUT(vts_transcode_ext_info6, frame_words, n);
   if (opt.qp_out && opt.frame_cap < n)
@@ -460,6 +495,7 @@ int Transcoder::alloc() {
   VTS_TRY(bufs.get(&d.err, 1));
   VTS_TRY(bufs.get(&d.jobs, static_cast<size_t>(max_chunk * nmb)));
   VTS_TRY(bufs.get(&d.njobs, 1));
+  if (opt.aq_strength_q8) VTS_TRY(bufs.get(&d.aq_off, static_cast<size_t>(n * nmb)));
   s1 = c->s_dec;
   s2 = c->s_score;
   bufs.streams = {s1, s2};
@@ -540,6 +576,9 @@ SearchArgs Transcoder::search_args(int64_t j) const {
     a.est_f = d.est_f;
     a.mv_lambda16 = opt.mv_lambda16;
     a.pcm_bits = opt.intra ? 0 : kPcmMbBits;
+    a.aq_off = d.aq_off;
+    a.aq_lo = opt.aq_lo;
+    a.aq_hi = opt.aq_hi;
   }
   return a;
 }
@@ -563,6 +602,9 @@ IntraArgs Transcoder::intra_args(int64_t j) const {
   a.i4 = l.i4;
   a.qp_f = d.qp_f;
   a.est_f = d.est_f;
+  a.aq_off = d.aq_off;
+  a.aq_lo = opt.aq_lo;
+  a.aq_hi = opt.aq_hi;
   return a;
 }
 
@@ -585,6 +627,9 @@ DeblockArgs Transcoder::deblock_args(int64_t j) const {
   a.count = d.stats + kStDeblocked;
   a.mv4 = l.mv4;
   a.qp_f = d.qp_f;
+  a.aq_off = d.aq_off;
+  a.aq_lo = opt.aq_lo;
+  a.aq_hi = opt.aq_hi;
   return a;
 }
 
@@ -626,6 +671,9 @@ WriteArgs Transcoder::write_args(int64_t ck) const {
   a.i4 = l.i4;
   a.mv4 = l.mv4;
   a.qp_f = d.qp_f;
+  a.aq_off = d.aq_off;
+  a.aq_lo = opt.aq_lo;
+  a.aq_hi = opt.aq_hi;
   return a;
 }
 
@@ -732,6 +780,8 @@ int Transcoder::write_chunk(int64_t ck) {
 // then chunk by chunk; both streams are drained when it returns VTS_OK
 int Transcoder::encode() {
   HIP_TRY(hipEventRecord(ev.search_begin, s1));
+  if (opt.aq_strength_q8)  // the offsets of every frame's macroblocks, ahead of every level in stream order
+    launch_enc_aq(AqArgs{S().d, S().stride, S().cw, S().ch, mbw, mbh, opt.aq_strength_q8, opt.aq_max, d.aq_off}, n, s1);
   VTS_TRY(enqueue_level(0));
   VTS_TRY(enqueue_searches(opt.qp >= 1 ? kRing : plan.maxlen));
   HIP_TRY(hipGetLastError());
@@ -827,6 +877,28 @@ int Transcoder::finish(vts_transcode_info *info, vts_transcode_ext_info *xinfo) 
   VTS_XINFO_PUT(vts_transcode_ext_info6, qp_lo, n ? *std::min_element(qps.begin(), qps.end()) : 0);
   VTS_XINFO_PUT(vts_transcode_ext_info6, qp_hi, n ? *std::max_element(qps.begin(), qps.end()) : 0);
   VTS_XINFO_PUT(vts_transcode_ext_info6, est_bits, est_bits);
+  // the QP of every macroblock: its picture's, moved by its offset (aq off and no mbqp_out: the facts stay 0)
+  if (opt.aq_strength_q8 || opt.mbqp_out) {
+    std::vector<int8_t> off(static_cast<size_t>(cmd_words), 0);
+    if (opt.aq_strength_q8) HIP_TRY(hipMemcpy(off.data(), d.aq_off, off.size(), hipMemcpyDeviceToHost));
+    int lo = 0, hi = 0;
+    int64_t moved = 0;
+    for (int64_t i = 0; i < cmd_words; ++i) {
+      lo = std::min<int>(lo, off[i]);
+      hi = std::max<int>(hi, off[i]);
+      moved += off[i] != 0;
+      if (opt.mbqp_out)
+        opt.mbqp_out[i] = static_cast<uint8_t>(
+            opt.aq_strength_q8 ? full::eaq::qp_mb(qps[i / nmb], off[i], opt.aq_lo, opt.aq_hi) : qps[i / nmb]);
+    }
+    VTS_XINFO_PUT(vts_transcode_ext_info8, aq_lo, lo);
+    VTS_XINFO_PUT(vts_transcode_ext_info8, aq_hi, hi);
+    VTS_XINFO_PUT(vts_transcode_ext_info8, aq_mbs, moved);
+  } else {
+    VTS_XINFO_PUT(vts_transcode_ext_info8, aq_lo, 0);
+    VTS_XINFO_PUT(vts_transcode_ext_info8, aq_hi, 0);
+    VTS_XINFO_PUT(vts_transcode_ext_info8, aq_mbs, int64_t(0));
+  }
 
   const auto t0 = clk::now();
   std::vector<uint8_t> sps, pps;

@@ -217,6 +217,19 @@ class TranscodeExtInfo7(C.Structure):
     _fields_ = [("base", TranscodeExtInfo6), ("frame_first", C.c_int64), ("frame_count", C.c_int64)]
 
 
+class TranscodeExt9(C.Structure):
+    """vts_transcode_ext9 (adaptive quantisation): begins with TranscodeExt8; passed by
+    pointer cast with the innermost struct_size = sizeof(TranscodeExt9)."""
+    _fields_ = [("base", TranscodeExt8), ("aq_strength_q8", C.c_int32), ("aq_max", C.c_int32),
+                ("mbqp_out", C.POINTER(C.c_uint8)), ("mbqp_cap", C.c_int64)]
+
+
+class TranscodeExtInfo8(C.Structure):
+    """vts_transcode_ext_info8: begins with TranscodeExtInfo7; as TranscodeExt9."""
+    _fields_ = [("base", TranscodeExtInfo7), ("mbqp_words", C.c_int64), ("aq_lo", C.c_int32),
+                ("aq_hi", C.c_int32), ("aq_mbs", C.c_int64)]
+
+
 class ManifestArgs(C.Structure):
     _fields_ = [("video_id", C.c_char_p), ("segment_dir", C.c_char_p),
                 ("created_at", C.c_char_p), ("duration", C.c_double),

@@ -270,7 +270,8 @@ class VideoScorer:
                   partitions: bool = False, want_vectors: bool = False,
                   bitrate_kbps: int = 0, qp_range: tuple[int, int] = (0, 0),
                   frame_qp=None, want_rate: bool = False,
-                  frames: tuple[int, int] | None = None) -> dict:
+                  frames: tuple[int, int] | None = None,
+                  aq_strength: float = 0.0, aq_max: int = 0) -> dict:
         """360p upload transcode of this video into `out_path`
         (vts_transcode_ex): decode + score + area downscale +
         device H.264 encode with a quantised residual at `qp` (<= 0: none, the
@@ -334,6 +335,16 @@ class VideoScorer:
         `frame_first` and `frame_count`.  The whole video is still decoded and
         scored; only the range is kept for the encoder (DESIGN.md §11
         "Segment re-encode").  None: the whole video, every byte as before.
+        `aq_strength` > 0 (up to 3.0; 1.0 is x264's default strength): adaptive
+        quantisation, a QP per macroblock from the variance of its source
+        samples, flat macroblocks below the picture's QP and busy ones above
+        by at most `aq_max` (0: 8; 1..10), inside `qp_range` (1..51 without
+        one), sent as mb_qp_delta (DESIGN.md §11 "Adaptive quantisation"); it
+        rides on `qp`, `frame_qp` or the rate controller's QP; needs `mvcost`
+        and `qp` > 0; 0, every byte is as before.  The result then holds
+        `mb_qp` (uint8 array (n_frames, mbh, mbw), the QP of each macroblock),
+        `aq_lo` / `aq_hi` (the lowest and highest offset used) and `aq_mbs`
+        (macroblocks with a non-zero offset).
         Returns the facts (with `intra`, `subpel`, `deblock`, `mvcost`
         or `early_skip` also the encoder's `recon_hash`) and per-stage
         milliseconds; with one of the last four keywords also
@@ -361,33 +372,40 @@ class VideoScorer:
             if f1 == f0 and 0 <= f0 < nf:   # a count of 0 means "through the last frame" to the library
                 raise _lib.VtsegError(_lib.VTS_E_INVALID, f"frame_count 0: frames=({f0}, {f1}) is empty")
             nf = max(f1 - f0, 0)
-        ext_t = _lib.TranscodeExt8 if frames is not None else _lib.TranscodeExt7 if rc else (
+        aq = bool(aq_strength or aq_max)
+        aq_q8 = int(round(float(aq_strength) * 256))
+        if aq_strength > 0 and aq_q8 == 0:
+            aq_q8 = 1   # the smallest strength the library knows, not "off"
+        ext_t = _lib.TranscodeExt9 if aq else _lib.TranscodeExt8 if frames is not None else _lib.TranscodeExt7 if rc else (
             _lib.TranscodeExt6 if pt else (_lib.TranscodeExt5 if i4 else _lib.TranscodeExt4))
-        info_t = _lib.TranscodeExtInfo7 if frames is not None else _lib.TranscodeExtInfo6 if rc else (
+        info_t = _lib.TranscodeExtInfo8 if aq else _lib.TranscodeExtInfo7 if frames is not None else _lib.TranscodeExtInfo6 if rc else (
             _lib.TranscodeExtInfo5 if pt else (_lib.TranscodeExtInfo4 if i4 else _lib.TranscodeExtInfo3))
-        ext8 = _lib.TranscodeExt8(_lib.TranscodeExt7(_lib.TranscodeExt6(_lib.TranscodeExt5(_lib.TranscodeExt4(
+        ext9 = _lib.TranscodeExt9(_lib.TranscodeExt8(_lib.TranscodeExt7(_lib.TranscodeExt6(_lib.TranscodeExt5(_lib.TranscodeExt4(
             _lib.TranscodeExt3(
                 _lib.TranscodeExt2(_lib.TranscodeExt(C.sizeof(ext_t), subpel),
                                    1 if deblock else 0, int(deblock_offsets[0]), int(deblock_offsets[1])),
                 1 if mvcost else 0, int(mv_lambda16), 1 if early_skip else 0), 1 if cabac else 0),
             1 if intra4x4 else 0), 1 if partitions else 0),
-            int(bitrate_kbps), int(qp_range[0]), int(qp_range[1])))
+            int(bitrate_kbps), int(qp_range[0]), int(qp_range[1]))))
+        ext8 = ext9.base
+        ext9.aq_strength_q8, ext9.aq_max = aq_q8, int(aq_max)
         if frames is not None:
             ext8.frame_first, ext8.frame_count = f0, f1 - f0
         ext7 = ext8.base
         ext6 = ext7.base
         ext5 = ext6.base
         ext = ext5.base.base
-        xinfo7 = _lib.TranscodeExtInfo7(_lib.TranscodeExtInfo6(_lib.TranscodeExtInfo5(_lib.TranscodeExtInfo4(
-            _lib.TranscodeExtInfo3(_lib.TranscodeExtInfo2(_lib.TranscodeExtInfo(C.sizeof(info_t))))))))
+        xinfo8 = _lib.TranscodeExtInfo8(_lib.TranscodeExtInfo7(_lib.TranscodeExtInfo6(_lib.TranscodeExtInfo5(
+            _lib.TranscodeExtInfo4(_lib.TranscodeExtInfo3(_lib.TranscodeExtInfo2(_lib.TranscodeExtInfo(C.sizeof(info_t)))))))))
+        xinfo7 = xinfo8.base
         xinfo6 = xinfo7.base
         xinfo5 = xinfo6.base
         xinfo4 = xinfo5.base
         xinfo3 = xinfo4.base
         xinfo2 = xinfo3.base
         xinfo = xinfo2.base
-        commands = modes = vectors = None
-        if want_commands or want_intra4_modes or want_vectors:
+        commands = modes = vectors = mb_qp = None
+        if want_commands or want_intra4_modes or want_vectors or aq:
             # the coded macroblock grid of the output: width as ffmpeg's scale=-2, both 16-aligned
             w, h = int(self.info.width), int(self.info.height)
             sw = (height * w + h) // (2 * h) * 2
@@ -404,6 +422,10 @@ class VideoScorer:
             vectors = np.zeros((nf, mbh, mbw, 4), np.uint32)
             ext6.mv_out = vectors.ctypes.data_as(C.POINTER(C.c_uint32))
             ext6.mv_cap = vectors.size
+        if aq:
+            mb_qp = np.zeros((nf, mbh, mbw), np.uint8)
+            ext9.mbqp_out = mb_qp.ctypes.data_as(C.POINTER(C.c_uint8))
+            ext9.mbqp_cap = mb_qp.size
         qps_in = qps = bits = None
         if rc:
             if frame_qp is not None:
@@ -421,10 +443,14 @@ class VideoScorer:
             ext7.bits_out = bits.ctypes.data_as(C.POINTER(C.c_uint32))
             ext7.frame_cap = nf
         _lib.check(self._lib.vts_transcode_ex(self._ctx, str(out_path).encode(), C.byref(prm),
-                                              C.cast(C.pointer(ext8), C.POINTER(_lib.TranscodeExt)),
+                                              C.cast(C.pointer(ext9), C.POINTER(_lib.TranscodeExt)),
                                               C.byref(info),
-                                              C.cast(C.pointer(xinfo7), C.POINTER(_lib.TranscodeExtInfo))))
+                                              C.cast(C.pointer(xinfo8), C.POINTER(_lib.TranscodeExtInfo))))
         extra = {}
+        if aq:
+            if xinfo8.mbqp_words != mb_qp.size:
+                raise RuntimeError(f"{xinfo8.mbqp_words} macroblock QPs reported, expected {mb_qp.size}")
+            extra.update(mb_qp=mb_qp, aq_lo=xinfo8.aq_lo, aq_hi=xinfo8.aq_hi, aq_mbs=xinfo8.aq_mbs)
         if frames is not None:
             extra.update(frame_first=int(xinfo7.frame_first), frame_count=int(xinfo7.frame_count))
         if rc:

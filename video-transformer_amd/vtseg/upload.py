@@ -155,7 +155,8 @@ def compress_video_for_upload(video_path: Path, *, logger: logging.Logger | None
                               deblock_offsets: tuple[int, int] = (0, 0), mvcost: bool = False,
                               early_skip: bool = False, cabac: bool = False,
                               intra4x4: bool = False, partitions: bool = False,
-                              target_size_mb: float | None = None) -> Path:
+                              target_size_mb: float | None = None, aq_strength: float = 0.0,
+                              aq_max: int = 0) -> Path:
     """Same decisions and return values as the reference method: the input
     path when it is <= 30 MB, an existing non-empty compressed_<name> as is,
     otherwise the new compressed file, or the input path when compression
@@ -172,7 +173,12 @@ def compress_video_for_upload(video_path: Path, *, logger: logging.Logger | None
     `mvcost`, which it needs).  No hit tolerance is promised: near the
     fixed-QP size the file lands within about a tenth of the target, far
     under it above the target (DESIGN.md §11 "Rate control"); target and
-    achieved size are logged.  None: the fixed-QP call it was."""
+    achieved size are logged.  None: the fixed-QP call it was.  `aq_strength`
+    > 0: its adaptive quantisation, a QP per macroblock from the variance of
+    the source, offsets up to `aq_max` (0: 8); 0: every byte as before.  It
+    needs `mvcost`, so, as `target_size_mb` does, it turns `mvcost` on for a
+    caller who left it off (logged): the motion decisions are then the
+    rate-aware ones, not only the quantiser differs."""
     log = logger or logging.getLogger(__name__)
     video_path = Path(video_path)
     file_size_mb = video_path.stat().st_size / (1024 * 1024)
@@ -194,6 +200,11 @@ def compress_video_for_upload(video_path: Path, *, logger: logging.Logger | None
                 kbps = target_bitrate_kbps(video_path, target_size_mb, float(v.info.duration))
                 log.info(f"target {target_size_mb:.2f}MB: video at {kbps} kbps")
                 rate = dict(bitrate_kbps=kbps)
+                mvcost = True
+            if aq_strength:
+                rate.update(aq_strength=aq_strength, aq_max=aq_max)
+                if not mvcost:
+                    log.info("aq_strength needs mvcost: turned on")
                 mvcost = True
             facts = v.transcode(video_only, intra=intra, subpel=subpel, deblock=deblock,
                                 deblock_offsets=deblock_offsets, mvcost=mvcost, early_skip=early_skip,
