@@ -262,8 +262,12 @@ typedef struct vts_params {
                               launches, chunk j+1 overlapping reconstruction of
                               chunk j; <= 1 (default) = one parse launch */
   int32_t level_block;     /* GOP levels decoded per reconstruct launch (k = 4,
-                              fused, GOPs that are plain P chains): 0 (auto)
-                              and 1 = one launch per level (fastest measured);
+                              fused, GOPs that are plain P chains): 0 (auto) =
+                              P levels two per launch, the first of a pair
+                              handed on in LDS and not stored (DESIGN.md §4.7;
+                              no kept frames, no transcode, default launch
+                              grouping, pictures up to 1360 wide), else one
+                              launch per level; 1 = one launch per level;
                               n >= 2 = up to n levels per launch with the
                               levels between in LDS */
   int32_t keep_frames;     /* level-blocked launches keep only each block's
@@ -321,7 +325,11 @@ int vts_frame_pts(const vts_ctx *ctx, int64_t *pts, int64_t cap, int64_t *n_out)
 int vts_boundary_frames(vts_ctx *ctx, const double *times, int64_t n,
                         int64_t *frame_idx);
 /* Copy frame i's decoded NV12 (display size, pitch = width) of the most
- * recent window to host; only frames still resident in the ring. */
+ * recent window to host; only frames still resident in the ring.  A session
+ * on the paired schedule (level_block 0) does not store the first frame of
+ * each pair: asking for one decodes the video once more with one launch per
+ * level, which stores every frame, and the session stays on that schedule
+ * for the rest of its life (same results, one extra run). */
 int vts_get_frame_nv12(vts_ctx *ctx, int64_t frame, uint8_t *out,
                        int64_t out_bytes);
 /* RGB thumbnail (w x h x 3, see vts_score_desc) of frame i of the last run. */
@@ -361,7 +369,10 @@ int vts_open_timings(const vts_ctx *ctx, double *ms, int32_t cap);
  * (0: every window one parse launch), 14 the intra kernel the general
  * decoder's level launches run (2 h264_intra_v2, lane-parallel; 1
  * h264_intra_full, by block: VTS_INTRA=1, or pictures whose level table does
- * not fit the former's LDS; 0: subset decoder); < 0 on error.  Fields are
+ * not fit the former's LDS; 0: subset decoder), 15 / 16 paired launches
+ * (two P levels each, the default schedule where it applies, see
+ * vts_params.level_block) / chains over them per run (0 once the session
+ * runs one launch per level); < 0 on error.  Fields are
  * only ever appended: a new index is no ABI break, and a library that does
  * not know an index answers VTS_E_INVALID. */
 int64_t vts_schedule_info(const vts_ctx *ctx, int32_t what);  /* 8: general decoder in use (1/0) */

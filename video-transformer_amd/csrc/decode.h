@@ -106,6 +106,11 @@ int recon_launch(const ReconArgs &a, int n_frames, hipStream_t s);
 int tb_launch(const TbArgs &a, int n_chains, hipStream_t s);
 int tb_lds_bytes(int mb_width, int mb_height, int L);
 int tb_max_tasks(int mb_width, int mb_height, int L);
+// two P levels per launch (h264_recon_score_pair): chains of L = 2 entries,
+// one workgroup per (chain, macroblock row); the picture shapes it takes
+int pair_launch(const TbArgs &a, int n_chains, hipStream_t s);
+bool pair_shape_ok(int mb_width, int mb_height);
+int pair_lds_bytes(int mb_width, int mb_height);
 // hist[0 .. 256 n) = 0, sad[0 .. n) = 0 (hist 16-byte aligned)
 int clear_accum_launch(uint32_t *hist, uint64_t *sad, int64_t n_frames, hipStream_t s);
 int score_launch(const vts_score_desc *d, hipStream_t stream);

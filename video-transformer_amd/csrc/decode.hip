@@ -1389,6 +1389,184 @@ h264_recon_score_tb(TbArgs ta) {
   if (errs | range) atomicOr(a.err, errs | (range ? static_cast<uint32_t>(DEC_W_LEVEL_RANGE) : 0u));
 }
 
+// ------------------------------------------ two P levels per launch (k = 4)
+// h264_recon_score_pair: one workgroup per (chain of two GOP levels,
+// macroblock row "band").  Level A, the chain's first entry, is decoded from
+// the HBM reference straight into registers, exactly as h264_recon_score<4>
+// does it (a lane task = (macroblock, 4 + 2-row group), every aligned row load
+// issued before any is used), over the band +- one halo group, and written to
+// LDS at its picture position (luma rows, then chroma rows, full picture
+// width).  After one barrier the band lanes decode level B from those LDS rows
+// (tb_group_lds: I_PCM from the stream, half-pel chroma, edge clamping, the
+// range flag), store it and score it.  Band tasks take the low lanes, so a
+// lane keeps its (group, macroblock) and level A's thumbnail word for level
+// B's SAD.  Level A's frame is not stored (unless ta.keep, or the chain has one
+// level: a GOP's odd tail); HBM sees one reference read (the halo rows twice,
+// unless the neighbouring band's read hits L2), one frame write and the
+// scoring outputs per two frames.  Two LDS histograms and SAD partials, flushed
+// once at the end.
+constexpr int kPairThreads = 512;
+constexpr int kPairGroups = 4 + 2 * kTbHalo;  // level A's groups per band
+
+// store + score one band task's rows; returns its packed thumbnail luma
+__device__ __forceinline__ uint32_t pair_score(const FusedArgs &fa, const uint4 (&rows)[6], int slot, int g, int m,
+                                               int H, bool store, uint32_t *hist) {
+  const ReconArgs &a = fa.r;
+  if (store) {
+    uint8_t *dst = a.surf + static_cast<int64_t>(slot) * a.frame_stride;
+    uint8_t *dst_uv = dst + static_cast<int64_t>(a.pitch) * H;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) st_row(dst + static_cast<int64_t>(4 * g + r) * a.pitch + m * 16, rows[r]);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) st_row(dst_uv + static_cast<int64_t>(2 * g + r) * a.pitch + m * 16, rows[4 + r]);
+  }
+  uint32_t ys[4] = {0, 0, 0, 0}, us[4] = {0, 0, 0, 0}, vs[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int r = 0; r < 4; ++r) add_luma16<4>(rows[r], ys);
+#pragma unroll
+  for (int r = 0; r < 2; ++r) add_chroma16<4>(rows[4 + r], us, vs);
+  uint32_t rgb24[4], packed = 0;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const uint32_t y = (ys[p] + 8) / 16, u = (us[p] + 2) / 4, v = (vs[p] + 2) / 4;
+    rgb24[p] = bt709_rgb24(y, u, v);
+    packed |= y << (8 * p);
+    atomicAdd(&hist[y], 1u);
+  }
+  const int64_t npx = static_cast<int64_t>(fa.w) * fa.h;
+  const int64_t tpx = static_cast<int64_t>(g) * fa.w + m * 4;
+  store_rgb<4>(fa.rgb + ((fa.frame0 + slot) * npx + tpx) * 3, rgb24);
+  *reinterpret_cast<uint32_t *>(fa.thumb + slot * npx + tpx) = packed;
+  return packed;
+}
+
+__global__ void __launch_bounds__(kPairThreads) __attribute__((amdgpu_waves_per_eu(4)))
+h264_recon_score_pair(TbArgs ta) {
+  extern __shared__ uint4 tb_dyn[];
+  __shared__ uint32_t lds_hist[2][256];
+  __shared__ uint32_t red[2][kPairThreads / 64];
+  const FusedArgs &fa = ta.f;
+  const ReconArgs &a = fa.r;
+  const int mbw = a.mb_width, mbh = a.mb_height, nmb = mbw * mbh;
+  const int W = mbw * 16, H = mbh * 16, NG = 4 * mbh;
+  const int bid = xcd_block(blockIdx.x, gridDim.x);
+  const int chain = bid / mbh, band = bid - chain * mbh;
+  const int4 fA = ta.chains[static_cast<int64_t>(chain) * 2], fB = ta.chains[static_cast<int64_t>(chain) * 2 + 1];
+  const bool two = fB.x >= 0;
+  // level A's groups [g_lo, g_hi): the band, and one halo group each side when
+  // a level B reads them; they are the LDS rows
+  const int h = two ? kTbHalo : 0;
+  const int g_lo = max(0, 4 * band - h), g_hi = min(NG, 4 * band + 4 + h);
+  const int ly0 = 4 * g_lo, cy0 = 2 * g_lo, nl = 4 * (g_hi - g_lo);
+  uint8_t *lds = reinterpret_cast<uint8_t *>(tb_dyn);
+  const int nb = 4 * mbw;  // band tasks: lanes [0, nb), the same at both levels
+  const int64_t npx = static_cast<int64_t>(fa.w) * fa.h;
+  const int t = static_cast<int>(threadIdx.x);
+  const bool own = t < nb;
+  // this lane's level-A task: band groups first, then the top and the bottom
+  // halo group
+  int g = -1, m = 0;
+  {
+    const int ntask = (g_hi - g_lo) * mbw, top = (4 * band - g_lo) * mbw;
+    if (own) {
+      g = 4 * band + t / mbw;
+      m = t - (t / mbw) * mbw;
+    } else if (t < ntask) {
+      const int u = t - nb;
+      g = u < top ? g_lo : 4 * band + 4 + (u - top) / mbw;
+      m = u - (u / mbw) * mbw;
+    }
+  }
+  const int mby = g >> 2, q = g & 3;
+  // both levels' commands and the predecessor's thumbnail word are in flight
+  // across the histogram-clearing barrier
+  uint64_t cA = 0, cB = 0;
+  uint32_t prevw = 0;
+  if (g >= 0) {
+    const int64_t mbi = static_cast<int64_t>(mby) * mbw + m;
+    cA = a.cmd[static_cast<int64_t>(fA.x) * nmb + mbi];
+    if (own) {
+      if (two) cB = a.cmd[static_cast<int64_t>(fB.x) * nmb + mbi];
+      if (fA.z >= 0)
+        prevw = *reinterpret_cast<const uint32_t *>(fa.thumb + fA.z * npx + static_cast<int64_t>(g) * fa.w + m * 4);
+    }
+  }
+  (&lds_hist[0][0])[t] = 0;  // kPairThreads == 2 x 256 bins
+  __syncthreads();
+  uint32_t errs = 0, range = 0, sadA = 0, sadB = 0, packedA = 0;
+  if (g >= 0) {
+    const FrameRefs F = frame_refs(a, fA.y);
+    const uint64_t c = current_cmd(cA, a.epoch);
+    uint4 rows[6];
+    if (fast_cmd(F, c)) {
+      const bool pcm = (c >> 62) == 1;
+      const uint8_t *pcmb = F.es + static_cast<int64_t>(c & 0xffffffffffffull);
+      const int mvx = static_cast<int16_t>(c & 0xffff), mvy = static_cast<int16_t>((c >> 16) & 0xffff);
+      uint4 lo[6], hi[6];
+      int shf[6];
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+        issue_row(F, pcmb, pcm, i >= 4, i < 4 ? 4 * q + i : 2 * q + (i - 4), m, mby, mvx, mvy, lo[i], hi[i], shf[i]);
+      uint32_t zero = 0;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) rows[i] = finish_row(i >= 4, pcm, lo[i], hi[i], shf[i], zero);
+      if (pcm && zero) errs |= pcm_rows_epb(pcmb, q, 4, 2);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) rows[r] = fetch_row(F, c, q * 4 + r, m, mby, errs);
+#pragma unroll
+      for (int r = 0; r < 2; ++r) rows[4 + r] = fetch_row(F, c, 16 + q * 2 + r, m, mby, errs);
+    }
+    if (two) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) *reinterpret_cast<uint4 *>(lds + (4 * g + r - ly0) * W + m * 16) = rows[r];
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+        *reinterpret_cast<uint4 *>(lds + nl * W + (2 * g + r - cy0) * W + m * 16) = rows[4 + r];
+    }
+    if (own) {
+      packedA = pair_score(fa, rows, fA.x, g, m, H, ta.keep || !two, lds_hist[0]);
+      if (fA.z >= 0) sadA = sad_u8(packedA, prevw, 0u);
+    }
+  }
+  __syncthreads();  // level A's rows are in LDS
+  if (two && own) {
+    uint4 rows[6];
+    tb_group_lds(lds, ly0, cy0, nl, W, H, 4 * g_lo, 4 * g_hi, 2 * g_lo, 2 * g_hi, a.es, current_cmd(cB, a.epoch), m,
+                 g, fB.y >= 0, rows, errs, range);
+    const uint32_t packedB = pair_score(fa, rows, fB.x, g, m, H, true, lds_hist[1]);
+    if (fB.z >= 0) sadB = sad_u8(packedB, packedA, 0u);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    sadA += __shfl_xor(sadA, off, 64);
+    sadB += __shfl_xor(sadB, off, 64);
+  }
+  if ((t & 63) == 0) {
+    red[0][t >> 6] = sadA;
+    red[1][t >> 6] = sadB;
+  }
+  __syncthreads();  // SAD shares and both histograms are complete
+  if (t < 2) {
+    const int4 fr = t ? fB : fA;
+    if (fr.x >= 0 && fr.z >= 0) {
+      uint64_t s = 0;
+#pragma unroll
+      for (int i = 0; i < kPairThreads / 64; ++i) s += red[t][i];
+      atomicAdd(reinterpret_cast<unsigned long long *>(fa.sad + fa.frame0 + fr.x), static_cast<unsigned long long>(s));
+    }
+  }
+  if (t < 256) {  // two bins per 64-bit atomic, as h264_recon_score does it
+    const int lv = t >> 7, b = t & 127;
+    const int4 fr = lv ? fB : fA;
+    const uint64_t lo = lds_hist[lv][2 * b], hi = lds_hist[lv][2 * b + 1];
+    if (fr.x >= 0 && (lo | hi))
+      atomicAdd(reinterpret_cast<unsigned long long *>(fa.hist + (fa.frame0 + fr.x) * 256) + b,
+                static_cast<unsigned long long>(lo | (hi << 32)));
+  }
+  if (errs | range) atomicOr(a.err, errs | (range ? static_cast<uint32_t>(DEC_W_LEVEL_RANGE) : 0u));
+}
+
 }  // namespace
 
 int clear_accum_launch(uint32_t *hist, uint64_t *sad, int64_t n_frames, hipStream_t s) {
@@ -1491,6 +1669,28 @@ int tb_launch(const TbArgs &a, int n_chains, hipStream_t s) {
     hipLaunchKernelGGL(h264_recon_score_tb<2>, grid, block, static_cast<unsigned>(lds), s, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(VTS_E_HIP, "h264_recon_score_tb launch: %s", hipGetErrorString(e));
+  return VTS_OK;
+}
+
+bool pair_shape_ok(int mb_width, int mb_height) {
+  // level A's (4 + 2) x mb_width tasks, one per lane; its rows in LDS (at most
+  // 48 KB at this width: three workgroups per CU)
+  return mb_width > 0 && mb_height > 0 && kPairGroups * mb_width <= kPairThreads;
+}
+
+int pair_lds_bytes(int mb_width, int mb_height) {
+  return std::min(4 * mb_height, kPairGroups) * 6 * mb_width * 16 + 32;
+}
+
+int pair_launch(const TbArgs &a, int n_chains, hipStream_t s) {
+  if (n_chains <= 0) return VTS_OK;
+  const int mbw = a.f.r.mb_width, mbh = a.f.r.mb_height;
+  if (!pair_shape_ok(mbw, mbh) || a.L != 2)
+    return fail(VTS_E_INVALID, "h264_recon_score_pair: %dx%d macroblocks, L=%d out of range", mbw, mbh, a.L);
+  const dim3 grid(static_cast<unsigned>(n_chains) * mbh), block(kPairThreads);
+  hipLaunchKernelGGL(h264_recon_score_pair, grid, block, static_cast<unsigned>(pair_lds_bytes(mbw, mbh)), s, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(VTS_E_HIP, "h264_recon_score_pair launch: %s", hipGetErrorString(e));
   return VTS_OK;
 }
 

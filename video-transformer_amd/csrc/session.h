@@ -41,6 +41,14 @@ struct Window {
   bool tb = false;
   std::vector<int64_t> tb_off;
   std::vector<int32_t> tb_cnt, tb_L;
+  // paired schedule (h264_recon_score_pair), the default of eligible
+  // sessions: after a GOP group's level-0 launch its P levels go two per
+  // launch; group g's pair launches are [pr_grp[g], pr_grp[g + 1]), launch i
+  // covers chains [pr_off[i], + pr_cnt[i]) of two entries each in
+  // vts_ctx::pair_chains
+  bool pair = false;
+  std::vector<int64_t> pr_off;
+  std::vector<int32_t> pr_cnt, pr_grp;
   int64_t fs0 = 0, fs1 = 0;        // general decoder: slices [fs0, fs1) of vts_ctx::fslices
   int64_t pn0 = 0;                 // general decoder: the window's slot entries in vts_ctx::pneed
   std::vector<int32_t> plv_end;    // general decoder: parse launch j covers window slices
@@ -129,6 +137,13 @@ struct vts_ctx {
   int4 *d_tb = nullptr;
   bool tb_off = false;              // a launch met motion beyond its halo: per-level from now on
   bool tb_ran_sparse = false;       // the last run kept only chain-last frames
+  std::vector<int4> pair_chains;    // paired launches: [chain][2], as tb_chains
+  std::vector<uint8_t> pair_first;  // per frame: first level of a two-level chain (not stored)
+  int4 *d_pair = nullptr;
+  bool pair_env = true;             // VTS_PAIR=0: per-level launches (A/B runs)
+  bool pair_off = false;            // motion beyond the halo, or a frame was asked for: per-level
+                                    // launches for the rest of the session's life
+  bool pair_ran = false;            // the last run left the pair_first frames unstored
   int64_t ring_frames = 0;
   int n_rings = 1;
   // device

@@ -565,10 +565,12 @@ int switch_to_general(vts_ctx *c) {
     c->d_ws[r] = nullptr;
   }
   f(c->d_tb);
+  f(c->d_pair);
   f(c->d_post);
   f(c->d_slices);
   f(c->d_levels);
   c->d_tb = nullptr;
+  c->d_pair = nullptr;
   c->d_post = nullptr;
   c->d_slices = nullptr;
   c->d_levels = nullptr;
@@ -580,6 +582,7 @@ int switch_to_general(vts_ctx *c) {
   c->slices.clear();
   c->post_slots.clear();
   c->tb_chains.clear();
+  c->pair_chains.clear();
   VTS_TRY(build_general(c, es.data(), c->es_off, c->sample_size, c->nal_length_size, c->sps_nal, c->pps_nal));
   return alloc_general(c);
 }
@@ -589,6 +592,7 @@ int build(vts_ctx *c, const Mp4Info &mp4, const uint8_t *mem, int64_t mem_size, 
   if (const char *s = std::getenv("VTS_RECON_GROUPS"))
     c->recon_groups = std::max(1, std::min(vts_ctx::kMaxGroups, std::atoi(s)));
   if (const char *s = std::getenv("VTS_GROUP_PARSE")) c->group_parse = std::atoi(s) > 0;
+  if (const char *s = std::getenv("VTS_PAIR")) c->pair_env = std::atoi(s) != 0;  // 0: per-level launches (A/B)
   if (const char *s = std::getenv("VTS_GENERAL_GROUPS")) c->general_groups = std::max(1, std::min(vts_ctx::kMaxGroups, std::atoi(s)));
   VTS_TRY(fill_video_info(mp4, &c->info));
   const Mp4VideoTrack &t = mp4.video.front();
@@ -904,8 +908,11 @@ int build(vts_ctx *c, const Mp4Info &mp4, const uint8_t *mem, int64_t mem_size, 
   // level-blocked reconstruction (h264_recon_score_tb): levels per launch
   int tb_L_max = 0;
   c->tb_last.assign(static_cast<size_t>(c->n_frames), 0);
+  c->pair_first.assign(static_cast<size_t>(c->n_frames), 0);
   // Opt-in (level_block >= 2): correct, but measured slower than one launch
-  // per level on MI355X, so auto (0) stays per-level.
+  // per level on MI355X.  Auto (0) runs the paired schedule
+  // (h264_recon_score_pair; see pair_ok below) where it
+  // applies and one launch per level elsewhere; 1 is strictly per-level.
   if (c->fused && c->k == 4 && c->params.level_block >= 2 && 4 * c->sps.mb_width <= 512) {
     tb_L_max = std::min(c->params.level_block, 16);
     const int lds_cap = 150 * 1024;
@@ -949,6 +956,18 @@ int build(vts_ctx *c, const Mp4Info &mp4, const uint8_t *mem, int64_t mem_size, 
                                                    : static_cast<int64_t>(gop_start.size());
     }
     const bool grouped = c->fused && c->params.gops_per_launch == 0 && per < static_cast<int64_t>(gop_start.size());
+    // Paired schedule, the default (level_block 0) where it applies: k = 4
+    // fused scoring, no kept frames, one parse chunk, every GOP a plain P chain
+    // (frame x at level l predicted from x - 1 at level l - 1), a picture
+    // narrow enough for the kernel.  Each GOP group's level 0 stays a per-level
+    // launch; its P levels follow in pairs (1,2), (3,4), ..., a GOP's odd tail
+    // as a chain of one level in the same launch.
+    bool pair_ok = c->pair_env && c->fused && c->k == 4 && c->params.level_block == 0 &&
+                   c->params.keep_frames <= 0 && c->params.gops_per_launch == 0 && c->params.parse_chunks <= 1 &&
+                   !c->group_parse && pair_shape_ok(c->sps.mb_width, c->sps.mb_height);
+    for (int64_t x = w.f0; x < w.f1 && pair_ok; ++x)
+      pair_ok = intra[x] ? (level[x] == 0) : (ref[x] == x - 1 && x > w.f0 && level[x] == level[x - 1] + 1);
+    w.pair = pair_ok;
     for (size_t g0 = 0; g0 < gop_start.size(); g0 += static_cast<size_t>(per)) {
       if (grouped) w.grp.push_back(static_cast<int32_t>(w.lvl_off.size()));
       const size_t g1 = std::min(gop_start.size(), g0 + static_cast<size_t>(per));
@@ -972,7 +991,30 @@ int build(vts_ctx *c, const Mp4Info &mp4, const uint8_t *mem, int64_t mem_size, 
         w.lvl_cnt.push_back(static_cast<int32_t>(l.size()));
         c->level_frames.insert(c->level_frames.end(), l.begin(), l.end());
       }
+      if (w.pair) {
+        w.pr_grp.push_back(static_cast<int32_t>(w.pr_off.size()));
+        for (int64_t l1 = 1; l1 <= gmax; l1 += 2) {
+          w.pr_off.push_back(static_cast<int64_t>(c->pair_chains.size()));
+          int32_t cnt = 0;
+          for (int64_t x = a; x < b; ++x) {
+            if (level[x] != l1) continue;
+            // x - 1 is x's reference and display predecessor, one level down
+            c->pair_chains.push_back(make_int4(static_cast<int>(x - w.f0), static_cast<int>(x - 1 - w.f0),
+                                               static_cast<int>(x - 1 - w.f0), 0));
+            if (x + 1 < b && level[x + 1] == l1 + 1) {
+              c->pair_chains.push_back(make_int4(static_cast<int>(x + 1 - w.f0), static_cast<int>(x - w.f0),
+                                                 static_cast<int>(x - w.f0), 0));
+              c->pair_first[static_cast<size_t>(x)] = 1;
+            } else {
+              c->pair_chains.push_back(make_int4(-1, -1, -1, 0));
+            }
+            ++cnt;
+          }
+          w.pr_cnt.push_back(cnt);
+        }
+      }
     }
+    if (w.pair) w.pr_grp.push_back(static_cast<int32_t>(w.pr_off.size()));
     (void)maxl;
     // Slices in launch order (stable: decode order within a launch), so the
     // slices of launches [a, b) are one contiguous range that a parse chunk
@@ -1105,6 +1147,11 @@ int build(vts_ctx *c, const Mp4Info &mp4, const uint8_t *mem, int64_t mem_size, 
     HIP_TRY(vts::dmalloc(&c->d_tb, sizeof(int4) * c->tb_chains.size()));
     HIP_TRY(hipMemcpy(c->d_tb, c->tb_chains.data(), sizeof(int4) * c->tb_chains.size(), hipMemcpyHostToDevice));
   }
+  if (!c->pair_chains.empty()) {
+    HIP_TRY(vts::dmalloc(&c->d_pair, sizeof(int4) * c->pair_chains.size()));
+    HIP_TRY(hipMemcpy(c->d_pair, c->pair_chains.data(), sizeof(int4) * c->pair_chains.size(),
+                      hipMemcpyHostToDevice));
+  }
   HIP_TRY(vts::dmalloc(&c->d_levels, sizeof(int4) * c->level_frames.size()));
   HIP_TRY(hipMemcpy(c->d_levels, c->level_frames.data(), sizeof(int4) * c->level_frames.size(),
                     hipMemcpyHostToDevice));
@@ -1208,6 +1255,7 @@ int vts::submit_all(vts_ctx *c) {
   // transcoder, which downscales every frame from the ring)
   const bool keep = c->params.keep_frames > 0 || c->small.on;
   c->tb_ran_sparse = false;
+  c->pair_ran = false;
   // one window: one stream (nothing to overlap, and HIP event timing of each
   // stage stays on a single queue)
   hipStream_t ss = (c->params.n_streams >= 2 && c->windows.size() > 1) ? c->s_score : c->s_dec;
@@ -1298,12 +1346,16 @@ int vts::submit_all(vts_ctx *c) {
       }
       HIP_TRY(hipEventRecord(LE[2 * (nl - 1) + 1], sd));
     }
-    if (!tb && w.grp.size() > 1) {
-      // Interleaved GOP groups (one parse chunk): group g's level launches on
-      // its own stream, so one group's launch tail overlaps the others' work.
-      const int ng = static_cast<int>(w.grp.size());
+    const bool pair = c->fused && w.pair && !c->pair_off && !keep;
+    if (!tb && (pair || w.grp.size() > 1)) {
+      // Interleaved GOP groups (one parse chunk): group g's launches on its own
+      // stream, so one group's launch tail overlaps the others' work.  Per
+      // level, or on the paired schedule: a group's level 0 one per-level
+      // launch, then its P levels two per launch (the first frame of each pair
+      // is not stored).
+      const int ng = pair ? static_cast<int>(w.pr_grp.size()) - 1 : static_cast<int>(w.grp.size());
       // group g waits for its own parse chunk (or the single one)
-      const bool per_grp = w.chunk_end.size() == w.grp.size();
+      const bool per_grp = !pair && w.chunk_end.size() == w.grp.size();
       HIP_TRY(hipStreamWaitEvent(sd, LE[2 * nl], 0));
       HIP_TRY(hipEventRecord(LE[0], sd));
       // LE[0] follows clear_accum on sd (this window's histograms / SADs are
@@ -1313,15 +1365,26 @@ int vts::submit_all(vts_ctx *c) {
         HIP_TRY(hipStreamWaitEvent(c->s_grp[g - 1], LE[0], 0));
         if (per_grp) HIP_TRY(hipStreamWaitEvent(c->s_grp[g - 1], LE[2 * nl + g], 0));
       }
+      TbArgs ta{};
+      ta.f = fa;
+      ta.L = 2;
       for (size_t i = 0;; ++i) {
         bool any = false;
         for (int g = 0; g < ng; ++g) {
-          const size_t l = static_cast<size_t>(w.grp[g]) + i;
-          const size_t end = g + 1 < ng ? static_cast<size_t>(w.grp[g + 1]) : nl;
-          if (l >= end) continue;
+          hipStream_t st = g == 0 ? sd : c->s_grp[g - 1];
+          if (!pair || i == 0) {
+            const size_t l = (w.grp.empty() ? 0 : static_cast<size_t>(w.grp[g])) + i;
+            const size_t end = g + 1 < ng ? static_cast<size_t>(w.grp[g + 1]) : nl;
+            if (l >= end) continue;
+            fa.r.frames = c->d_levels + w.lvl_off[l];
+            VTS_TRY(fused_launch(fa, c->k, w.lvl_cnt[l], st));
+          } else {
+            const size_t p = static_cast<size_t>(w.pr_grp[g]) + i - 1;
+            if (p >= static_cast<size_t>(w.pr_grp[g + 1])) continue;
+            ta.chains = c->d_pair + w.pr_off[p];
+            VTS_TRY(pair_launch(ta, w.pr_cnt[p], st));
+          }
           any = true;
-          fa.r.frames = c->d_levels + w.lvl_off[l];
-          VTS_TRY(fused_launch(fa, c->k, w.lvl_cnt[l], g == 0 ? sd : c->s_grp[g - 1]));
         }
         if (!any) break;
       }
@@ -1330,8 +1393,9 @@ int vts::submit_all(vts_ctx *c) {
         HIP_TRY(hipStreamWaitEvent(sd, c->ev_grp[g - 1], 0));
       }
       HIP_TRY(hipEventRecord(LE[2 * (nl - 1) + 1], sd));
+      if (pair) c->pair_ran = true;
     }
-    for (size_t l = 0; l < nl && !tb && w.grp.size() <= 1; ++l) {
+    for (size_t l = 0; l < nl && !tb && !pair && w.grp.size() <= 1; ++l) {
       if (l == 0 || static_cast<int32_t>(l) == w.chunk_end[j - 1]) {
         HIP_TRY(hipStreamWaitEvent(sd, LE[2 * nl + j++], 0));  // this launch's slices are parsed
         // reconstruct span starts once its first launch may run (a timing
@@ -1434,8 +1498,10 @@ int vts::finish_subset(vts_ctx *c) {
   }
   c->last_window_done = static_cast<int64_t>(nw) - 1;
   if (err & DEC_W_LEVEL_RANGE) {
-    // motion beyond a level-blocked launch's halo: redo with one launch per level
+    // motion beyond a level-blocked or paired launch's halo: redo with one
+    // launch per level, and stay there for the session's life
     c->tb_off = true;
+    c->pair_off = true;
     return run_all(c);
   }
   for (const Window &w : c->windows) c->tb_ran_sparse |= c->fused && w.tb && !c->tb_off && !keep;
@@ -1589,6 +1655,13 @@ extern "C" int vts_get_frame_nv12(vts_ctx *c, int64_t frame, uint8_t *out, int64
                   "frame %lld was decoded in LDS only (level-blocked launches keep each block's last "
                   "frame; open with vts_params.keep_frames = 1 or level_block = 1)",
                   static_cast<long long>(frame));
+    if (c->pair_ran && w.pair && c->pair_first[static_cast<size_t>(frame)]) {
+      // the paired schedule did not store this frame: decode again with one
+      // launch per level (which stores every frame), from now on
+      c->pair_off = true;
+      VTS_TRY(run_all(c));
+      return vts_get_frame_nv12(c, frame, out, out_bytes);
+    }
     const uint8_t *base = c->d_surf[wi % c->n_rings] + (frame - w.f0) * c->frame_stride;
     HIP_TRY(hipMemcpy2D(out, c->width, base, c->pitch, c->width, c->height, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy2D(out + static_cast<int64_t>(c->width) * c->height, c->width,
@@ -1672,6 +1745,15 @@ extern "C" int64_t vts_schedule_info(const vts_ctx *c, int32_t what) {
     }
     case 14:  // general decoder: the intra kernel its level launches run (0: subset decoder)
       return c->general ? intra_kernel_for(c->intra_kernel, c->fprm.mb_width, c->fprm.mb_height) : 0;
+    case 15:    // paired launches per run (0 when the per-level schedule runs)
+    case 16: {  // chains over all paired launches
+      if (c->pair_off || !c->fused || c->general || c->small.on) return 0;
+      int64_t n = 0;
+      for (const Window &w : c->windows)
+        if (w.pair)
+          for (int32_t k : w.pr_cnt) n += what == 15 ? 1 : k;
+      return n;
+    }
     default: return fail(VTS_E_INVALID, "unknown schedule field %d", what);
   }
 }
@@ -1693,6 +1775,7 @@ extern "C" int vts_close(vts_ctx *c) {
   f(c->d_slices);
   f(c->d_levels);
   f(c->d_tb);
+  f(c->d_pair);
   f(c->d_post);
   for (int r = 0; r < 2; ++r) {
     f(c->d_cmd[r]);
